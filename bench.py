@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- FA2 fwd+bwd TFLOP/s at (B=4,H=16,N=8192,d=128) on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic bf16 Q/K/V/dO already
@@ -9,15 +9,27 @@ resident in HBM: fa2_forward then fa2_backward (delta + the single five-product 
 of libfa2_mi355x.so.  W untimed warm-up steps, then EXACTLY K steps bracketed by a barrier +
 torch.cuda.synchronize() on both sides; rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, the warm-up, the K timed steps, the dump
+of --dump-outputs and the line.  --full adds everything else the line has carried: the
+per-kernel timings and the `roofline` object, the `sustained` window, the device's bare-MFMA
+ceiling, the `side_figures`, the CPU baseline and the ring leg (each still switched off by its
+--no-* option).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned, as
+float32 .npy files: L.npy (B, H, N) whole, and O.npy, dQ.npy, dK.npy, dV.npy as the same fixed,
+seeded sample of DUMP_ROWS of the B*H*N rows (numpy default_rng(DUMP_SEED), sorted), each
+(DUMP_ROWS, d).  The inputs come from a seeded generator, so two runs with the same arguments
+compute on the same data.
+
 N > 1 ranks: the path shards over independent (batch, head) slabs with no data-path
 collective, so every rank runs the full (4,16,8192,128) batch of its own ("weak" scaling) and
 `value` is the total flops of all ranks / the slowest rank's time.  The sequence-sharded ring
-forward (the path's one real exchange step, RCCL send/recv over xGMI) is timed afterwards and
-reported in the extra "ring" object when the ring library is available.
+forward (the path's one real exchange step, RCCL send/recv over xGMI) is timed afterwards by a
+--full run and reported in the extra "ring" object when the ring library is available.
 
 Flop model: fwd 4 B H N^2 d, bwd 10 B H N^2 d (five block products), fwd+bwd 14.
 At this shape fa2_backward runs the single five-product kernel (csrc/fa2_bwd_fused.hip); the two-kernel
-form, which executes seven products for the same five, is timed beside it (`two_kernel_backward_ms`).
+form, which executes seven products for the same five, is timed beside it by a --full run (`two_kernel_backward_ms`).
 """
 import argparse
 import json
@@ -41,6 +53,10 @@ PEAK_FP8_TFLOPS = 5033.2    # dense fp8 MFMA (v_mfma_f32_32x32x64_f8f6f4): twice
 # PMC evidence for the two side configurations (MFMA-busy, clock, VALU / LDS / wait split, FETCH / WRITE): see profiles/README.md
 SIDE_PMC_FILE = os.path.join("profiles", "r3_e_side_pmc_summary.txt")
 B, H, N, D = 4, 16, 8192, 128
+# Steps run after the four one-time steps of a plain run, where a --full run takes its per-kernel timings (~0.35 s of
+# launches): they bring the GPU out of its idle power state, so that the headline is the sustained figure whatever W is.
+RAMP_STEPS = 60
+DUMP_ROWS, DUMP_SEED = 16384, 0     # --dump-outputs: 4 x 16384 x 128 x 4 B = 32 MiB of rows, plus L (2 MiB)
 
 
 def parse():
@@ -52,7 +68,14 @@ def parse():
     ap.add_argument("--no-ring", action="store_true")
     ap.add_argument("--no-sustained", action="store_true")
     ap.add_argument("--sustained-steps", type=int, default=350)     # 350 x ~6 ms > 2 s
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, sustained, side figures, CPU baseline, ring")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def timed(fn, iters, torch):
@@ -82,6 +105,53 @@ def median_ms(fn, torch, repeats=3, iters=10):
     """Median over `repeats` timings of `iters` launches each (HIP events on the launch stream)."""
     vals = sorted(timed(fn, iters, torch) for _ in range(repeats))
     return vals[len(vals) // 2]
+
+
+def roofline_object(k_ms, two_kernel_ms, value, world, box):
+    """The `roofline` object of a --full run, from the per-kernel timings taken before the warm-up."""
+    # MFMA flops each launch executes = the ALGORITHMIC flops it delivers: forward 2 block products, backward 5 (S, dP, dV,
+    # dK, dQ, each formed once by the single kernel).  The two-kernel form executes 3 + 4 for the same five.
+    prod = 2.0 * B * H * N * N * D
+    k_flops = {"fa2_fwd1_bf16_kernel": 2 * prod, "fa2_bwd_fused_kernel": 5 * prod}
+    k_alg = dict(k_flops)
+    dom = max(k_flops, key=lambda k: k_ms[k])
+    achieved = k_alg[dom] / (k_ms[dom] * 1e-3) / 1e12
+    traffic, traffic_src = pmc_traffic(dom)
+    roofline = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS,
+                "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                "traffic": traffic, "traffic_unit": "bytes/launch (rocprofv3 PMC)", "traffic_source": traffic_src and PMC_TRAFFIC_FILE,
+                "sustained_mfma_peak": SUSTAINED_MFMA_TFLOPS, "frac_of_sustained": round(achieved / SUSTAINED_MFMA_TFLOPS, 4),
+                "flops_per_launch": k_alg[dom], "ms_per_launch": round(k_ms[dom], 4),
+                "kernels_ms": {k: round(v, 4) for k, v in k_ms.items()},
+                "kernels_frac_executed": {k: round(k_flops[k] / (k_ms[k] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) for k in k_flops},
+                "kernels_frac_algorithmic": {k: round(k_alg[k] / (k_ms[k] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) for k in k_alg},
+                "two_kernel_backward_ms": {k: round(v, 4) for k, v in two_kernel_ms.items()},
+                "whole_path_frac": round(value / world / PEAK_BF16_TFLOPS, 4)}
+    if box is not None:
+        roofline["this_device"] = box
+        if "bare_mfma_tflops" in box:
+            roofline["frac_of_this_device_bare_mfma"] = round(achieved / box["bare_mfma_tflops"], 4)
+            roofline["whole_path_frac_of_this_device_bare_mfma"] = round(value / world / box["bare_mfma_tflops"], 4)
+    return roofline
+
+
+def sample_outputs(torch, dev, O, L, dQ, dK, dV):
+    """What the last step returned, as float32 copies on the device: L whole, and the fixed seeded sample of DUMP_ROWS of
+    the B*H*N rows of O, dQ, dK and dV (--dump-outputs)."""
+    import numpy as np
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B * H * N, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(dev)
+    out = {"L": L.float().clone()}
+    for name, t in (("O", O), ("dQ", dQ), ("dK", dK), ("dV", dV)):
+        out[name] = t.reshape(B * H * N, D).index_select(0, idx).float()
+    return out
+
+
+def write_outputs(dumped, where):
+    import numpy as np
+    os.makedirs(where, exist_ok=True)
+    for name, t in dumped.items():
+        np.save(os.path.join(where, name + ".npy"), t.cpu().numpy())
 
 
 def cpu_baseline(torch):
@@ -155,24 +225,29 @@ def main():
         fwd()
         bwd()
 
-    # ---- per-kernel launch durations (HIP events, same stream), for the roofline object.  Taken BEFORE the
-    # timed region: besides being needed below, these ~40 launches bring the GPU out of its idle power state,
-    # so that the W warm-up steps and the K timed steps that follow run at the sustained clock whatever W is
-    # (a cold start costs ~5 % on the first few steps).
+    # ---- per-kernel launch durations (HIP events, same stream), for the roofline object of a --full run; a plain run
+    # runs RAMP_STEPS whole steps in their place.  Either way, BEFORE the timed region, these launches bring the GPU out
+    # of its idle power state, so that the W warm-up steps and the K timed steps that follow run at the sustained clock
+    # whatever W is (a cold start costs ~5 % on the first few steps).
     for _ in range(4):          # one-time work (code-object load, LDS limits) and the clock ramp stay out of every timing below
         step()
     torch.cuda.synchronize()
-    it = max(5, min(args.steps, 10))
-    k_ms = {
-        "fa2_fwd1_bf16_kernel": median_ms(fwd, torch, 3, it),
-        "fa2_bwd_delta_kernel": median_ms(lambda: bwd(1), torch, 3, it),
-        # what fa2_backward runs at this shape: the single five-product kernel (with its control-block memset and the
-        # fp32 -> bf16 output pass of dQ: ~0.08 ms of the figure)
-        "fa2_bwd_fused_kernel": median_ms(lambda: bwd(8), torch, 3, it),
-    }
-    # the two-kernel form of the same backward (seven products), for comparison: FA2_BACKWARD_PATH=two_kernel selects it
-    two_kernel_ms = {"fa2_bwd_dq_kernel": median_ms(lambda: bwd(2), torch, 3, it),
-                     "fa2_bwd_dkdv_kernel": median_ms(lambda: bwd(4), torch, 3, it)}
+    if args.full:
+        it = max(5, min(args.steps, 10))
+        k_ms = {
+            "fa2_fwd1_bf16_kernel": median_ms(fwd, torch, 3, it),
+            "fa2_bwd_delta_kernel": median_ms(lambda: bwd(1), torch, 3, it),
+            # what fa2_backward runs at this shape: the single five-product kernel (with its control-block memset and the
+            # fp32 -> bf16 output pass of dQ: ~0.08 ms of the figure)
+            "fa2_bwd_fused_kernel": median_ms(lambda: bwd(8), torch, 3, it),
+        }
+        # the two-kernel form of the same backward (seven products), for comparison: FA2_BACKWARD_PATH=two_kernel selects it
+        two_kernel_ms = {"fa2_bwd_dq_kernel": median_ms(lambda: bwd(2), torch, 3, it),
+                         "fa2_bwd_dkdv_kernel": median_ms(lambda: bwd(4), torch, 3, it)}
+    else:
+        for _ in range(RAMP_STEPS):
+            step()
+        torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -183,6 +258,8 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    # the sampled outputs of the last timed step, copied at once: the --full figures below overwrite O, L, dQ, dK, dV
+    dumped = sample_outputs(torch, dev, O, L, dQ, dK, dV) if args.dump_outputs and rank == 0 else None
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -192,7 +269,7 @@ def main():
     # launches does not show what the chip holds), with the mean shader clock over the window from the device's own
     # counters (fa2_read_clocks: s_memtime / s_memrealtime x 100 MHz)
     sustained = None
-    if rank == 0 and not args.no_sustained:
+    if args.full and rank == 0 and not args.no_sustained:
         n_sus = max(args.sustained_steps, 1)
         torch.cuda.synchronize()
         clk0 = fa.ops.read_clocks()
@@ -212,7 +289,7 @@ def main():
     # of one pool differ by several per cent on power-limited kernels, so the line carries the box's own ceiling beside the
     # nominal peak.  After the timed region; ~0.2 s.
     box = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             tf, mhz = fa.ops.bare_mfma_tflops()
             box = {"bare_mfma_tflops": round(tf, 1), "clock_mhz": round(mhz, 1),
@@ -224,30 +301,6 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * flops_step / (ms_per_step * 1e-3) / 1e12
 
-    # MFMA flops each launch executes = the ALGORITHMIC flops it delivers: forward 2 block products, backward 5 (S, dP, dV,
-    # dK, dQ, each formed once by the single kernel).  The two-kernel form executes 3 + 4 for the same five.
-    prod = 2.0 * B * H * N * N * D
-    k_flops = {"fa2_fwd1_bf16_kernel": 2 * prod, "fa2_bwd_fused_kernel": 5 * prod}
-    k_alg = dict(k_flops)
-    dom = max(k_flops, key=lambda k: k_ms[k])
-    achieved = k_alg[dom] / (k_ms[dom] * 1e-3) / 1e12
-    traffic, traffic_src = pmc_traffic(dom)
-    roofline = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS,
-                "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                "traffic": traffic, "traffic_unit": "bytes/launch (rocprofv3 PMC)", "traffic_source": traffic_src and PMC_TRAFFIC_FILE,
-                "sustained_mfma_peak": SUSTAINED_MFMA_TFLOPS, "frac_of_sustained": round(achieved / SUSTAINED_MFMA_TFLOPS, 4),
-                "flops_per_launch": k_alg[dom], "ms_per_launch": round(k_ms[dom], 4),
-                "kernels_ms": {k: round(v, 4) for k, v in k_ms.items()},
-                "kernels_frac_executed": {k: round(k_flops[k] / (k_ms[k] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) for k in k_flops},
-                "kernels_frac_algorithmic": {k: round(k_alg[k] / (k_ms[k] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) for k in k_alg},
-                "two_kernel_backward_ms": {k: round(v, 4) for k, v in two_kernel_ms.items()},
-                "whole_path_frac": round(value / world / PEAK_BF16_TFLOPS, 4)}
-    if box is not None:
-        roofline["this_device"] = box
-        if "bare_mfma_tflops" in box:
-            roofline["frac_of_this_device_bare_mfma"] = round(achieved / box["bare_mfma_tflops"], 4)
-            roofline["whole_path_frac_of_this_device_bare_mfma"] = round(value / world / box["bare_mfma_tflops"], 4)
-
     out = {
         "metric": "FA2 fwd+bwd TFLOP/s at (B=4,H=16,N=8192,d=128); % MFMA peak",
         "value": round(value, 2), "unit": "TFLOP/s", "n_gpus": world, "steps": args.steps,
@@ -257,14 +310,15 @@ def main():
                                "(BASELINE configs[2]); flops = 14 B H N^2 d",
                    "B": B, "H": H, "N": N, "d": D, "parallelism": f"head-sharded replicas x{world}"},
         "pct_mfma_peak": round(100.0 * value / world / PEAK_BF16_TFLOPS, 2),
-        "roofline": roofline,
     }
+    if args.full:
+        out["roofline"] = roofline_object(k_ms, two_kernel_ms, value, world, box)
     if sustained is not None:
         out["sustained"] = sustained
 
     # ---- side figures SURVEY 8d asks for beside the headline (timed BEFORE the CPU baseline idles the GPU): forward only at BASELINE configs[1] (bf16)
     # and the fp8 causal forward of configs[4] (B and H unspecified there: B=1, H=16)
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             extra = {}
             def fwd_only(Bx, Hx, Nx, dx, dt, causal):
@@ -339,7 +393,7 @@ def main():
         except Exception as e:
             out["side_figures"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(torch)
         except Exception as e:  # the baseline is a reported side figure, never fatal
@@ -349,7 +403,8 @@ def main():
     # worker thread under a deadline; if the transport wedges (an RCCL hang cannot be interrupted) the
     # line is printed without it and the process leaves through os._exit.
     hung = False
-    if not args.no_ring:
+    ring_leg_runs = args.full and not args.no_ring
+    if ring_leg_runs:
         import threading
         box = {}
 
@@ -380,6 +435,8 @@ def main():
         elif box.get("ring") is not None:
             out["ring"] = box["ring"]
 
+    if dumped is not None:
+        write_outputs(dumped, args.dump_outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     sys.stdout.flush()
@@ -393,7 +450,7 @@ def main():
             time.sleep(5.0)
             os._exit(0)
         os._exit(3)
-    if dist is not None and not args.no_ring:
+    if dist is not None and ring_leg_runs:
         # After a ring leg the ranks may disagree on whether it finished (each has its own deadline): no
         # further collective, every rank simply leaves.  The timed region and its barriers are long past.
         if rank != 0:

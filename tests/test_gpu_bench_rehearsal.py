@@ -1,6 +1,6 @@
 """GPU: bench.py's multi-rank path rehearsed ONCE before a driver runs it on an 8-GPU node.
 
-`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ...` with FA2_BENCH_BACKEND=gloo: two ranks share
+`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 --full ...` with FA2_BENCH_BACKEND=gloo: two ranks share
 the one GPU of the test box (the launcher itself never touches the GPU, every rank is an ordinary child process), so the
 branches only world > 1 reaches -- process-group init, the barriers around the timed region, the all-reduce MAX of the
 elapsed time, `value` = all ranks' flops / the slowest rank's time, rank 0 printing the one JSON line, the shutdown --
@@ -29,7 +29,7 @@ def test_two_rank_bench_line_over_gloo():
     env = dict(os.environ, FA2_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-ring", "--sustained-steps", "24"]
+           "--full", "--no-cpu-baseline", "--no-ring", "--sustained-steps", "24"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
