@@ -553,20 +553,13 @@ static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream)
     const int nb = (a.Nq + kBwdRows - 1) / kBwdRows;
     constexpr int lds_dq = 3 * 2 * kDqKV * D * 2;      // ring of three (K tile | V tile)
     constexpr int lds_dk = kDkKeys * D * 2 + 2 * (2 * 2 * kDkQ * D * 2 + 512);
-    static bool set_dq[64] = {}, set_dk[64] = {};
-    e = ensure_dynamic_lds(fa2_bwd_dq_kernel<D, CAUSAL>, lds_dq, set_dq);
-    if (e != hipSuccess) return e;
-    e = ensure_dynamic_lds(fa2_bwd_dkdv_kernel<D, CAUSAL>, lds_dk, set_dk);
-    if (e != hipSuccess) return e;
     if (a.phases & 2) {
-        hipLaunchKernelGGL((fa2_bwd_dq_kernel<D, CAUSAL>), dim3((unsigned)(nb * a.BH)), dim3(256), lds_dq, stream, a);
-        e = hipGetLastError();
+        e = launch_lds<fa2_bwd_dq_kernel<D, CAUSAL>>(dim3((unsigned)(nb * a.BH)), dim3(256), lds_dq, stream, a);
         if (e != hipSuccess) return e;
     }
     if (a.phases & 4) {
         const int ncb = (a.Nk + kDkKeys - 1) / kDkKeys;
-        hipLaunchKernelGGL((fa2_bwd_dkdv_kernel<D, CAUSAL>), dim3((unsigned)(ncb * a.BH)), dim3(256), lds_dk, stream, a);
-        e = hipGetLastError();
+        e = launch_lds<fa2_bwd_dkdv_kernel<D, CAUSAL>>(dim3((unsigned)(ncb * a.BH)), dim3(256), lds_dk, stream, a);
     }
     return e;
 }

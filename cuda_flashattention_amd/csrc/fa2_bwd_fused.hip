@@ -1,8 +1,8 @@
 // fa2_bwd_fused.hip -- the single-kernel, five-product FlashAttention-2 backward for gfx950: what fa2_backward runs for
-// bf16, causal or not, at d = 128 (every seq_len from 897 up and every multiple of 256; padded to the key block inside: RAGGED)
-// and, since round 4, at d = 64 (HD = 64: every seq_len whose padding costs under 7 %), and what fa2_backward_block runs for the
-// ring backward's dense square and unmasked rectangular blocks (RECT).  Everything else -- short ragged lengths, masked
-// rectangular blocks -- runs the dQ and dK/dV kernels of fa2_bwd_bf16.hip.
+// bf16, causal or not, at d = 128 and, since round 4, d = 64 (HD = 64) for the lengths of the routing rule stated at fa2_backward
+// in include/fa2_mi355x.h (padded to the key block inside: RAGGED), and what fa2_backward_block runs for the ring backward's
+// dense square and unmasked rectangular blocks (RECT).  Everything else -- short ragged lengths, masked rectangular blocks --
+// runs the dQ and dK/dV kernels of fa2_bwd_bf16.hip.
 // Replaces the reference's flash_attention_2_backward_kernel (02_flash_attention_v2_backward/
 // flash_attention_backward_kernel.cu:47-246), one kernel for any N and d <= 128 there (dispatch :264-297).  Design and
 // measurements: DESIGN.md section 3.  The text below describes d = 128; the d = 64 differences are at the kernel template.
@@ -762,8 +762,8 @@ __global__ void __launch_bounds__(256) fa2_bwd_fused_rcpad_kernel(const float* _
 
 // The ordered hand-off relies on one hardware property: a workgroup's plain stores land in the L2 of the XCC whose id it
 // reads from HW_REG_XCC_ID, and sc1 loads issued on that XCC read that L2.  That was validated on gfx950 in SPX mode (one
-// device = 8 XCCs x 32 CUs = 256 CUs); on anything else the launcher does not take the chained form (fa2_backward then runs
-// the dQ and dK/dV kernels and fa2_backward_plan says why).
+// device = 8 XCCs x 32 CUs = 256 CUs); on anything else the backward's route (fa2_capi.cpp) does not take the chained form
+// (fa2_backward then runs the dQ and dK/dV kernels and fa2_backward_plan says why).
 bool bwd_fused_device_ok(const char** why)
 {
     static int verdict[64] = {};          // 0 = unknown, 1 = ok, 2 = not gfx950, 3 = not 256 CUs
@@ -798,6 +798,17 @@ hipError_t bwd_fused_clear_error(int* ctl, hipStream_t stream)
 // (the last 8 ints per unit are only written by -DFA2_FUSED_STATS builds: tools/gpu_stats_fused.py)
 size_t bwd_fused_ctl_bytes(int BH, int N) { return (size_t)(kCtlHeadmap + 16 * (BH + kHmPad) + 9 * BH * ((N + 255) / 256)) * sizeof(int); }
 
+// the chained instance of a dense square problem at head_dim HD
+template <int HD>
+static hipError_t launch_chained_square(bool causal, bool ragged, dim3 grid, int lds, hipStream_t stream, const FusedArgs& fa)
+{
+    if (causal)
+        return ragged ? launch_lds<fa2_bwd_fused_kernel<true, true, true, false, HD>>(grid, dim3(256), lds, stream, fa)
+                      : launch_lds<fa2_bwd_fused_kernel<true, true, false, false, HD>>(grid, dim3(256), lds, stream, fa);
+    return ragged ? launch_lds<fa2_bwd_fused_kernel<true, false, true, false, HD>>(grid, dim3(256), lds, stream, fa)
+                  : launch_lds<fa2_bwd_fused_kernel<true, false, false, false, HD>>(grid, dim3(256), lds, stream, fa);
+}
+
 hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int mode, hipStream_t stream, float* rcpad)
 {
     const int npad = (a.Nk + 255) / 256 * 256;
@@ -811,7 +822,6 @@ hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int m
         return hipErrorInvalidValue;
     if (ragged && (mode != 1 || !rcpad)) return hipErrorInvalidValue;
     if (a.causal && (mode != 1 || a.causal_shift != 0)) return hipErrorInvalidValue;
-    if (mode == 1 && (a.phases & 8) && !bwd_fused_device_ok(nullptr)) return hipErrorNotSupported;
     hipError_t e = hipSuccess;
     if (a.phases & 1) {
         BwdArgs d = a;
@@ -836,10 +846,7 @@ hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int m
         if (e != hipSuccess) return e;
         e = bwd_fused_clear_error(ctl, stream);
         if (e != hipSuccess) return e;
-        static bool set_f[64] = {};
-        e = ensure_dynamic_lds(fa2_bwd_fused_kernel<false, false>, lds, set_f);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((fa2_bwd_fused_kernel<false, false>), dim3((unsigned)units), dim3(256), lds, stream, fa);
+        e = launch_lds<fa2_bwd_fused_kernel<false, false>>(dim3((unsigned)units), dim3(256), lds, stream, fa);
     } else {
         static int cus[64] = {};
         int dev = 0;
@@ -856,7 +863,6 @@ hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int m
         // the (1,4,1024,128) test replayed fine).  A kernel node replays like any other launch.
         e = launch_fill_f32(reinterpret_cast<float*>(ctl), bwd_fused_ctl_bytes(a.BH, a.Nk) / sizeof(float), 0.0f, stream);
         if (e != hipSuccess) return e;
-        static bool set_t[64] = {}, set_c[64] = {};
         // a.reserve_cus: the ring backward's exchanges (RCCL kernels on the communication stream) must find a CU while this
         // grid runs -- its workgroups are persistent and fill a CU's register file, nothing else becomes resident beside them
         int avail = cus[dev] - (a.reserve_cus > 0 ? a.reserve_cus : 0);
@@ -867,46 +873,12 @@ hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int m
         if (g_hook_grid >= 1 && g_hook_grid < wgs) wgs = g_hook_grid;
         FA2_HOOK_NOTE_GRID(wgs);
         const dim3 grid((unsigned)wgs);
-        static bool set_cr[64] = {}, set_tr[64] = {}, set_re[64] = {}, set_64[64] = {}, set_64c[64] = {}, set_64r[64] = {}, set_64cr[64] = {};
-        if (a.d == 64 && a.causal && ragged) {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, true, true, false, 64>, lds, set_64cr);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, true, true, false, 64>), grid, dim3(256), lds, stream, fa);
-        } else if (a.d == 64 && ragged) {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, false, true, false, 64>, lds, set_64r);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, false, true, false, 64>), grid, dim3(256), lds, stream, fa);
-        } else if (a.d == 64 && a.causal) {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, true, false, false, 64>, lds, set_64c);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, true, false, false, 64>), grid, dim3(256), lds, stream, fa);
-        } else if (a.d == 64) {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, false, false, false, 64>, lds, set_64);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, false, false, false, 64>), grid, dim3(256), lds, stream, fa);
-        } else if (rect) {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, false, false, true>, lds, set_re);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, false, false, true>), grid, dim3(256), lds, stream, fa);
-        } else if (a.causal && ragged) {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, true, true>, lds, set_cr);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, true, true>), grid, dim3(256), lds, stream, fa);
-        } else if (a.causal) {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, true>, lds, set_c);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, true>), grid, dim3(256), lds, stream, fa);
-        } else if (ragged) {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, false, true>, lds, set_tr);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, false, true>), grid, dim3(256), lds, stream, fa);
-        } else {
-            e = ensure_dynamic_lds(fa2_bwd_fused_kernel<true, false>, lds, set_t);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fa2_bwd_fused_kernel<true, false>), grid, dim3(256), lds, stream, fa);
-        }
+        if (rect)
+            e = launch_lds<fa2_bwd_fused_kernel<true, false, false, true>>(grid, dim3(256), lds, stream, fa);
+        else
+            e = a.d == 64 ? launch_chained_square<64>(a.causal, ragged, grid, lds, stream, fa)
+                          : launch_chained_square<128>(a.causal, ragged, grid, lds, stream, fa);
     }
-    e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (mode == 0)
         hipLaunchKernelGGL(fa2_bwd_fused_dq_out_kernel, dim3(2048), dim3(256), 0, stream, dQacc, (__bf16*)a.dQ, elems / 8, a.scale,

@@ -178,36 +178,36 @@ int fa2_forward_fp8_scaled(const void* Q, const void* K, const void* V, void* O,
     return hip_status(fa2::launch_fwd_fp8(a, (hipStream_t)stream));
 }
 
-// D = rowsum(dO o O), then the two row-constant planes (-L/scale, -D) of the kernels that own key blocks
-static size_t bwd_base_ws(int B, int H, int rows) { return 3 * align256((size_t)B * H * rows * sizeof(float)); }
-
 // shapes the single-kernel (five-product) backward takes: csrc/fa2_bwd_fused.hip.  Any seq_len: its loops run on the length
 // rounded up to a multiple of 256 (keys past the end are masked, rows past the end get row constants that make P vanish), so
-// it is taken whenever that padding costs less than the two extra block products of the two-kernel form, whose own tiles are
-// 64 keys: 5 x roundup(N, 256) <= 7 x roundup(N, 64) -- every N >= 897, and the N just below a multiple of 256 under that.
+// it is taken whenever that padding costs less than the two extra block products of the two-kernel form (64-key tiles), and
+// at head_dim 64, where it is ~10 % ahead of the two kernels (half the MFMAs beside the same VALU and hand-off work), whenever
+// the padding costs under 7 %.  The sets these inequalities give: include/fa2_mi355x.h, fa2_backward.
 static int fused_npad(int n) { return (n + 255) / 256 * 256; }
 static bool bwd_fused_shape(int seq_len, int head_dim, int dtype)
 {
     if (dtype != FA2_DTYPE_BF16 || seq_len < 1) return false;
     const long long np = fused_npad(seq_len), n64 = (seq_len + 63) / 64 * 64;
-    // head_dim 64 (round 4): the single kernel is ~10 % ahead of the two kernels there (the same VALU and hand-off work beside half
-    // the MFMAs), so padding to the key block may cost 7 % at most: every multiple of 256, the lengths just below one, every N >= 3329
     if (head_dim == 64) return 13 * np <= 14 * n64 && np * 128 * 4 <= 0x7fffffffLL;
     if (head_dim != 128) return false;
     return 5 * np <= 7 * n64 && np * head_dim * 4 <= 0x7fffffffLL;
 }
-// workspace behind the D / row-constant planes: fp32 dQ sums [BH][NP][d] | control block | (ragged only) padded row constants
-struct FusedWs { float* acc; int* ctl; float* rcpad; size_t bytes; };
-static FusedWs fused_ws(void* base, int B, int H, int seq_len, int head_dim)
+
+// The backward workspace for `rows` rows per head (a block's q_head_stride), each part 256-byte aligned: D [BH][rows] | RC
+// [2][BH][rows] (-L/scale, -D) | then, where the single kernel takes the shape (`single`), its fp32 dQ sums [BH][NP][128]
+// (128 floats per row at either head_dim) | control block | (ragged rows only) RC padded to NP rows (NP = roundup(rows, 256)).
+struct BwdWs { bool single; float *D, *RC, *acc; int* ctl; float* rcpad; size_t base_bytes, bytes; };
+static BwdWs bwd_ws(const void* base, int B, int H, int rows, int head_dim, int dtype)
 {
-    const int np = fused_npad(seq_len);
-    (void)head_dim;      // the running sums are [np / 32 sub-tiles][4 waves][32 x 32] fp32 at either head_dim: 128 floats per row
-    const size_t a = align256((size_t)B * H * np * 128 * 4), c = align256(fa2::bwd_fused_ctl_bytes(B * H, np));
-    const size_t r = np != seq_len ? align256((size_t)2 * B * H * np * sizeof(float)) : 0;
-    char* b = (char*)base;
-    return FusedWs{(float*)b, (int*)(b + a), r ? (float*)(b + a + c) : nullptr, a + c + r};
+    const int np = fused_npad(rows);
+    const bool single = bwd_fused_shape(rows, head_dim, dtype);
+    const size_t plane = align256((size_t)B * H * rows * sizeof(float)), acc = align256((size_t)B * H * np * 128 * 4);
+    const size_t ctl = single ? align256(fa2::bwd_fused_ctl_bytes(B * H, np)) : 0;
+    const size_t pad = np != rows ? align256((size_t)2 * B * H * np * 4) : 0;
+    char* b = (char*)const_cast<void*>(base);
+    return BwdWs{single, (float*)b, (float*)(b + plane), (float*)(b + 3 * plane), (int*)(b + 3 * plane + acc),
+                 pad ? (float*)(b + 3 * plane + acc + ctl) : nullptr, 3 * plane, 3 * plane + (single ? acc + ctl + pad : 0)};
 }
-static size_t bwd_fused_ws(int B, int H, int seq_len, int head_dim) { return fused_ws(nullptr, B, H, seq_len, head_dim).bytes; }
 
 // FA2_BACKWARD_PATH=two_kernel keeps fa2_backward on the two deterministic kernels for every shape (A/B runs, triage)
 static bool bwd_fused_allowed()
@@ -219,17 +219,138 @@ static bool bwd_fused_allowed()
     return allowed;
 }
 
-size_t fa2_backward_workspace_bytes(int B, int H, int seq_len, int head_dim, int dtype)
+enum class Entry { phases, block, fused, status, plan };      // the public entry point that asks
+enum class Path { none, f32, two_kernel, single };
+struct Route {
+    int status = FA2_OK;
+    Path path = Path::none;
+    int mode = 1;                 // single: 0 = dQ by fp32 atomics, 1 = the ordered hand-off
+    bool clear_error = false;     // two kernels on a workspace with a control block: its error word must describe this call
+    fa2::BwdArgs args{};
+    BwdWs ws{};
+    const char* why = "";         // fa2_backward_plan's reason
+};
+
+// The one place the backward is routed (the rule: include/fa2_mi355x.h, fa2_backward): validation in the order of the asking
+// entry point, then what to run, its arguments and its workspace.  `t` holds the nine tensors (none for status and plan);
+// `phases` is fa2_backward_fused's mode.
+static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int q_len, int kv_len, int q_stride, int kv_stride,
+                       int q_row0, int d, int dtype, int causal, int shift, float scale, int phases, const void* ws, size_t ws_bytes)
 {
-    if (B <= 0 || H <= 0 || seq_len <= 0) return 0;
-    return bwd_base_ws(B, H, seq_len) + (bwd_fused_shape(seq_len, head_dim, dtype) ? bwd_fused_ws(B, H, seq_len, head_dim) : 0);
+    Route r;
+    const auto fail = [&r](int st) { r.status = st; return r; };
+    const auto device_ok = [&r] { return fa2::bwd_fused_device_ok(&r.why); };
+    const auto env_and_device_ok = [&] { return bwd_fused_allowed() && device_ok(); };      // rules (b) and (c)
+    if (entry <= Entry::fused && (!t.Q || !t.K || !t.V || !t.O || !t.L || !t.dO || !t.dQ || !t.dK || !t.dV))
+        return fail(FA2_ERR_NULL_POINTER);
+    const int q_hs = q_stride ? q_stride : q_len, k_hs = kv_stride ? kv_stride : kv_len;
+    switch (entry) {
+    case Entry::phases:      // phases: 1 = D and the row constants, 2 = dQ kernel, 4 = dK/dV kernel, 8 = the single kernel
+        if ((r.status = check_common(B, H, q_len, d, scale))) return r;
+        if (dtype == FA2_DTYPE_FP8_E4M3) return fail(FA2_ERR_UNSUPPORTED_DTYPE);      // fp8 is forward only
+        if ((r.status = check_dim(d, dtype))) return r;
+        r.ws = bwd_ws(ws, B, H, q_len, d, dtype);
+        if (!ws || ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
+        if (dtype == FA2_DTYPE_F32) { r.path = Path::f32; r.args.phases = phases & 7; break; }
+        if ((r.status = check_bwd_planes(B, H, q_len))) return r;
+        // bit 3 does not combine with bits 1 and 2 (two ways of computing the same outputs); 7 takes the single kernel where
+        // the rule allows it (7 | 16 and 6: the two kernels)
+        if ((phases & 8) && ((phases & 6) || !r.ws.single || !device_ok())) return fail(FA2_ERR_UNSUPPORTED);
+        if ((phases & 8) || (phases == 7 && r.ws.single && env_and_device_ok())) {
+            r.path = Path::single; r.args.phases = phases == 7 ? 9 : (phases & 9);
+        } else {
+            r.path = Path::two_kernel; r.args.phases = phases & 7; r.clear_error = r.ws.single;
+        }
+        break;
+    case Entry::block: {
+        r.status = check_common(B, H, q_len, d, scale);
+        if (!r.status) r.status = check_common(B, H, kv_len > 0 ? kv_len : 1, d, scale);
+        if (!r.status) r.status = check_common(B, H, q_hs > 0 ? q_hs : 1, d, scale);
+        if (r.status) return r;
+        if (kv_len <= 0 || q_row0 < 0 || q_hs < q_row0 + q_len || k_hs < kv_len) return fail(FA2_ERR_INVALID_SHAPE);
+        if ((r.status = check_bwd_planes(B, H, q_hs))) return r;
+        if (dtype != FA2_DTYPE_BF16) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
+        if ((r.status = check_dim(d, dtype))) return r;
+        r.ws = bwd_ws(ws, B, H, q_hs, d, dtype);      // the square problem's layout for q_hs rows, whatever the block
+        if (!ws || ws_bytes < r.ws.base_bytes) return fail(FA2_ERR_WORKSPACE);
+        const bool ctl = r.ws.single && ws_bytes >= r.ws.bytes;      // room for the running sums and a control block
+        const bool square = q_len == kv_len && q_hs == q_len && k_hs == kv_len && q_row0 == 0 && (!causal || shift == 0);
+        const bool rect = !causal && d == 128 && q_len % 32 == 0 && q_len >= 512 && kv_len % 256 == 0 && kv_len <= fused_npad(q_hs);
+        if ((phases & 6) == 6 && (square || rect) && ctl && env_and_device_ok()) {
+            r.path = Path::single; r.args.phases = 8 | (phases & 1);
+            // bits 8..15: how many CUs to leave (FA2_PHASE_LEAVE_CUS(n)); 0 there = the default of 16
+            r.args.reserve_cus = (phases & FA2_PHASE_LEAVE_ROOM) ? (((phases >> 8) & 0xff) ? ((phases >> 8) & 0xff) : 16) : 0;
+        } else {
+            r.path = Path::two_kernel; r.args.phases = phases & 7; r.clear_error = ctl;
+        }
+        break;
+    }
+    case Entry::fused:
+        if ((r.status = check_common(B, H, q_len, d, scale)) || (r.status = check_bwd_planes(B, H, q_len))) return r;
+        r.ws = bwd_ws(ws, B, H, q_len, d, FA2_DTYPE_BF16);
+        if (!r.ws.single || (phases != 0 && phases != 1)) return fail(FA2_ERR_UNSUPPORTED);
+        if (phases == 0 && (q_len % 256 != 0 || d != 128)) return fail(FA2_ERR_UNSUPPORTED);      // the atomics form: d = 128, aligned
+        if (phases == 1 && !device_ok()) return fail(FA2_ERR_UNSUPPORTED);
+        if (!ws || ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
+        r.path = Path::single; r.mode = phases; r.args.phases = 9;
+        break;
+    case Entry::status:      // Path::single: read the error word.  Where this process never runs the single kernel (shape,
+                             // environment or device) the caller's buffer is not to be trusted: Path::none, drain the stream
+        if (!ws) return fail(FA2_ERR_NULL_POINTER);
+        if (B <= 0 || H <= 0 || q_len <= 0) return fail(FA2_ERR_INVALID_SHAPE);
+        r.ws = bwd_ws(ws, B, H, q_len, d, dtype);
+        if (!r.ws.single || !env_and_device_ok()) break;
+        if (ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
+        r.path = Path::single;
+        break;
+    case Entry::plan:
+        if (B <= 0 || H <= 0 || q_len <= 0) return fail(FA2_ERR_INVALID_SHAPE);
+        if (dtype == FA2_DTYPE_FP8_E4M3) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
+        if ((r.status = check_dim(d, dtype))) return r;
+        r.path = dtype == FA2_DTYPE_F32 ? Path::f32 : Path::two_kernel;
+        if (dtype == FA2_DTYPE_F32) r.why = "fp32 path (exact f32 MFMA kernels)";
+        else if (!bwd_fused_shape(q_len, d, dtype))
+            r.why = "two kernels: the single kernel takes bf16 with head_dim 128 and a seq_len whose padding to a multiple of 256 "
+                    "costs less than two block products (5 roundup(N,256) <= 7 roundup(N,64)), or head_dim 64 and a seq_len whose "
+                    "padding costs less than 7 % (13 roundup(N,256) <= 14 roundup(N,64))";
+        else if (!bwd_fused_allowed()) r.why = "two kernels: FA2_BACKWARD_PATH=two_kernel";
+        else if (device_ok()) r.path = Path::single;
+        return r;
+    }
+    fa2::BwdArgs& a = r.args;
+    a.Q = t.Q; a.K = t.K; a.V = t.V; a.O = t.O; a.dO = t.dO; a.L = t.L; a.dQ = t.dQ; a.dK = t.dK; a.dV = t.dV;
+    a.D = r.ws.D; a.RC = r.ws.RC; a.BH = B * H; a.Nq = q_len; a.Nk = kv_len; a.d = d;
+    a.q_hs = q_hs; a.k_hs = k_hs; a.q_row0 = q_row0; a.scale = scale; a.causal = causal ? 1 : 0; a.causal_shift = causal ? shift : 0;
+    return r;
 }
 
-static int backward_block_impl(const void* Q, const void* K, const void* V, const void* O, const float* L,
-                               const void* dO, void* dQ, void* dK, void* dV,
-                               int B, int H, int q_len, int kv_len, int head_dim, float softmax_scale, int dtype,
-                               int q_head_stride, int kv_head_stride, int q_row0, int causal, int causal_shift,
-                               void* workspace, size_t workspace_bytes, void* stream, int phases, bool allow_single);
+static int bwd_launch(const Route& r, void* stream)
+{
+    const hipStream_t s = (hipStream_t)stream;
+    const fa2::BwdArgs& a = r.args;
+    if (r.status) return r.status;
+    if (r.clear_error) {
+        const hipError_t e = fa2::bwd_fused_clear_error(r.ws.ctl, s);
+        if (e != hipSuccess) return hip_status(e);
+    }
+    if (r.path == Path::single) return hip_status(fa2::launch_bwd_fused_bf16(a, r.ws.acc, r.ws.ctl, r.mode, s, r.ws.rcpad));
+    if (r.path == Path::two_kernel) return hip_status(fa2::launch_bwd_bf16(a, s));
+    const fa2::F32Args f{(const float*)a.Q, (const float*)a.K, (const float*)a.V, (float*)a.O, (float*)a.L, (const float*)a.dO,
+                         (float*)a.dQ, (float*)a.dK, (float*)a.dV, a.D, a.BH, a.Nq, a.d, a.scale, a.causal, a.phases};
+    return hip_status(fa2::launch_bwd_f32(f, s));
+}
+
+size_t fa2_backward_workspace_bytes(int B, int H, int seq_len, int head_dim, int dtype)
+{
+    return B <= 0 || H <= 0 || seq_len <= 0 ? 0 : bwd_ws(nullptr, B, H, seq_len, head_dim, dtype).bytes;
+}
+
+size_t fa2_backward_fused_workspace_bytes(int B, int H, int seq_len, int head_dim)
+{
+    if (B <= 0 || H <= 0 || seq_len <= 0) return 0;
+    const BwdWs w = bwd_ws(nullptr, B, H, seq_len, head_dim, FA2_DTYPE_BF16);
+    return w.single ? w.bytes : 0;
+}
 
 int fa2_backward(const void* Q, const void* K, const void* V, const void* O, const float* L,
                  const void* dO, void* dQ, void* dK, void* dV,
@@ -246,151 +367,8 @@ int fa2_backward_phases(const void* Q, const void* K, const void* V, const void*
                         int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream,
                         int phases)
 {
-    if (!Q || !K || !V || !O || !L || !dO || !dQ || !dK || !dV) return FA2_ERR_NULL_POINTER;
-    int st = check_common(B, H, seq_len, head_dim, softmax_scale);
-    if (st) return st;
-    if (dtype == FA2_DTYPE_FP8_E4M3) return FA2_ERR_UNSUPPORTED_DTYPE;      // fp8 is forward only
-    st = check_dim(head_dim, dtype);
-    if (st) return st;
-    if (!workspace || workspace_bytes < fa2_backward_workspace_bytes(B, H, seq_len, head_dim, dtype))
-        return FA2_ERR_WORKSPACE;
-    if (dtype == FA2_DTYPE_BF16) {
-        st = check_bwd_planes(B, H, seq_len);
-        if (st) return st;
-        // phases: 1 = D and the row constants, 2 = dQ kernel, 4 = dK/dV kernel, 8 = the single five-product kernel + its
-        // output pass.  7 ("all of it") takes the single kernel where the shape and the device allow (d = 128,
-        // seq_len % 256 == 0, gfx950 with all 256 CUs); bit 3 does not combine with bits 1 and 2 (they are two ways of
-        // computing the same outputs).
-        const bool fused_ok = bwd_fused_shape(seq_len, head_dim, dtype);
-        if ((phases & 8) && (phases & 6)) return FA2_ERR_UNSUPPORTED;
-        if ((phases & 8) && (!fused_ok || !fa2::bwd_fused_device_ok(nullptr))) return FA2_ERR_UNSUPPORTED;
-        if ((phases & 8) || (phases == 7 && fused_ok && bwd_fused_allowed() && fa2::bwd_fused_device_ok(nullptr))) {
-            fa2::BwdArgs a{};
-            a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.L = L; a.dQ = dQ; a.dK = dK; a.dV = dV;
-            a.D = (float*)workspace; a.BH = B * H; a.Nq = seq_len; a.Nk = seq_len; a.d = head_dim;
-            a.RC = (float*)((char*)workspace + align256((size_t)B * H * seq_len * sizeof(float)));
-            a.q_hs = seq_len; a.k_hs = seq_len; a.q_row0 = 0; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.causal_shift = 0;
-            a.phases = phases == 7 ? 9 : (phases & 9);
-            const FusedWs w = fused_ws((char*)workspace + bwd_base_ws(B, H, seq_len), B, H, seq_len, head_dim);
-            return hip_status(fa2::launch_bwd_fused_bf16(a, w.acc, w.ctl, 1, (hipStream_t)stream, w.rcpad));
-        }
-        if (fused_ok) {
-            // the workspace has a control block whose error word fa2_backward_status reads: it must describe THIS call, also
-            // when the two kernels run it (FA2_BACKWARD_PATH, a device that is not the validated layout, phases 2 | 4)
-            const FusedWs w = fused_ws((char*)workspace + bwd_base_ws(B, H, seq_len), B, H, seq_len, head_dim);
-            const hipError_t e = fa2::bwd_fused_clear_error(w.ctl, (hipStream_t)stream);
-            if (e != hipSuccess) return hip_status(e);
-        }
-        return backward_block_impl(Q, K, V, O, L, dO, dQ, dK, dV, B, H, seq_len, seq_len, head_dim, softmax_scale, dtype, 0, 0, 0,
-                                   causal, 0, workspace, workspace_bytes, stream, phases, false);     // phases 6 here = the two kernels
-    }
-    fa2::F32Args a{};
-    a.Q = (const float*)Q; a.K = (const float*)K; a.V = (const float*)V; a.O = (float*)O;
-    a.L = (float*)L; a.dO = (const float*)dO; a.dQ = (float*)dQ; a.dK = (float*)dK; a.dV = (float*)dV;
-    a.D = (float*)workspace; a.BH = B * H; a.N = seq_len; a.d = head_dim;
-    a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.phases = phases & 7;
-    return hip_status(fa2::launch_bwd_f32(a, (hipStream_t)stream));
-}
-
-int fa2_backward_plan(int B, int H, int seq_len, int head_dim, int dtype, int causal, const char** reason)
-{
-    (void)causal;
-    static const char* const kShape = "two kernels: the single kernel takes bf16 with head_dim 128 and a seq_len whose padding to a "
-                                      "multiple of 256 costs less than two block products (5 roundup(N,256) <= 7 roundup(N,64)), or "
-                                      "head_dim 64 and a seq_len whose padding costs less than 7 % (13 roundup(N,256) <= 14 roundup(N,64))";
-    static const char* const kEnv = "two kernels: FA2_BACKWARD_PATH=two_kernel";
-    static const char* const kF32 = "fp32 path (exact f32 MFMA kernels)";
-    if (reason) *reason = "";
-    if (B <= 0 || H <= 0 || seq_len <= 0) return FA2_ERR_INVALID_SHAPE;
-    if (dtype == FA2_DTYPE_FP8_E4M3) return FA2_ERR_UNSUPPORTED_DTYPE;
-    int st = check_dim(head_dim, dtype);
-    if (st) return st;
-    if (dtype == FA2_DTYPE_F32) { if (reason) *reason = kF32; return 2; }
-    if (!bwd_fused_shape(seq_len, head_dim, dtype)) { if (reason) *reason = kShape; return 2; }
-    if (!bwd_fused_allowed()) { if (reason) *reason = kEnv; return 2; }
-    const char* why = "";
-    const bool ok = fa2::bwd_fused_device_ok(&why);
-    if (reason) *reason = why;
-    return ok ? 1 : 2;
-}
-
-int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,
-                        void* stream)
-{
-    if (!workspace) return FA2_ERR_NULL_POINTER;
-    if (B <= 0 || H <= 0 || seq_len <= 0) return FA2_ERR_INVALID_SHAPE;
-    // no hand-off, nothing that can time out: only drain the stream.  (A workspace of a single-kernel shape always carries an
-    // error word written by the LAST backward on it -- every launch path clears or sets it -- but where this process never
-    // runs the single kernel, environment or device, there is no reason to trust what the caller's buffer holds.)
-    if (!bwd_fused_shape(seq_len, head_dim, dtype) || !bwd_fused_allowed() || !fa2::bwd_fused_device_ok(nullptr)) {
-        return hip_status(hipStreamSynchronize((hipStream_t)stream));
-    }
-    if (workspace_bytes < fa2_backward_workspace_bytes(B, H, seq_len, head_dim, dtype)) return FA2_ERR_WORKSPACE;
-    const FusedWs w = fused_ws((char*)const_cast<void*>(workspace) + bwd_base_ws(B, H, seq_len), B, H, seq_len, head_dim);
-    int err = 0;
-    hipError_t e = fa2::bwd_fused_read_error(w.ctl, &err, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_status(e);
-    return err ? FA2_ERR_HANDOFF_TIMEOUT : FA2_OK;
-}
-
-static int backward_block_impl(const void* Q, const void* K, const void* V, const void* O, const float* L,
-                       const void* dO, void* dQ, void* dK, void* dV,
-                       int B, int H, int q_len, int kv_len, int head_dim, float softmax_scale, int dtype,
-                       int q_head_stride, int kv_head_stride, int q_row0, int causal, int causal_shift,
-                       void* workspace, size_t workspace_bytes, void* stream, int phases, bool allow_single)
-{
-    if (!Q || !K || !V || !O || !L || !dO || !dQ || !dK || !dV) return FA2_ERR_NULL_POINTER;
-    const int q_hs = q_head_stride ? q_head_stride : q_len, k_hs = kv_head_stride ? kv_head_stride : kv_len;
-    int st = check_common(B, H, q_len, head_dim, softmax_scale);
-    if (!st) st = check_common(B, H, kv_len > 0 ? kv_len : 1, head_dim, softmax_scale);
-    if (!st) st = check_common(B, H, q_hs > 0 ? q_hs : 1, head_dim, softmax_scale);
-    if (st) return st;
-    if (kv_len <= 0 || q_row0 < 0 || q_hs < q_row0 + q_len || k_hs < kv_len) return FA2_ERR_INVALID_SHAPE;
-    st = check_bwd_planes(B, H, q_hs);
-    if (st) return st;
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
-    st = check_dim(head_dim, dtype);
-    if (st) return st;
-    if (!workspace || workspace_bytes < bwd_base_ws(B, H, q_hs)) return FA2_ERR_WORKSPACE;
-    // A dense square block (the ring backward's unit whenever the local length is a multiple of 256: every non-causal step,
-    // and the local causal block) IS a problem the single five-product kernel takes -- L being the log-sum-exp over more
-    // keys than the block's changes nothing for it.  Taken when both main kernels are asked for at once (phases 6 or 7),
-    // the workspace has room for its running sums and the device is the validated layout; otherwise the two kernels.
-    // Round 4: so is an UNMASKED rectangular, head-strided block whose lengths are aligned (q_len a multiple of 32 and at least
-    // 512, kv_len a multiple of 256) -- the other two block shapes of the zig-zag causal ring.  The workspace layout is the
-    // square problem's for q_hs rows (planes, running sums, control block -- fa2_backward_status finds its word in one place),
-    // so kv_len must not exceed what its control block was sized for.
-    const bool square = q_len == kv_len && q_hs == q_len && k_hs == kv_len && q_row0 == 0 && (!causal || causal_shift == 0) &&
-                        bwd_fused_shape(q_len, head_dim, dtype);
-    const bool rect = !square && !causal && head_dim == 128 && q_len % 32 == 0 && q_len >= 512 && kv_len % 256 == 0 &&
-                      kv_len <= fused_npad(q_hs) && bwd_fused_shape(q_hs, head_dim, dtype);
-    if (allow_single && (phases & 6) == 6 && (square || rect) && bwd_fused_allowed() &&
-        workspace_bytes >= fa2_backward_workspace_bytes(B, H, q_hs, head_dim, dtype) && fa2::bwd_fused_device_ok(nullptr)) {
-        fa2::BwdArgs f{};
-        f.Q = Q; f.K = K; f.V = V; f.O = O; f.dO = dO; f.L = L; f.dQ = dQ; f.dK = dK; f.dV = dV;
-        f.D = (float*)workspace; f.BH = B * H; f.Nq = q_len; f.Nk = kv_len; f.d = head_dim;
-        f.RC = (float*)((char*)workspace + align256((size_t)B * H * q_hs * sizeof(float)));
-        f.q_hs = q_hs; f.k_hs = k_hs; f.q_row0 = q_row0; f.scale = softmax_scale; f.causal = causal ? 1 : 0; f.causal_shift = 0;
-        f.phases = 8 | (phases & 1);
-        // bits 8..15: how many CUs to leave (FA2_PHASE_LEAVE_CUS(n)); 0 there = the default of 16
-        f.reserve_cus = (phases & FA2_PHASE_LEAVE_ROOM) ? (((phases >> 8) & 0xff) ? ((phases >> 8) & 0xff) : 16) : 0;
-        const FusedWs w = fused_ws((char*)workspace + bwd_base_ws(B, H, q_hs), B, H, q_hs, head_dim);
-        return hip_status(fa2::launch_bwd_fused_bf16(f, w.acc, w.ctl, 1, (hipStream_t)stream, w.rcpad));
-    }
-    if (allow_single && bwd_fused_shape(q_hs, head_dim, dtype) &&
-        workspace_bytes >= fa2_backward_workspace_bytes(B, H, q_hs, head_dim, dtype)) {
-        // the two kernels on a workspace that carries a control block: its error word must describe this call (fa2_backward_status)
-        const FusedWs w = fused_ws((char*)workspace + bwd_base_ws(B, H, q_hs), B, H, q_hs, head_dim);
-        const hipError_t e = fa2::bwd_fused_clear_error(w.ctl, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_status(e);
-    }
-    fa2::BwdArgs a{};
-    a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.L = L; a.dQ = dQ; a.dK = dK; a.dV = dV;
-    a.D = (float*)workspace; a.BH = B * H; a.Nq = q_len; a.Nk = kv_len; a.d = head_dim;
-    a.RC = (float*)((char*)workspace + align256((size_t)B * H * q_hs * sizeof(float)));
-    a.q_hs = q_hs; a.k_hs = k_hs; a.q_row0 = q_row0;
-    a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.causal_shift = causal ? causal_shift : 0; a.phases = phases & 7;
-    return hip_status(fa2::launch_bwd_bf16(a, (hipStream_t)stream));
+    return bwd_launch(bwd_route(Entry::phases, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, seq_len, seq_len, 0, 0, 0, head_dim, dtype,
+                                causal, 0, softmax_scale, phases, workspace, workspace_bytes), stream);
 }
 
 int fa2_backward_block(const void* Q, const void* K, const void* V, const void* O, const float* L,
@@ -399,14 +377,8 @@ int fa2_backward_block(const void* Q, const void* K, const void* V, const void* 
                        int q_head_stride, int kv_head_stride, int q_row0, int causal, int causal_shift,
                        void* workspace, size_t workspace_bytes, void* stream, int phases)
 {
-    return backward_block_impl(Q, K, V, O, L, dO, dQ, dK, dV, B, H, q_len, kv_len, head_dim, softmax_scale, dtype, q_head_stride,
-                               kv_head_stride, q_row0, causal, causal_shift, workspace, workspace_bytes, stream, phases, true);
-}
-
-size_t fa2_backward_fused_workspace_bytes(int B, int H, int seq_len, int head_dim)
-{
-    if (B <= 0 || H <= 0 || seq_len <= 0 || !bwd_fused_shape(seq_len, head_dim, FA2_DTYPE_BF16)) return 0;
-    return fa2_backward_workspace_bytes(B, H, seq_len, head_dim, FA2_DTYPE_BF16);
+    return bwd_launch(bwd_route(Entry::block, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, q_len, kv_len, q_head_stride, kv_head_stride,
+                                q_row0, head_dim, dtype, causal, causal_shift, softmax_scale, phases, workspace, workspace_bytes), stream);
 }
 
 int fa2_backward_fused(const void* Q, const void* K, const void* V, const void* O, const float* L,
@@ -414,22 +386,28 @@ int fa2_backward_fused(const void* Q, const void* K, const void* V, const void* 
                        int B, int H, int seq_len, int head_dim, float softmax_scale, int mode,
                        void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!Q || !K || !V || !O || !L || !dO || !dQ || !dK || !dV) return FA2_ERR_NULL_POINTER;
-    int st = check_common(B, H, seq_len, head_dim, softmax_scale);
-    if (st) return st;
-    if (!st) st = check_bwd_planes(B, H, seq_len);
-    if (st) return st;
-    if (!bwd_fused_shape(seq_len, head_dim, FA2_DTYPE_BF16) || (mode != 0 && mode != 1)) return FA2_ERR_UNSUPPORTED;
-    if (mode == 0 && (seq_len % 256 != 0 || head_dim != 128)) return FA2_ERR_UNSUPPORTED;      // the atomics form: head_dim 128, aligned
-    if (mode == 1 && !fa2::bwd_fused_device_ok(nullptr)) return FA2_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < fa2_backward_fused_workspace_bytes(B, H, seq_len, head_dim)) return FA2_ERR_WORKSPACE;
-    fa2::BwdArgs a{};
-    a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.L = L; a.dQ = dQ; a.dK = dK; a.dV = dV;
-    a.D = (float*)workspace; a.BH = B * H; a.Nq = seq_len; a.Nk = seq_len; a.d = head_dim;
-    a.RC = (float*)((char*)workspace + align256((size_t)B * H * seq_len * sizeof(float)));
-    a.q_hs = seq_len; a.k_hs = seq_len; a.q_row0 = 0; a.scale = softmax_scale; a.causal = 0; a.causal_shift = 0; a.phases = 9;
-    const FusedWs w = fused_ws((char*)workspace + bwd_base_ws(B, H, seq_len), B, H, seq_len, head_dim);
-    return hip_status(fa2::launch_bwd_fused_bf16(a, w.acc, w.ctl, mode, (hipStream_t)stream, w.rcpad));
+    return bwd_launch(bwd_route(Entry::fused, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, seq_len, seq_len, 0, 0, 0, head_dim,
+                                FA2_DTYPE_BF16, 0, 0, softmax_scale, mode, workspace, workspace_bytes), stream);
+}
+
+int fa2_backward_plan(int B, int H, int seq_len, int head_dim, int dtype, int causal, const char** reason)
+{
+    const Route r = bwd_route(Entry::plan, {}, B, H, seq_len, seq_len, 0, 0, 0, head_dim, dtype, causal, 0, 1.0f, 0, nullptr, 0);
+    if (reason) *reason = r.status ? "" : r.why;
+    return r.status ? r.status : r.path == Path::single ? 1 : 2;
+}
+
+int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,
+                        void* stream)
+{
+    const Route r = bwd_route(Entry::status, {}, B, H, seq_len, seq_len, 0, 0, 0, head_dim, dtype, 0, 0, 1.0f, 0, workspace,
+                              workspace_bytes);
+    if (r.status) return r.status;
+    if (r.path != Path::single) return hip_status(hipStreamSynchronize((hipStream_t)stream));
+    int err = 0;
+    const hipError_t e = fa2::bwd_fused_read_error(r.ws.ctl, &err, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_status(e);
+    return err ? FA2_ERR_HANDOFF_TIMEOUT : FA2_OK;
 }
 
 int fa2_forward_step(const void* Q, const void* K, const void* V,

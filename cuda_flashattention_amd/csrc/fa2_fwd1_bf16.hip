@@ -594,19 +594,10 @@ static hipError_t launch_one1(const FwdArgs& a, hipStream_t stream)
     constexpr int lds = 2 * kF1Bufs * 16384 + 16;          // the two rings + the workgroup's restart flag
     const int nrb1 = (a.Nq + kF1Rows - 1) / kF1Rows;
     const int nrb = (CAUSAL && !STATE) ? (nrb1 + 1) / 2 : nrb1;      // plain causal launches: two row blocks per workgroup (fa2_fwd1_impl)
-    static bool attr_set[64] = {};
-    if constexpr (D == 64 && FA2_FWD64_QBS == 1) {
-        auto kern = fa2_fwd1x2_bf16_kernel<D, CAUSAL, STATE>;
-        hipError_t e = ensure_dynamic_lds(kern, lds, attr_set);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(nrb * a.BH)), dim3(512), lds, stream, a);
-    } else {
-        auto kern = fa2_fwd1_bf16_kernel<D, CAUSAL, STATE>;
-        hipError_t e = ensure_dynamic_lds(kern, lds, attr_set);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(nrb * a.BH)), dim3(256), lds, stream, a);
-    }
-    return hipGetLastError();
+    if constexpr (D == 64 && FA2_FWD64_QBS == 1)
+        return launch_lds<fa2_fwd1x2_bf16_kernel<D, CAUSAL, STATE>>(dim3((unsigned)(nrb * a.BH)), dim3(512), lds, stream, a);
+    else
+        return launch_lds<fa2_fwd1_bf16_kernel<D, CAUSAL, STATE>>(dim3((unsigned)(nrb * a.BH)), dim3(256), lds, stream, a);
 }
 hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream)
 {

@@ -495,17 +495,8 @@ hipError_t launch_fwd_fp8(const FwdFp8Args& a, hipStream_t stream)
     if (e != hipSuccess) return e;
     const int nrb = (a.N + kF8Rows - 1) / kF8Rows;
     const dim3 grid((unsigned)(nrb * a.BH));
-    static bool set_c[64] = {}, set_n[64] = {};
-    if (a.causal) {
-        e = ensure_dynamic_lds(fa2_fwd_fp8_kernel<true>, lds, set_c);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(fa2_fwd_fp8_kernel<true>, grid, dim3(64 * kF8Waves), lds, stream, a);
-    } else {
-        e = ensure_dynamic_lds(fa2_fwd_fp8_kernel<false>, lds, set_n);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(fa2_fwd_fp8_kernel<false>, grid, dim3(64 * kF8Waves), lds, stream, a);
-    }
-    return hipGetLastError();
+    if (a.causal) return launch_lds<fa2_fwd_fp8_kernel<true>>(grid, dim3(64 * kF8Waves), lds, stream, a);
+    return launch_lds<fa2_fwd_fp8_kernel<false>>(grid, dim3(64 * kF8Waves), lds, stream, a);
 }
 
 }  // namespace fa2

@@ -67,7 +67,9 @@ struct BwdArgs {
 };
 
 hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream);
-// Single-kernel five-product backward (fa2_bwd_fused.hip): d = 128, dense, square; causal with mode 1 only.
+// Single-kernel five-product backward (fa2_bwd_fused.hip): d = 128 or 64, a dense square problem or (d = 128, mode 1) an unmasked
+// rectangular block; causal with mode 1 only.  Which problems come here: the routing rule at fa2_backward (include/fa2_mi355x.h),
+// applied by fa2_capi.cpp alone (device check included).
 // dQacc: [BH][NP][128] fp32 scratch (NP = N rounded up to 256); ctl: bwd_fused_ctl_bytes of scratch; mode 0 = dQ by fp32
 // atomics (N % 256 == 0 only), 1 = dQ handed from key block to key block in a fixed order (deterministic; any N: a ragged
 // launch also needs rcpad, 2 BH NP floats, for the padded row-constant planes).  hipErrorInvalidValue for shapes it does not take.
@@ -98,22 +100,23 @@ struct F32Args {
 hipError_t launch_fwd_f32(const F32Args& a, hipStream_t stream);
 hipError_t launch_bwd_f32(const F32Args& a, hipStream_t stream);
 
-// Raises the dynamic-LDS limit of `kern` on the current device once (per template instance:
-// pass a function-local static flag array).  Benign race: the attribute is idempotent.
-template <typename Kern>
-inline hipError_t ensure_dynamic_lds(Kern kern, int bytes, bool (&done)[64])
+// Enqueues kernel K (one struct argument) with `lds` bytes of dynamic LDS, raising K's dynamic-LDS limit on the current device
+// the first time (one flag per kernel instance and device; a benign race: the attribute is idempotent).
+template <auto K, typename A>
+inline hipError_t launch_lds(dim3 grid, dim3 block, int lds, hipStream_t stream, const A& arg)
 {
+    static bool done[64] = {};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     if (!done[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
         done[dev] = true;
     }
-    return hipSuccess;
+    hipLaunchKernelGGL(K, grid, block, lds, stream, arg);
+    return hipGetLastError();
 }
 
 // FlashAttention-1 restatement (fa1_f32.hip): one head, fp32, didactic baseline row.

@@ -118,28 +118,37 @@ int fa2_forward_fp8_scaled(const void* Q, const void* K, const void* V, void* O,
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* Bytes of scratch fa2_backward needs for this problem: D and the row-constant planes, plus -- for the shapes the
- * single-kernel backward takes (bf16; head_dim 128, or head_dim 64 at aligned lengths: see fa2_backward) -- the fp32 running sums
- * of dQ (B H NP 128 x 4 bytes at either head_dim, NP = seq_len rounded up to a multiple of 256), a small control block and, when
- * NP != seq_len, padded row-constant planes. */
+ * single-kernel backward takes (rule (a) of fa2_backward) -- the fp32 running sums of dQ (B H NP 128 x 4 bytes at either
+ * head_dim, NP = seq_len rounded up to a multiple of 256), a small control block and, when NP != seq_len, padded
+ * row-constant planes. */
 size_t fa2_backward_workspace_bytes(int B, int H, int seq_len, int head_dim, int dtype);
 
 /* dQ, dK, dV from Q, K, V, O, L (forward outputs) and dO.  Deterministic: no floating-point atomics, every
  * gradient element is summed in a fixed order (the reference's smem + global atomicAdd scheme,
- * flash_attention_backward_kernel.cu:208-231, is not reproduced).  Two implementations behind this call:
- *   - bf16, head_dim 128 (causal or not): ONE kernel that forms the five block products once (csrc/fa2_bwd_fused.hip); a
+ * flash_attention_backward_kernel.cu:208-231, is not reproduced).  Two implementations for bf16 (fp32 has kernels of its own):
+ *   - the SINGLE KERNEL (csrc/fa2_bwd_fused.hip, head_dim 128 or 64, causal or not) forms the five block products once; a
  *     workgroup owns 256 keys (dK, dV in registers) and the dQ tiles are summed key block after key block in a fixed order
  *     through the L2 of the XCD the head is pinned to.  Its loops run on seq_len rounded up to a multiple of 256 (keys past
- *     the end masked, rows past the end given row constants that make P vanish, nothing past the end stored); it is taken
- *     whenever that padding costs less than the two extra products of the other form: 5 roundup(N, 256) <= 7 roundup(N, 64),
- *     i.e. every multiple of 256, every N >= 897 and the lengths just below a multiple of 256 under that;
- *   - bf16, head_dim 64 (causal or not; round 4): the same kernel built for head_dim 64 (a sub-tile's dQ tile is summed in two
- *     key halves, i.e. two running sums per column block), taken when 13 roundup(N, 256) <= 14 roundup(N, 64) -- it is ~10 %
- *     ahead of the other form there, so the padding may cost 7 %: every multiple of 256, the lengths just below, every N >= 3329;
- *   - everything else: a dQ kernel and a dK/dV kernel (seven products, csrc/fa2_bwd_bf16.hip).
- * The environment variable FA2_BACKWARD_PATH=two_kernel keeps every shape on the second form.
- * PLACEMENT ASSUMPTION of the first form: its workgroups read HW_REG_XCC_ID and hand running sums to each other through the
+ *     the end masked, rows past the end given row constants that make P vanish, nothing past the end stored);
+ *   - the TWO KERNELS: a dQ kernel and a dK/dV kernel (seven products, csrc/fa2_bwd_bf16.hip).
+ * THE ROUTING RULE, which every backward entry point follows (fa2_backward_plan reports it for a problem): bf16 runs the single
+ * kernel iff
+ *   (a) its padding costs less than what the two kernels cost more:
+ *       head_dim 128 -- 5 roundup(N, 256) <= 7 roundup(N, 64) (the other form's two extra block products on 64-key tiles):
+ *         129 <= N <= 256 and every N >= 321;
+ *       head_dim 64 -- 13 roundup(N, 256) <= 14 roundup(N, 64) (the single kernel is ~10 % ahead there, so the padding may cost
+ *         7 %): every N >= 2369 and every multiple of 256; below 2369 the lengths 193-256, 449-512, 705-768, 897-1024,
+ *         1153-1280, 1409-1536, 1601-1792, 1857-2048, 2113-2304;
+ *   (b) the environment variable FA2_BACKWARD_PATH is not "two_kernel" (read once per process), and
+ *   (c) the device is the layout the hand-off was validated on (PLACEMENT ASSUMPTION below);
+ * every other problem runs the two kernels.  fa2_backward_block applies the rule to two block shapes, given phase bits 1 and 2
+ * and the full workspace of fa2_backward_workspace_bytes(B, H, q_head_stride, ...): a DENSE SQUARE block (q_len = kv_len, dense
+ * strides, q_row0 = 0, causal only with shift 0) with (a) on its length, and an UNMASKED (non-causal) rectangular, head-strided
+ * block of head_dim 128 with q_len a multiple of 32 and >= 512 and kv_len a multiple of 256 and <= roundup(q_head_stride, 256),
+ * with (a) on q_head_stride (the zig-zag causal ring's half blocks).
+ * PLACEMENT ASSUMPTION of the single kernel: its workgroups read HW_REG_XCC_ID and hand running sums to each other through the
  * L2 of that XCC (plain stores, sc1 loads); validated on gfx950 in SPX mode (one device = 8 XCCs x 32 CUs).  On any other
- * device layout (a partitioned GPU, another architecture) this call runs the second form instead: fa2_backward_plan.
+ * device layout (a partitioned GPU, another architecture) this call runs the two kernels instead: fa2_backward_plan.
  * A hand-off that times out (every wait is bounded) leaves dQ all NaN and dK / dV complete: fa2_backward_status. */
 int fa2_backward(const void* Q, const void* K, const void* V, const void* O, const float* L,
                  const void* dO, void* dQ, void* dK, void* dV,
@@ -185,14 +194,9 @@ int fa2_backward_phases(const void* Q, const void* K, const void* V, const void*
  * pointers address row q_row0 of head 0), so phase bit 0 (D = rowsum(dO o O)) may be run once over the
  * dense local tensors (q_row0 = 0, q_len = q_head_stride) and reused by every block of them.  bf16 only.
  * fa2_backward is the block q_len = kv_len = seq_len, strides 0, q_row0 0, shift 0.
- * phases as fa2_backward_phases bits 0..2.  With bits 1 and 2 both set (6 or 7) the library picks the implementation as
- * fa2_backward does: a DENSE SQUARE block (q_len = kv_len, dense strides, q_row0 = 0, no shift) of head_dim 128 and a
- * length that is a multiple of 256 runs the single five-product kernel -- provided the workspace is
- * fa2_backward_workspace_bytes(B, H, q_len, ...) (room for its running sums) and the device is the validated layout
- * (fa2_backward_plan) -- and so does an UNMASKED rectangular, head-strided block of head_dim 128 with q_len a multiple of 32
- * (at least 512) and kv_len a multiple of 256 (at most q_head_stride rounded up to 256), given the workspace of
- * fa2_backward_workspace_bytes(B, H, q_head_stride, ...): the zig-zag causal ring's half blocks.  Every other block runs the dQ
- * and dK/dV kernels.  A single bit (2 or 4) always runs that kernel.
+ * phases as fa2_backward_phases bits 0..2.  With bits 1 and 2 both set (6 or 7) the block runs the single five-product kernel
+ * where the routing rule of fa2_backward (its block shapes included) takes it, the dQ and dK/dV kernels otherwise.  A single
+ * bit (2 or 4) always runs that kernel.
  * FA2_PHASE_LEAVE_ROOM (bit 4) asks the single kernel to leave some of the device's CUs free: its persistent workgroups fill a
  * CU's register file for the whole launch, so a kernel on another stream that must run CONCURRENTLY (the ring backward's RCCL
  * exchange of the previous step's dK / dV pieces) would otherwise wait for the launch to end.  How many: bits 8..15 of
@@ -209,8 +213,9 @@ int fa2_backward_block(const void* Q, const void* K, const void* V, const void* 
 /* The single-kernel five-product backward (csrc/fa2_bwd_fused.hip) with the way dQ is summed over the key-block
  * workgroups of a head chosen by the caller -- mode 1: handed from key block to key block in a fixed order by a
  * persistent grid (deterministic; what fa2_backward uses), mode 0: fp32 atomics (NOT bit-reproducible; kept as the
- * measured alternative; seq_len a multiple of 256 and d = 128 only).  bf16, d = 128 or (mode 1, aligned lengths) 64, non-causal (fa2_backward also takes the causal case), the seq_len rule of fa2_backward;
- * FA2_ERR_UNSUPPORTED otherwise.  Workspace: fa2_backward_fused_workspace_bytes (= fa2_backward_workspace_bytes). */
+ * measured alternative; seq_len a multiple of 256 and d = 128 only).  bf16, non-causal (fa2_backward
+ * also takes the causal case), a head_dim and seq_len that rule (a) of fa2_backward admits, mode 1 only on the device of rule
+ * (c); FA2_ERR_UNSUPPORTED otherwise.  FA2_BACKWARD_PATH does not apply.  Workspace: fa2_backward_fused_workspace_bytes (= fa2_backward_workspace_bytes). */
 size_t fa2_backward_fused_workspace_bytes(int B, int H, int seq_len, int head_dim);
 int fa2_backward_fused(const void* Q, const void* K, const void* V, const void* O, const float* L,
                        const void* dO, void* dQ, void* dK, void* dV,

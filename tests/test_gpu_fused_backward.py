@@ -120,7 +120,7 @@ def test_fused_backward_vs_oracle(B, H, N, mode):
 @pytest.mark.parametrize("B,H,N,causal", [
     (1, 2, 1000, False),     # padded to 1024: the last key block holds 24 keys that do not exist, the last sub-tile 24 such rows
     (1, 3, 2049, False),     # one key and one row past a multiple of 256
-    (2, 2, 897, False),      # the smallest N above 640 the rule admits (5 x 1024 <= 7 x 960 = 6720)
+    (2, 2, 897, False),      # ragged, padded to 1024 (5 x 1024 <= 7 x 960 = 6720: the rule admits it)
     (1, 2, 1000, True),
     (1, 2, 1279, True),
 ])
@@ -576,8 +576,8 @@ def test_status_codes():
     assert lib.fa2_backward_fused_workspace_bytes(1, 1, 300, 128) == 0
     assert lib.fa2_backward_fused_workspace_bytes(1, 1, 300, 64) == 0          # 512 against 320: two kernels
     assert lib.fa2_backward_fused_workspace_bytes(1, 1, 256, 64) == lib.fa2_backward_fused_workspace_bytes(1, 1, 256, 128)
-    assert call(300, 128, 1, ws.numel()) != 0          # not a multiple of 256
-    assert call(300, 64, 1, ws.numel()) != 0           # head_dim 64: aligned lengths only
+    assert call(300, 128, 1, ws.numel()) != 0          # 5 x 512 > 7 x 320: the rule rejects 257 .. 320
+    assert call(300, 64, 1, ws.numel()) != 0           # head_dim 64: 13 x 512 > 14 x 320
     assert call(256, 64, 0, ws.numel()) != 0           # head_dim 64 has no atomics form
     assert call(256, 128, 2, ws.numel()) != 0          # no such mode
     assert call(256, 128, 1, 1024) != 0                # workspace too small
