@@ -315,6 +315,28 @@ def test_generated_bodies_are_up_to_date(tmp_path):
         assert out.read_text() == open(os.path.join(CSRC, inc)).read(), inc
 
 
+def test_generators_share_one_interpreter(monkeypatch):
+    """All five generators imported into ONE process (not in alphabetical order) still produce the committed files: they
+    share tools/bodygen.py, and none of them configures it for the others."""
+    import importlib
+    import sys
+    monkeypatch.syspath_prepend(os.path.join(ROOT, "tools"))
+    for k in [k for k in os.environ if k.startswith("FA2_GEN_")]:
+        monkeypatch.delenv(k)
+    names = ("gen_fused_body", "gen_fwd_fp8_body", "gen_dq_body", "gen_fwd_body", "gen_dkdv_body")
+    incs = ("fa2_bwd_fused_body.inc", "fa2_fwd_fp8_body.inc", "fa2_bwd_dq_body.inc", "fa2_fwd_body.inc", "fa2_bwd_dkdv_body.inc")
+    assert not any(n in sys.modules for n in names)
+    try:
+        gens = [importlib.import_module(n) for n in names]
+        bodygen = sys.modules["bodygen"]
+        for rounds in (0, 1):                      # the second round: after every other generator has run
+            for g, inc in zip(gens, incs):
+                assert bodygen.file_text(g.file_chunks) == open(os.path.join(CSRC, inc)).read(), (inc, rounds)
+    finally:
+        for n in names + ("bodygen",):
+            sys.modules.pop(n, None)
+
+
 def test_version_names_the_compiler():
     import ctypes
     lib = ctypes.CDLL(os.path.join(ROOT, "cuda_flashattention_amd", "lib", "libfa2_mi355x.so"))

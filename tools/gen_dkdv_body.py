@@ -34,17 +34,15 @@ into immediates.
 
 `python tools/gen_dkdv_body.py --check` prints the per-gap issue load of the schedule.
 """
-import argparse
 import os
-import re
 
-GAP_BUDGET = 20          # clocks of other issue hidden per MFMA (one wave per SIMD)
-COST = {"lds": 4, "valu": 4, "exp": 8, "cvt": 4, "mask": 16}
-READ_AHEAD = 7           # issue a fragment read this many MFMAs before its consumer ...
-READ_LATEST = 4          # ... and not later than this many
+import bodygen
+from bodygen import Task, COST, GAP_BUDGET, READ_AHEAD, READ_LATEST
+
 NSLOT = 7
-WAIT_AGE = int(os.environ.get("FA2_GEN_WAIT_AGE", "3"))
-WAIT_LOOK = int(os.environ.get("FA2_GEN_WAIT_LOOK", "0"))       # see render_lines; 2 was MEASURED 2-3 % slower (fused backward)
+# tuning switches (tools/README.md): merged waits, see bodygen.render_lines -- off here
+WAITS = dict(wait_look=int(os.environ.get("FA2_GEN_WAIT_LOOK", str(bodygen.WAIT_LOOK))),
+             wait_age=int(os.environ.get("FA2_GEN_WAIT_AGE", str(bodygen.WAIT_AGE))))
 
 
 class Regs:
@@ -80,15 +78,6 @@ class Regs:
     def dk(self, kb, dt): b = self.A_DK + 16 * (kb * self.DT + dt); return f"a[{b}:{b + 15}]"
     def dv(self, kb, dt): b = self.A_DV + 16 * (kb * self.DT + dt); return f"a[{b}:{b + 15}]"
     def roffv(self, s): return f"v{self.ROFFV + s}"
-
-
-class Task:
-    __slots__ = ("text", "cost", "release", "deadline", "kind", "key", "gap", "seq", "after")
-
-    def __init__(self, text, cost, release, deadline, kind, key=None, after=None):
-        self.text, self.cost, self.release, self.deadline, self.kind, self.key = text, cost, release, deadline, kind, key
-        self.after = after or []       # tasks that must be placed (strictly earlier in issue order) before this one
-        self.gap = None
 
 
 def build(D, masked):
@@ -249,137 +238,12 @@ def build(D, masked):
     return R, mfma, tasks, NS, guard_after
 
 
-def place(tasks, NS, budget=None):
-    """Places every task into a gap (possibly negative = previous body), earliest deadline first, respecting the
-    dependencies in `after`.  Returns (per-gap lists in issue order, per-gap load)."""
-    budget = GAP_BUDGET if budget is None else budget
-    load = {}
-    for i, t in enumerate(tasks):
-        t.seq = i
-    # LDS reads are placed FIRST, on their own: which of them a body leaves in flight for the next one (the tasks with
-    # negative gaps) must not depend on the VALU load, because plain and masked bodies follow each other in any order.
-    for phase in (0, 1):
-        pending = sorted((t for t in tasks if (t.kind == "lds") == (phase == 0)), key=lambda t: (t.deadline, t.seq))
-        guard = 0
-        while pending:
-            guard += 1
-            assert guard < 100000
-            progressed = False
-            for t in list(pending):
-                lo = t.release
-                ok = True
-                for dep in t.after:
-                    if isinstance(dep, tuple):           # ("prev", task): the dependency sits in the PREVIOUS body
-                        d = dep[1]
-                        if d.gap is None:
-                            ok = False
-                            break
-                        lo = max(lo, d.gap - NS + 1)
-                    else:
-                        if dep.gap is None:
-                            ok = False
-                            break
-                        lo = max(lo, dep.gap + (1 if dep.kind == "exp" else 0))    # a trans result is not read in the same gap
-                if not ok:
-                    continue
-                g = lo
-                while load.get(g % NS, 0) + t.cost > budget and g < t.deadline:
-                    g += 1
-                assert g <= t.deadline, (t.text, g, t.deadline)
-                t.gap = g
-                load[g % NS] = load.get(g % NS, 0) + t.cost
-                pending.remove(t)
-                progressed = True
-            assert progressed, "dependency cycle (an LDS task may not depend on a VALU task)"
-    per_gap = {}
-    for t in tasks:
-        per_gap.setdefault(t.gap, []).append(t)
-    for g in per_gap:
-        per_gap[g].sort(key=lambda t: (0 if t.kind == "lds" else 1, t.seq))
-    return per_gap, [load.get(g, 0) for g in range(NS)]
-
-
-def schedule(D, masked):
+def render(D, masked):
     R, mfma, tasks, NS, guard_after = build(D, masked)
-    per_gap, load = place(tasks, NS)
+    lines, pro, load = bodygen.schedule(mfma, tasks, NS, **WAITS)
     for g_first, t in guard_after:
         assert t.gap - NS < g_first - 2, (t.text, t.gap)
     assert all(t.kind == "lds" for t in tasks if t.gap < 0)
-    return R, mfma, tasks, per_gap, load, NS
-
-
-def render_lines(mfma, per_gap, NS):
-    """(body lines with @placeholders, prologue lines) of a cyclic schedule.  Lines tagged '@N ' belong to the NEXT
-    body's early work (they use the next unit's bases); the counted lgkmcnt in front of each MFMA is derived from the
-    steady-state issue order of the LDS operations (two periods are simulated, the second one is emitted)."""
-    gmin = min(per_gap)
-    assert gmin >= -NS, gmin
-
-    def gap_items(g):
-        own = per_gap.get(g, []) if g >= 0 else []
-        nxt = per_gap.get(g - NS, []) if g - NS < 0 else []
-        return own, nxt
-
-    issued = []         # keys in issue order; entries are (period, key)
-    issue_gap = []      # absolute gap (period * NS + g) at which each was issued
-    waited_upto = [-1]  # index into `issued` up to which completion is known
-    lines = []
-    for period in (0, 1):
-        for g in range(NS):
-            text, needs = mfma[g]
-            pos = -1
-            for k in needs:
-                idx = max(i for i, (p, kk) in enumerate(issued) if kk == k and p == period) if any(kk == k and p == period for p, kk in issued) else None
-                assert idx is not None or period == 0, (k, g)
-                if idx is not None:
-                    pos = max(pos, idx)
-            cnt = min(len(issued) - 1 - pos, 15) if pos >= 0 else None
-            # a wait is needed only if it asks for something an earlier wait has not already covered (LDS returns in order)
-            if cnt is not None and len(issued) - 1 - cnt <= waited_upto[0]:
-                cnt = None
-            if cnt is not None and WAIT_LOOK:
-                # fewer s_waitcnt: one wait may also cover what the next WAIT_LOOK MFMAs need, as far as those reads have been
-                # in flight for WAIT_AGE MFMAs.  Without the age limit it halves the waits and is 2-3 % SLOWER (the merged
-                # wait stalls on reads issued a moment ago); with it, about 1 % faster in the fused backward, which sets
-                # its own values.  Off (0) for the dQ and dK/dV bodies.
-                for g2 in range(g + 1, g + 1 + WAIT_LOOK):
-                    p2 = period + g2 // NS
-                    for k in mfma[g2 % NS][1]:
-                        hits = [i for i, (p, kk) in enumerate(issued) if kk == k and p == p2]
-                        # only reads that have been in flight for WAIT_AGE MFMAs or more: younger ones may not have landed
-                        if hits and issue_gap[hits[-1]] <= period * NS + g - WAIT_AGE:
-                            pos = max(pos, hits[-1])
-                cnt = min(len(issued) - 1 - pos, 15)
-            if cnt is not None:
-                waited_upto[0] = len(issued) - 1 - cnt
-            if period == 1:
-                if cnt is not None:
-                    lines.append(f"s_waitcnt lgkmcnt({cnt})")
-                lines.append(text)
-            own, nxt = gap_items(g)
-            for t in own:
-                if t.kind == "lds":
-                    issued.append((period, t.key))
-                    issue_gap.append(period * NS + g)
-                if period == 1:
-                    lines.append(t.text)
-            for t in nxt:
-                if t.kind == "lds":
-                    issued.append((period + 1, t.key))
-                    issue_gap.append(period * NS + g)
-                if period == 1:
-                    lines.append("@N " + t.text)
-    # prologue = the wrapped tasks alone, in the same order
-    pro = []
-    for g in range(NS):
-        for t in per_gap.get(g - NS, []):
-            pro.append("@N " + t.text)
-    return lines, pro
-
-
-def render(D, masked):
-    R, mfma, tasks, per_gap, load, NS = schedule(D, masked)
-    lines, pro = render_lines(mfma, per_gap, NS)
     return R, lines, pro, load, NS
 
 
@@ -389,37 +253,15 @@ def resolve(lines, D, buf, sh, first_next_barrier):
     ROWB = 2 * D
     TILEB, HALFB = 64 * ROWB, 32 * ROWB
     BUFB = 2 * TILEB + 512
-    out = []
-    barrier_done = not first_next_barrier
 
     def bases(b, s):
         return {"Q": b * BUFB + s * HALFB, "G": b * BUFB + TILEB + s * HALFB, "RC": b * BUFB + 128 * s, "RR": 32 * s}
-    cur = bases(buf, sh)
     nxt = bases(buf, 1) if sh == 0 else bases(buf ^ 1, 0)
-    for l in lines:
-        b = cur
-        if l.startswith("@N "):
-            l = l[3:]
-            b = nxt
-            if not barrier_done:
-                out.append("s_waitcnt vmcnt(0)")
-                out.append("s_barrier")
-                barrier_done = True
-        l = re.sub(r"@(Q|G|RC|RR)\+(\d+)", lambda m: str(b[m.group(1)] + int(m.group(2))), l)
-        out.append(l)
-    return out
+    barrier = bodygen.Once(lambda i, l, is_next: is_next) if first_next_barrier else None
+    return bodygen.resolve(lines, bases(buf, sh), nxt, split=False, before=barrier)
 
 
-def c_string(lines):
-    return " \\\n".join('    "' + l.replace("\n\t", "\\n\\t") + '\\n\\t"' for l in lines)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--check", action="store_true")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cuda_flashattention_amd", "csrc",
-                                                  "fa2_bwd_dkdv_body.inc"))
-    args = ap.parse_args()
+def file_chunks(check=False):
     chunks = ["// GENERATED by tools/gen_dkdv_body.py -- do not edit.  Hand-placed main-loop bodies of fa2_bwd_dkdv_kernel:\n"
               "// FA2_DKDV_BODY_D<d>_B<buffer>_S<sub-tile>_M<masked> and the prologues FA2_DKDV_PRO_D<d>_M<masked> (the early\n"
               "// reads of the very first sub-tile).  Register map and schedule: tools/gen_dkdv_body.py.\n"]
@@ -430,18 +272,16 @@ def main():
                       f"#define FA2_DKDV_D{D}_A_DK {R0.A_DK}\n#define FA2_DKDV_D{D}_A_DV {R0.A_DV}\n")
         for masked in (0, 1):
             R, lines, pro, load, NS = render(D, bool(masked))
-            if args.check:
+            if check:
                 nm = sum("v_mfma" in l for l in lines)
                 print(f"D={D} masked={masked}: {len(lines)} lines, {nm} MFMAs, {len(pro)} early reads, max gap load {max(load)}, "
                       f"{sum(l > GAP_BUDGET for l in load)} of {NS} gaps over {GAP_BUDGET}")
                 print("   load:", " ".join(f"{l}" for l in load))
-            p = resolve(pro, D, 1, 1, False)          # 'next' of (buffer 1, sub-tile 1) is (buffer 0, sub-tile 0): the first one
-            p.append("s_waitcnt lgkmcnt(0)")          # in steady state the previous body's last waits cover these reads
-            chunks.append(f"#define FA2_DKDV_PRO_D{D}_M{masked} \\\n" + c_string(p) + "\n")
+            # 'next' of (buffer 1, sub-tile 1) is (buffer 0, sub-tile 0): the first one
+            chunks.append(bodygen.define_prologue(f"FA2_DKDV_PRO_D{D}_M{masked}", resolve(pro, D, 1, 1, False)))
             for buf in (0, 1):
                 for sh in (0, 1):
-                    body = resolve(lines, D, buf, sh, sh == 1)
-                    chunks.append(f"#define FA2_DKDV_BODY_D{D}_B{buf}_S{sh}_M{masked} \\\n" + c_string(body) + "\n")
+                    chunks.append(bodygen.define(f"FA2_DKDV_BODY_D{D}_B{buf}_S{sh}_M{masked}", resolve(lines, D, buf, sh, sh == 1)))
     disp = ["// dispatch: the body of sub-tile (B, S) of a tile, plain or masked\n"
             "#define FA2_DKDV_OPS_128 [r0] \"v\"(roff[0]), [r1] \"v\"(roff[1]), [r2] \"v\"(roff[2]), [r3] \"v\"(roff[3]), [r4] \"v\"(roff[4]), "
             "[r5] \"v\"(roff[5]), [r6] \"v\"(roff[6]), [r7] \"v\"(roff[7]), [t0] \"v\"(toff[0]), [t1] \"v\"(toff[1]), [t2] \"v\"(toff[2]), "
@@ -449,11 +289,8 @@ def main():
             "#define FA2_DKDV_OPS_64 [r0] \"v\"(roff[0]), [r1] \"v\"(roff[1]), [r2] \"v\"(roff[2]), [r3] \"v\"(roff[3]), [t0] \"v\"(toff[0]), "
             "[t1] \"v\"(toff[1]), [t2] \"v\"(toff[2]), [t3] \"v\"(toff[3])\n"]
     chunks.append("".join(disp))
-    if not args.check:
-        with open(args.out, "w") as f:
-            f.write("\n".join(chunks))
-        print("wrote", args.out)
+    return chunks
 
 
 if __name__ == "__main__":
-    main()
+    bodygen.main("fa2_bwd_dkdv_body.inc", file_chunks)

@@ -11,7 +11,7 @@ One body = one 64-key K/V tile for one wave that owns 64 query rows (two 32-row 
 
 so the 3 + 1 VALU instructions per element (fma, exp, mul, half a pack) always run beside MFMAs that do not depend on
 them, and every LDS fragment read is issued several MFMAs ahead of its use behind a counted lgkmcnt -- the same
-generator as the dK/dV kernel's (tools/gen_dkdv_body.py: task placement, cyclic bodies, wait derivation).
+generator core as the dK/dV kernel's (tools/bodygen.py: task placement, cyclic bodies, wait derivation).
 
 Registers (kernel compiled with amdgpu_num_vgpr(64): hipcc owns v0..v63):
     a[0:128)   dQ^T tiles (qb, dt);  a[128:192) Q fragments (qb, s);  a[192:256) dO fragments -- as before
@@ -23,14 +23,19 @@ Operands: %[r*] row-read, %[t*] transposed-read LDS addresses, %[c2], %[lq0/1] =
 %[hp0/1] (of the previous one).  LDS: a ring of three K tiles, then a ring of three V tiles (tile t in slot t mod 3);
 every offset from its address register fits the 16-bit immediate.
 """
-import argparse
 import os
 import re
 
-import gen_dkdv_body as base
-from gen_dkdv_body import Task, COST, READ_AHEAD, READ_LATEST
+import bodygen
+from bodygen import Task, COST, READ_AHEAD, READ_LATEST
 
 NSLOT = 6
+# tuning switches (tools/README.md): the per-gap issue budget, VALU work released later behind its chain, merged waits
+# (bodygen.render_lines -- off here)
+BUDGET = int(os.environ.get("FA2_GEN_BUDGET", str(bodygen.GAP_BUDGET)))
+REL_EXTRA = int(os.environ.get("FA2_GEN_REL_EXTRA", "0"))
+WAITS = dict(wait_look=int(os.environ.get("FA2_GEN_WAIT_LOOK", str(bodygen.WAIT_LOOK))),
+             wait_age=int(os.environ.get("FA2_GEN_WAIT_AGE", str(bodygen.WAIT_AGE))))
 A_DQ, A_QF, A_GF = 0, 128, 192
 V0 = 64
 
@@ -141,7 +146,7 @@ def build(D, masked):
             ends = gA[1] + 4 * KS - 1 - NS     # last MFMA of the previous body's A1
             use0 = gQ1p
             hi = "@HP"                         # the previous tile's bounds in-body, this tile's when emitted in its own body's tail
-        rel = ends + 3 + int(os.environ.get('FA2_GEN_REL_EXTRA', '0'))
+        rel = ends + 3 + REL_EXTRA
         for qb in (0, 1):
             for sp in (0, 1):
                 use = use0 + 2 * sp * DT + qb
@@ -171,7 +176,7 @@ def build(D, masked):
 
 def render(D, masked):
     R, mfma, tasks, NS = build(D, masked)
-    per_gap, load = base.place(tasks, NS, int(os.environ.get('FA2_GEN_BUDGET', str(base.GAP_BUDGET))))
+    lines, pro, load = bodygen.schedule(mfma, tasks, NS, BUDGET, **WAITS)
     # the tiles a stage overwrites must have been consumed: A1 writes SET1 at gA1, A0 of the next body SET0 at NS
     gA1 = 4 * R.KS + 4 * R.DT
     for t in tasks:
@@ -181,42 +186,25 @@ def render(D, masked):
                 assert t.gap < gA1 - 1, (t.text, t.gap)
             if R.SET[0] <= reg < R.SET[0] + 64:
                 assert t.gap < NS - 1, (t.text, t.gap)
-    lines, pro = base.render_lines(mfma, per_gap, NS)
     return R, lines, pro, load, NS
 
 
-def resolve(lines, D, buf):
+def resolve(lines, D, buf, barrier=True):
     """Substitutes placeholders for the body of the tile in ring buffer `buf`; '@N ' lines belong to the next tile."""
     ROWB = 2 * D
     TILEB = 64 * ROWB
 
     def bases(b):
-        return {"K": b * TILEB, "V": b * TILEB}          # V relative to ROFFV (= roff + 3 tiles)
-    cur, nxt, prv = bases(buf), bases((buf + 1) % 3), bases((buf + 2) % 3)
-    out = []
-    barrier_done = False
-    for l in lines:
-        b, is_next = cur, False
-        if l.startswith("@N "):
-            l, b, is_next = l[3:], nxt, True
-            if not barrier_done and l.startswith("ds_read"):
-                out.append("s_waitcnt vmcnt(0)")          # this wave's pieces of the next tile have landed ...
-                out.append("s_barrier")                   # ... and everyone's
-                barrier_done = True
-        l = re.sub(r"@KP\+(\d+)", lambda m: str(prv["K"] + int(m.group(1))), l)
-        l = re.sub(r"@(K|V)\+(\d+)", lambda m: str(b[m.group(1)] + int(m.group(2))), l)
-        l = re.sub(r"@HP(\d)@", lambda m: f"%[hi{m.group(1)}]" if is_next else f"%[hp{m.group(1)}]", l)
-        out.append(l)
-    assert barrier_done
+        return {"K": b * TILEB, "V": b * TILEB, "KP": ((buf + 2) % 3) * TILEB}          # V relative to ROFFV (= roff + 3 tiles)
+    # in front of the first read of the next tile: this wave's pieces of it have landed (vmcnt) and everyone's (barrier)
+    first_read = bodygen.Once(lambda i, l, is_next: is_next and l.startswith("ds_read")) if barrier else None
+    out = bodygen.resolve(lines, bases(buf), bases((buf + 1) % 3), split=False, before=first_read,
+                          rules=[(r"@HP(\d)@", lambda m, is_next: f"%[hi{m.group(1)}]" if is_next else f"%[hp{m.group(1)}]")])
+    assert first_read is None or first_read.done
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--check", action="store_true")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cuda_flashattention_amd", "csrc",
-                                                  "fa2_bwd_dq_body.inc"))
-    args = ap.parse_args()
+def file_chunks(check=False):
     chunks = ["// GENERATED by tools/gen_dq_body.py -- do not edit.  Hand-placed main-loop bodies of fa2_bwd_dq_kernel:\n"
               "// FA2_DQ_BODY_D<d>_B<ring buffer>_M<masked> and the prologues FA2_DQ_PRO_D<d>_M<masked> (the early work of the\n"
               "// very first tile).  Register map and schedule: tools/gen_dq_body.py.\n"]
@@ -227,20 +215,15 @@ def main():
         chunks.append(f"#define FA2_DQ_D{D}_SET1 {R0.SET[1]}\n#define FA2_DQ_D{D}_ROFFV {R0.ROFFV}\n#define FA2_DQ_D{D}_VEND {R0.VEND}\n")
         for masked in (0, 1):
             R, lines, pro, load, NS = render(D, bool(masked))
-            if args.check:
+            if check:
                 print(f"D={D} masked={masked}: {len(lines)} lines, {sum('v_mfma' in l for l in lines)} MFMAs, {len(pro)} early, "
-                      f"max gap load {max(load)}, {sum(l > base.GAP_BUDGET for l in load)} of {NS} gaps over {base.GAP_BUDGET}")
+                      f"max gap load {max(load)}, {sum(l > BUDGET for l in load)} of {NS} gaps over {BUDGET}")
                 print("   load:", " ".join(str(l) for l in load))
-            p = [l for l in resolve(pro, D, 2) if l not in ("s_waitcnt vmcnt(0)", "s_barrier")]      # 'next' of buffer 2 is buffer 0
-            p.append("s_waitcnt lgkmcnt(0)")          # in steady state the previous body's last waits cover these reads
-            chunks.append(f"#define FA2_DQ_PRO_D{D}_M{masked} \\\n" + base.c_string(p) + "\n")
+            chunks.append(bodygen.define_prologue(f"FA2_DQ_PRO_D{D}_M{masked}", resolve(pro, D, 2, barrier=False)))      # 'next' of buffer 2 is buffer 0
             for buf in (0, 1, 2):
-                chunks.append(f"#define FA2_DQ_BODY_D{D}_B{buf}_M{masked} \\\n" + base.c_string(resolve(lines, D, buf)) + "\n")
-    if not args.check:
-        with open(args.out, "w") as f:
-            f.write("\n".join(chunks))
-        print("wrote", args.out)
+                chunks.append(bodygen.define(f"FA2_DQ_BODY_D{D}_B{buf}_M{masked}", resolve(lines, D, buf)))
+    return chunks
 
 
 if __name__ == "__main__":
-    main()
+    bodygen.main("fa2_bwd_dq_body.inc", file_chunks)

@@ -14,7 +14,7 @@ one 32-key block j for one wave, a software pipeline two key blocks deep:
 So each of the 4 VALU instructions per element has a whole body of MFMAs that do not depend on it to hide behind (the
 two-wave kernel's stages put 8 of them beside the 8 S^T products and 56 beside the 8 PV products), every LDS read is issued
 4-7 MFMAs ahead of its use behind a counted lgkmcnt, and nothing is left for hipcc to schedule.  Same generator core as the
-backward kernels' (tools/gen_dkdv_body.py: task placement, cyclic bodies, wait derivation).
+backward kernels' (tools/bodygen.py: task placement, cyclic bodies, wait derivation).
 
 LDS: a ring of FOUR K tiles, then a ring of four V tiles; a tile is KV keys = NH key blocks (KV = 64 at d = 128, 128 at
 d = 64: 16 KiB per tile either way).  Body (tile in buffer b, key block kb) reads K(b, kb) and the V rows of key block
@@ -36,15 +36,18 @@ DMA bodies
 %[mw] (s: LDS byte address of the wave's first piece), %[dvo] (v), %[krs], %[vrs] (s x4), %[kso] (s: byte offset of the
 wave's first piece of tile t + 2).
 """
-import argparse
 import os
-import re
 
-import gen_dkdv_body as base
-from gen_dkdv_body import Task, COST
+import bodygen
+from bodygen import Task, COST
 
-READ_AHEAD = int(os.environ.get("FA2_GEN_READ_AHEAD", str(base.READ_AHEAD)))
-READ_LATEST = int(os.environ.get("FA2_GEN_READ_LATEST", str(base.READ_LATEST)))
+# tuning switches (tools/README.md): how far ahead of its MFMA a fragment read is issued, the per-gap issue budget by
+# head_dim, merged waits (bodygen.render_lines -- off here)
+READ_AHEAD = int(os.environ.get("FA2_GEN_READ_AHEAD", str(bodygen.READ_AHEAD)))
+READ_LATEST = int(os.environ.get("FA2_GEN_READ_LATEST", str(bodygen.READ_LATEST)))
+BUDGET = {128: int(os.environ.get("FA2_GEN_BUDGET_FWD128", "24")), 64: int(os.environ.get("FA2_GEN_BUDGET_FWD64", "44"))}
+WAITS = dict(wait_look=int(os.environ.get("FA2_GEN_WAIT_LOOK", str(bodygen.WAIT_LOOK))),
+             wait_age=int(os.environ.get("FA2_GEN_WAIT_AGE", str(bodygen.WAIT_AGE))))
 NBUF = 4
 # (head_dim, row blocks per wave): what fa2_fwd1_bf16.hip instantiates
 CONFIGS = ((128, 2), (64, 2), (64, 1))
@@ -54,6 +57,8 @@ NEG_INF = "0xff800000"
 #   noFMA / noEXP / noADD / noCVT (that class of the softmax's VALU instructions dropped; expMOV: v_exp_f32 -> v_mov_b32),
 #   noK / noV (the K / V^T fragment reads), noDMA (the next tile's LDS-DMA)
 ABL = set(x for x in os.environ.get("FA2_GEN_FWD_ABL", "").split(",") if x)
+# experiment: every plain body without the lane maxima and the compare, the upper bound of what the X rounds can gain
+NOMAX_ALL = os.environ.get("FA2_GEN_FWD_NOMAX_ALL") == "1"
 
 
 def kv_of(D):
@@ -189,9 +194,8 @@ def build(D, QBS, par, masked, dma, nomax=False):
 
     # ---- lane maxima of block j behind its A chains (masked variant: dead keys to -inf first), then the compare
     last = []
-    # X variant: no lane maxima, no compare -- the kernel runs it where it does not move the reference (fa2_fwd1_bf16.hip);
-    # FA2_GEN_FWD_NOMAX_ALL=1 (experiment): every plain body, the upper bound of what the X rounds can gain
-    nomax = nomax or (os.environ.get("FA2_GEN_FWD_NOMAX_ALL") == "1" and not masked)
+    # X variant: no lane maxima, no compare -- the kernel runs it where it does not move the reference (fa2_fwd1_bf16.hip)
+    nomax = nomax or (NOMAX_ALL and not masked)
     for qb in (() if nomax else QB):
         rel = min(QBS * (KS - 1) + qb + 3, NS - 3)          # the chain's last product has left the matrix pipe
         prev = None
@@ -234,18 +238,13 @@ def build(D, QBS, par, masked, dma, nomax=False):
         def gone(t):
             k0 = t.key[0] if isinstance(t.key, tuple) else None
             return ("noK" in ABL and k0 == "K") or ("noV" in ABL and k0 == "VT") or ("noDMA" in ABL and k0 == "dma")
-        dead = set(id(t) for t in tasks if gone(t))
-        tasks[:] = [t for t in tasks if id(t) not in dead]
-        present = set(t.key for t in tasks)
-        mfma = [(text, [k for k in needs if k in present]) for text, needs in mfma]
+        tasks, mfma = bodygen.prune(tasks, mfma, gone)
     return R, mfma, tasks, NS
 
 
 def render(D, QBS, par, masked, dma, budget, nomax=False):
     R, mfma, tasks, NS = build(D, QBS, par, masked, dma, nomax)
-    per_gap, load = base.place(tasks, NS, budget)
-    lines, pro = base.render_lines(mfma, per_gap, NS)
-    return R, lines, pro, load, NS
+    return (R,) + bodygen.schedule(mfma, tasks, NS, budget, **WAITS) + (NS,)
 
 
 def resolve(lines, D, QBS, buf, kb, barrier):
@@ -254,67 +253,43 @@ def resolve(lines, D, QBS, buf, kb, barrier):
     R = Regs(D, QBS)
     ROWB = 2 * D
     TILEB = R.KV * ROWB
-    lines = [part for l in lines for part in (l.split("\n\t") if not l.startswith("@N ") else [l])]
 
     def bases(b, k):
-        # key block j - 2: two blocks back in the same tile, or in the previous tile's buffer
+        # key block j - 2: two blocks back in the same tile, or in the previous tile's buffer; NB: where tile t + 2 goes
         vb, vk = (b, k - 2) if k >= 2 else ((b + NBUF - 1) % NBUF, k + R.NH - 2)
-        return {"K": b * TILEB + k * 32 * ROWB, "VP": vb * TILEB + vk * 32 * ROWB}
-    cur = bases(buf, kb)
+        return {"K": b * TILEB + k * 32 * ROWB, "VP": vb * TILEB + vk * 32 * ROWB, "NB": ((buf + 2) % NBUF) * TILEB}
     nxt = bases(buf, kb + 1) if kb + 1 < R.NH else bases((buf + 1) % NBUF, 0)
-    out = []
-    if barrier:
-        out += ["s_waitcnt vmcnt(0)", "s_barrier"]
-    for l in lines:
-        b = cur
-        if l.startswith("@N "):
-            l, b = l[3:], nxt
-        l = re.sub(r"@NB\+(\d+)", lambda m: str(((buf + 2) % NBUF) * TILEB + int(m.group(1))), l)
-        l = re.sub(r"@(K|VP)\+(\d+)", lambda m: str(b[m.group(1)] + int(m.group(2))), l)
-        out.append(l)
-    return out
+    return bodygen.resolve(lines, bases(buf, kb), nxt, before=bodygen.Once(lambda i, l, is_next: i == 0) if barrier else None)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--check", action="store_true")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cuda_flashattention_amd", "csrc",
-                                                  "fa2_fwd_body.inc"))
-    args = ap.parse_args()
+def file_chunks(check=False):
     chunks = ["// GENERATED by tools/gen_fwd_body.py -- do not edit.  Main-loop bodies of fa2_fwd1_bf16_kernel (one wave per SIMD):\n"
               "// FA2_FWD_BODY_D<d>Q<row blocks>_B<ring buffer>_K<key block of the tile>_<M0 plain | M1 masked | X no maxima> and the prologue FA2_FWD_PRO_D<d> (the early reads\n"
               "// of the very first body).  Register map, LDS map and schedule: the generator.\n"]
     for D, QBS in CONFIGS:
         R0 = Regs(D, QBS)
         tag = f"D{D}Q{QBS}"
-        budget = int(os.environ.get("FA2_GEN_BUDGET_FWD%d" % D, "24" if D == 128 else "44"))
         chunks.append(f"#define FA2_FWD_{tag}_SET0 {R0.SET[0]}\n#define FA2_FWD_{tag}_SET1 {R0.SET[1]}\n#define FA2_FWD_{tag}_PF0 {R0.PF[0]}\n"
                       f"#define FA2_FWD_{tag}_ROFF {R0.ROFF}\n#define FA2_FWD_{tag}_TOFFV {R0.TOFFV}\n#define FA2_FWD_{tag}_VEND {R0.VEND}\n"
                       f"#define FA2_FWD_{tag}_KV {R0.KV}\n#define FA2_FWD_{tag}_STATE {R0.STATE}\n#define FA2_FWD_{tag}_V0 {R0.V0}\n"
                       f"#define FA2_FWD_{tag}_A_QF {R0.A_QF}\n")
-        pros = set()
+        pros = []
         for vtag, masked, nomax in (("M0", False, False), ("M1", True, False), ("X", False, True)):
             for kb in range(R0.NH):
                 par = kb & 1
                 dma = kb == R0.NH - 1
-                R, lines, pro, load, NS = render(D, QBS, par, masked, dma, budget + (12 if masked else 0) + (4 if dma else 0), nomax)
-                pros.add(tuple(pro))
-                if args.check:
+                R, lines, pro, load, NS = render(D, QBS, par, masked, dma, BUDGET[D] + (12 if masked else 0) + (4 if dma else 0), nomax)
+                pros.append(pro)
+                if check:
                     print(f"{tag} kb={kb} {vtag} dma={int(dma)}: {len(lines)} lines, {sum('v_mfma' in l for l in lines)} MFMAs, "
                           f"{len(pro)} early, max gap load {max(load)}, mean {sum(load) / len(load):.1f}")
                     print("   load:", " ".join(str(l) for l in load))
                 for buf in range(NBUF):
-                    body = resolve(lines, D, QBS, buf, kb, dma)
-                    chunks.append(f"#define FA2_FWD_BODY_{tag}_B{buf}_K{kb}_{vtag} \\\n" + base.c_string(body) + "\n")
-        assert len(pros) == 1, "every body must leave the same reads in flight for the next one"
-        p = resolve(list(pros.pop()), D, QBS, NBUF - 1, R0.NH - 1, False)       # 'next' of the last key block of buffer 3 = (buffer 0, kb 0)
-        p.append("s_waitcnt lgkmcnt(0)")
-        chunks.append(f"#define FA2_FWD_PRO_{tag} \\\n" + base.c_string(p) + "\n")
-    if not args.check:
-        with open(args.out, "w") as f:
-            f.write("\n".join(chunks))
-        print("wrote", args.out)
+                    chunks.append(bodygen.define(f"FA2_FWD_BODY_{tag}_B{buf}_K{kb}_{vtag}", resolve(lines, D, QBS, buf, kb, dma)))
+        # 'next' of the last key block of buffer 3 = (buffer 0, kb 0)
+        chunks.append(bodygen.define_prologue(f"FA2_FWD_PRO_{tag}", resolve(bodygen.one_prologue(pros), D, QBS, NBUF - 1, R0.NH - 1, False)))
+    return chunks
 
 
 if __name__ == "__main__":
-    main()
+    bodygen.main("fa2_fwd_body.inc", file_chunks)

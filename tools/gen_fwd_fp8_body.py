@@ -32,18 +32,25 @@ Operands: %[c2] (s), %[need] (=s), masked variant %[hi] (v: first masked key of 
 the lane's half), %[ninf] (v); DMA bodies %[mw] (s: LDS byte address of the wave's first K piece), %[dvk], %[dvv] (v: per-lane
 source offsets), %[krs], %[vrs] (s x4), %[kso], %[vso] (s: byte offsets of the wave's first pieces of tile t + 2).
 """
-import argparse
 import os
-import re
 
-import gen_dkdv_body as base
-from gen_dkdv_body import Task
+import bodygen
+from bodygen import Task
 
+# tuning switches (tools/README.md)
 READ_AHEAD = int(os.environ.get("FA2_GEN_F8_READ_AHEAD", "4"))
 READ_LATEST = int(os.environ.get("FA2_GEN_F8_READ_LATEST", "2"))
 BUDGET = int(os.environ.get("FA2_GEN_F8_BUDGET", "96"))
 ORDER = int(os.environ.get("FA2_GEN_F8_ORDER", "0"))       # 0: A A A A P P P P; 1: A A P P A A P P
 WIN = int(os.environ.get("FA2_GEN_F8_WIN", "1"))           # half-width (gaps) of a softmax quad's window
+WAITS = dict(wait_look=int(os.environ.get("FA2_GEN_WAIT_LOOK", str(bodygen.WAIT_LOOK))),          # merged waits
+             wait_age=int(os.environ.get("FA2_GEN_WAIT_AGE", str(bodygen.WAIT_AGE))))             # (bodygen.render_lines): off here
+# timing experiments only -- the results are wrong.  NOMAX_ALL: every plain body without the lane maxima (upper bound of the X
+# rounds); NOSYNC: 1 = no tile barrier, 2 = no barrier and no DMA wait; ABL: noFMA / expMOV / noADD -- what a class of the
+# softmax's instructions costs
+NOMAX_ALL = os.environ.get("FA2_GEN_F8_NOMAX_ALL") == "1"
+NOSYNC = int(os.environ.get("FA2_GEN_F8_NOSYNC", "0"))
+ABL = set(x for x in os.environ.get("FA2_GEN_F8_ABL", "").split(",") if x)
 NBUF = 4
 D = 128
 ROWB = 128                    # bytes per K row
@@ -121,25 +128,22 @@ def build(par, masked, dma, nomax=False):
                     alloc_p(rec, dt, g)
 
     def alloc_a(rec, blk, s, g):
-        if True:
-            if True:
-                sk, fk = take(g)
-                if rec:
-                    k0, k1 = ("K", blk, s, 0), ("K", blk, s, 1)
-                    rd(f"ds_read_b128 {slot_lo(sk)}, {ka(s, 0)} offset:@K+{blk * 32 * ROWB}", k0, g, fk)
-                    rd(f"ds_read_b128 {slot_hi(sk)}, {ka(s, 1)} offset:@K+{blk * 32 * ROWB}", k1, g, fk)
-                    c = "0" if s == 0 else sset(par, blk)
-                    mfma[g] = (f"{MFMA} {sset(par, blk)}, {slot(sk)}, {qf(s)}, {c}", [k0, k1])
+        sk, fk = take(g)
+        if rec:
+            k0, k1 = ("K", blk, s, 0), ("K", blk, s, 1)
+            rd(f"ds_read_b128 {slot_lo(sk)}, {ka(s, 0)} offset:@K+{blk * 32 * ROWB}", k0, g, fk)
+            rd(f"ds_read_b128 {slot_hi(sk)}, {ka(s, 1)} offset:@K+{blk * 32 * ROWB}", k1, g, fk)
+            c = "0" if s == 0 else sset(par, blk)
+            mfma[g] = (f"{MFMA} {sset(par, blk)}, {slot(sk)}, {qf(s)}, {c}", [k0, k1])
 
     def alloc_p(rec, dt, g):
-        if True:
-            sv, fv = take(g)
-            if rec:
-                k0, k1 = ("VT", dt, 0), ("VT", dt, 1)
-                rd(f"ds_read_b128 {slot_lo(sv)}, {va(0)} offset:@VP+{dt * 32 * 64}", k0, g, fv)
-                rd(f"ds_read_b128 {slot_hi(sv)}, {va(1)} offset:@VP+{dt * 32 * 64}", k1, g, fv)
-                # P of the keys j - 2: the same parity as this body's
-                mfma[g] = (f"{MFMA} {o(dt)}, {slot(sv)}, {pf(par)}, {o(dt)}", [k0, k1])
+        sv, fv = take(g)
+        if rec:
+            k0, k1 = ("VT", dt, 0), ("VT", dt, 1)
+            rd(f"ds_read_b128 {slot_lo(sv)}, {va(0)} offset:@VP+{dt * 32 * 64}", k0, g, fv)
+            rd(f"ds_read_b128 {slot_hi(sv)}, {va(1)} offset:@VP+{dt * 32 * 64}", k1, g, fv)
+            # P of the keys j - 2: the same parity as this body's
+            mfma[g] = (f"{MFMA} {o(dt)}, {slot(sv)}, {pf(par)}, {o(dt)}", [k0, k1])
 
     # two passes (the schedule is cyclic): the first learns which gap last consumes each slot
     allocate(False)
@@ -163,7 +167,6 @@ def build(par, masked, dma, nomax=False):
             k += 1
             done = []
             for e, r in enumerate((4 * w, 4 * w + 1, 4 * w + 2, 4 * w + 3)):
-                # FA2_GEN_F8_ABL (timing only, wrong results): noFMA / expMOV / noADD -- what a class of the softmax's instructions costs
                 f = None if "noFMA" in ABL else valu(f"v_fma_f32 {sreg(op, blk, r)}, {sreg(op, blk, r)}, %[c2], -{MB}", "valu", rel, dl)
                 x = valu(f"{'v_mov_b32' if 'expMOV' in ABL else 'v_exp_f32'} {sreg(op, blk, r)}, {sreg(op, blk, r)}",
                          "valu" if "expMOV" in ABL else "exp", rel, dl, after=[f] if f else None)
@@ -209,79 +212,50 @@ def build(par, masked, dma, nomax=False):
     return mfma, tasks
 
 
-ABL = set(x for x in os.environ.get("FA2_GEN_F8_ABL", "").split(",") if x)
-
-
 def render(par, masked, dma, budget, nomax=False):
     mfma, tasks = build(par, masked, dma, nomax)
-    per_gap, load = base.place(tasks, NS, budget)
-    lines, pro = base.render_lines(mfma, per_gap, NS)
-    return lines, pro, load
+    return bodygen.schedule(mfma, tasks, NS, budget, **WAITS)
 
 
 def resolve(lines, buf, kb, barrier):
     """Substitutes the placeholders for the body of half kb of the tile in ring buffer buf; '@N ' lines (the next body's early
     reads) get the next body's bases."""
-    lines = [part for l in lines for part in (l.split("\n\t") if not l.startswith("@N ") else [l])]
-
     def bases(b, k):
-        vb = (b + NBUF - 1) % NBUF          # the keys j - 2: the same half of the previous tile
-        return {"K": b * TILEB + k * 64 * ROWB, "VP": vb * TILEB + k * HALFV}      # (VA holds the V^T ring's base: ds offsets are 16 bits)
-    cur = bases(buf, kb)
+        vb = (b + NBUF - 1) % NBUF          # the keys j - 2: the same half of the previous tile; NB: where tile t + 2 goes
+        return {"K": b * TILEB + k * 64 * ROWB, "VP": vb * TILEB + k * HALFV,      # (VA holds the V^T ring's base: ds offsets are 16 bits)
+                "NB": ((buf + 2) % NBUF) * TILEB}
     nxt = bases(buf, kb + 1) if kb + 1 < NH else bases((buf + 1) % NBUF, 0)
-    out = []
-    if barrier:
-        # FA2_GEN_F8_NOSYNC (timing experiments only -- the results are wrong): 1 = no barrier, 2 = no barrier and no DMA wait
-        nosync = int(os.environ.get("FA2_GEN_F8_NOSYNC", "0"))
-        out += (["s_waitcnt vmcnt(0)"] if nosync < 2 else []) + (["s_barrier"] if nosync < 1 else [])
-    for l in lines:
-        b = cur
-        if l.startswith("@N "):
-            l, b = l[3:], nxt
-        l = re.sub(r"@NB\+(\d+)", lambda m: str(((buf + 2) % NBUF) * TILEB + int(m.group(1))), l)
-        l = re.sub(r"@(K|VP)\+(\d+)", lambda m: str(b[m.group(1)] + int(m.group(2))), l)
-        out.append(l)
-    return out
+    sync = bodygen.BARRIER[:max(0, 2 - NOSYNC)]
+    return bodygen.resolve(lines, bases(buf, kb), nxt, before=bodygen.Once(lambda i, l, is_next: i == 0, sync) if barrier else None)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--check", action="store_true")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cuda_flashattention_amd", "csrc",
-                                                  "fa2_fwd_fp8_body.inc"))
-    args = ap.parse_args()
+def file_chunks(check=False):
     chunks = ["// GENERATED by tools/gen_fwd_fp8_body.py -- do not edit.  Main-loop bodies of fa2_fwd_fp8_kernel (two waves per SIMD):\n"
               "// FA2_F8_BODY_B<ring buffer>_K<half of the tile>_<M0 plain | M1 masked | X no maxima> and the prologue FA2_F8_PRO (the early reads of the very\n"
               "// first body).  Register map, LDS map and schedule: the generator.\n",
               f"#define FA2_F8_V0 {V0}\n#define FA2_F8_SET0 {SET[0]}\n#define FA2_F8_SET1 {SET[1]}\n#define FA2_F8_PF0 {PF[0]}\n"
               f"#define FA2_F8_KA {KA}\n#define FA2_F8_VA {VA}\n#define FA2_F8_STATE {STATE}\n#define FA2_F8_VEND {VEND}\n"
               f"#define FA2_F8_A_QF {A_QF}\n#define FA2_F8_KV {KV}\n#define FA2_F8_NBUF {NBUF}\n"]
-    pros = set()
+    pros = []
     # variants: M0 plain, M1 masked (sequence tail, causal diagonal), X = plain without the lane maxima and the compare (the
     # kernel runs it for keys whose scores it has bounded below every row's threshold: |q| |k| <= m + 6)
     for tag, masked, nomax in (("M0", False, False), ("M1", True, False), ("X", False, True)):
         for kb in range(NH):
             par = kb & 1
             dma = kb == NH - 1
-            nm = nomax or (os.environ.get("FA2_GEN_F8_NOMAX_ALL") == "1" and not masked)
+            nm = nomax or (NOMAX_ALL and not masked)
             lines, pro, load = render(par, masked, dma, BUDGET + ((64 if ORDER == 0 else 160) if masked else 0) + (8 if dma else 0), nomax=nm)
-            pros.add(tuple(pro))
-            if args.check:
+            pros.append(pro)
+            if check:
                 print(f"kb={kb} {tag} dma={int(dma)}: {len(lines)} lines, {sum('v_mfma' in x for x in lines)} MFMAs, {len(pro)} early, "
                       f"max gap load {max(load)}, mean {sum(load) / len(load):.1f}")
                 print("   load:", " ".join(str(x) for x in load))
             for buf in range(NBUF):
-                body = resolve(lines, buf, kb, dma)
-                chunks.append(f"#define FA2_F8_BODY_B{buf}_K{kb}_{tag} \\\n" + base.c_string(body) + "\n")
-    assert len(pros) == 1, "every body must leave the same reads in flight for the next one"
-    p = resolve(list(pros.pop()), NBUF - 1, NH - 1, False)       # 'next' of the last half of buffer 3 = (buffer 0, half 0)
-    p.append("s_waitcnt lgkmcnt(0)")
-    chunks.append("#define FA2_F8_PRO \\\n" + base.c_string(p) + "\n")
-    if not args.check:
-        with open(args.out, "w") as f:
-            f.write("\n".join(chunks))
-        print("wrote", args.out)
+                chunks.append(bodygen.define(f"FA2_F8_BODY_B{buf}_K{kb}_{tag}", resolve(lines, buf, kb, dma)))
+    # 'next' of the last half of buffer 3 = (buffer 0, half 0)
+    chunks.append(bodygen.define_prologue("FA2_F8_PRO", resolve(bodygen.one_prologue(pros), NBUF - 1, NH - 1, False)))
+    return chunks
 
 
 if __name__ == "__main__":
-    main()
+    bodygen.main("fa2_fwd_fp8_body.inc", file_chunks)
