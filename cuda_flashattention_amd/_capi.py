@@ -40,6 +40,10 @@ SIGNATURES = {
     "fa2_backward_plan": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p)]),
     "fa2_backward_status": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "fa2_backward_phases": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp, _i]),
+    "fa2_forward_gqa": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    "fa2_backward_gqa_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "fa2_backward_gqa": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp, _i]),
+    "fa2_backward_gqa_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p)]),
     "fa2_backward_fused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fa2_backward_fused": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "fa2_backward_block": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),

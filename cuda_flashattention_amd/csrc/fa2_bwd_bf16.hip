@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
     if (CAUSAL) rb = nrb - 1 - rb;
 
     const size_t slab = (size_t)head * p.q_hs * ROWB;          // Q, dO, dQ
-    const size_t kslab = (size_t)head * p.k_hs * ROWB;         // K, V
+    const size_t kslab = (size_t)(head / p.kv_group) * p.k_hs * ROWB;      // K, V: kv_group query heads share a K/V head
     const char* Qh = (const char*)p.Q + slab;
     const char* Kh = (const char*)p.K + kslab;
     const char* Vh = (const char*)p.V + kslab;
@@ -322,6 +322,10 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
 // (vmcnt(0) + barrier: the next tile has landed) in front of its first read of the other buffer.
 // Masking (sequence tail, causal diagonal) is a second body variant that zeroes P behind each exp; dS then uses
 // v_mul_legacy (0 x anything = 0), so rows past the end contribute nothing whatever their row constants hold.
+// Grouped-query attention (kv_group = G > 1): the workgroup owns 256 keys of a K/V head and walks the query tiles of ALL G query
+// heads of its group, one head after the other, on top of the same accumulators: K fragments, V image and the zeroing happen once,
+// the Q/dO slab, the row-constant offset, the first staging and the prologue once per query head (the two-tile pipeline drains
+// between heads), the stores once.  The order of the sum over (query head, tile) is fixed: deterministic as before.
 constexpr int kDkWaves = 4;
 constexpr int kDkKeys = 64 * kDkWaves;      // keys per workgroup
 
@@ -386,15 +390,12 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
     const int N = p.Nk, Nq = p.Nq;          // N: keys of the block
 
     const int ncb = (N + kDkKeys - 1) / kDkKeys;
-    int head, cb;
-    map_block(blockIdx.x, p.BH, ncb, head, cb);     // causal: key block 0 is the heaviest, already first
+    int kvhead, cb;
+    map_block(blockIdx.x, p.BH / p.kv_group, ncb, kvhead, cb);     // causal: key block 0 is the heaviest, already first
 
-    const size_t slab = (size_t)head * p.k_hs * ROWB;          // K, V, dK, dV
-    const size_t qslab = (size_t)head * p.q_hs * ROWB;         // Q, dO
-    const char* Qh = (const char*)p.Q + qslab;
+    const size_t slab = (size_t)kvhead * p.k_hs * ROWB;        // K, V, dK, dV
     const char* Kh = (const char*)p.K + slab;
     const char* Vh = (const char*)p.V + slab;
-    const char* Gh = (const char*)p.dO + qslab;
     const size_t rc_plane = (size_t)p.BH * p.q_hs;
 
     const int kw0 = cb * kDkKeys + wave * 64;       // first key of this wave
@@ -448,24 +449,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
     const int dslot = lane % CPR;
     const int prow = wave * RPI + drow;                                   // row inside the tile (first piece)
     const int doff = drow * ROWB + 16 * ((lds_off<D>(prow, dslot) - ROWB * prow) >> 4);
-    const auto q_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Qh, 0, Nq * ROWB, 0x00020000);
-    const auto g_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Gh, 0, Nq * ROWB, 0x00020000);
     const auto rc_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.RC, 0, (int)(2 * rc_plane * 4), 0x00020000);
-    const int rcoff = (int)(((wave == 0 ? 0 : rc_plane) + (size_t)head * p.q_hs + p.q_row0 + lane) * 4);
-    auto stage = [&](int t, int buf) {
-        char* b = bufs + buf * BUFB;
-#pragma unroll
-        for (int j = wave; j < 2 * NINS; j += kDkWaves) {
-            const int which = j / NINS, piece = j % NINS;
-            const int soff = (t * TROWS + piece * RPI) * ROWB;            // wave-uniform
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(which ? g_rsrc : q_rsrc, (lptr_t)(b + which * TILEB + piece * 1024),
-                                                     16, doff, soff, 0, 0);
-        }
-        if (wave < 2)                                // row constants: wave 0 the 64 x -L/scale, wave 1 the 64 x -D
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rc_rsrc, (lptr_t)(b + 2 * TILEB + wave * 256), 4, rcoff, t * TROWS * 4, 0, 0);
-    };
-
-    if (t0 < tend) stage(t0, 0);                     // tile t lives in buffer (t - t0) & 1
 
     // ---- loop-invariant per-lane LDS addresses (byte addresses; buffer / sub-tile parts are immediates in the bodies)
     const uint32_t lbase = (uint32_t)(uintptr_t)smem;
@@ -486,6 +470,35 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
         constexpr int sidx = decltype(S)::value;
         dkdv_vset<ROFFV + sidx>(roff[sidx] + 2 * BUFB + 64 * wave * ROWB);
     });
+
+    // ---- the query heads of the group (one, unless grouped-query attention), one after the other
+#pragma nounroll
+    for (int gq = 0; gq < p.kv_group; ++gq) {
+    const int head = kvhead * p.kv_group + gq;
+    const size_t qslab = (size_t)head * p.q_hs * ROWB;         // Q, dO
+    const char* Qh = (const char*)p.Q + qslab;
+    const char* Gh = (const char*)p.dO + qslab;
+    const auto q_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Qh, 0, Nq * ROWB, 0x00020000);
+    const auto g_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Gh, 0, Nq * ROWB, 0x00020000);
+    const int rcoff = (int)(((wave == 0 ? 0 : rc_plane) + (size_t)head * p.q_hs + p.q_row0 + lane) * 4);
+    auto stage = [&](int t, int buf) {
+        char* b = bufs + buf * BUFB;
+#pragma unroll
+        for (int j = wave; j < 2 * NINS; j += kDkWaves) {
+            const int which = j / NINS, piece = j % NINS;
+            const int soff = (t * TROWS + piece * RPI) * ROWB;            // wave-uniform
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(which ? g_rsrc : q_rsrc, (lptr_t)(b + which * TILEB + piece * 1024),
+                                                     16, doff, soff, 0, 0);
+        }
+        if (wave < 2)                                // row constants: wave 0 the 64 x -L/scale, wave 1 the 64 x -D
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rc_rsrc, (lptr_t)(b + 2 * TILEB + wave * 256), 4, rcoff, t * TROWS * 4, 0, 0);
+    };
+
+    if (gq > 0) {                                    // the previous head's last body has look-ahead reads of buffer 0 in flight:
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // they land, and every wave is past them, before it is restaged
+        __builtin_amdgcn_s_barrier();
+    }
+    if (t0 < tend) stage(t0, 0);                     // tile t lives in buffer (t - t0) & 1
 
     __syncthreads();                                 // V image written, first tile landed (vmcnt(0) inside)
     if (t0 < tend) dkdv_prologue<D>(roff, toff, rcadr);
@@ -513,6 +526,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
         tile(std::integral_constant<int, 0>{}, t);
         tile(std::integral_constant<int, 1>{}, t + 1);
     }
+    }      // the group's next query head
 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the last body's look-ahead reads
     mfma_acc_settle();
@@ -559,13 +573,14 @@ static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream)
     }
     if (a.phases & 4) {
         const int ncb = (a.Nk + kDkKeys - 1) / kDkKeys;
-        e = launch_lds<fa2_bwd_dkdv_kernel<D, CAUSAL>>(dim3((unsigned)(ncb * a.BH)), dim3(256), lds_dk, stream, a);
+        e = launch_lds<fa2_bwd_dkdv_kernel<D, CAUSAL>>(dim3((unsigned)(ncb * (a.BH / a.kv_group))), dim3(256), lds_dk, stream, a);
     }
     return e;
 }
 
 hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream)
 {
+    if (a.kv_group < 1 || a.BH % a.kv_group != 0) return hipErrorInvalidValue;
     if (a.d == 128) return a.causal ? launch_bwd_one<128, true>(a, stream) : launch_bwd_one<128, false>(a, stream);
     if (a.d == 64) return a.causal ? launch_bwd_one<64, true>(a, stream) : launch_bwd_one<64, false>(a, stream);
     return hipErrorInvalidValue;

@@ -275,6 +275,11 @@ __device__ __forceinline__ bool fused_spin_over(int* ctl, int spins)
 // head, heads q_hs rows apart, the first of them row q_row0 of the dense row-constant planes, against Nk keys (a multiple of
 // 256), heads k_hs rows apart: the unmasked half blocks of the zig-zag causal ring's backward.  Its own instantiation too: the
 // square kernels keep one length in one register.
+// Grouped-query attention (b.kv_group = G > 1; chained, square): a unit stays (QUERY head, key block) and the hand-off chain is
+// untouched; the unit reads K / V of head / G, and its dK / dV go, per query head, where b.dK / b.dV point -- the launcher aims
+// them at the partials [BH][N][d] and fa2_bwd_fused_dkdv_out_kernel adds each group's G partials.  (Keeping a group's dK / dV in
+// the accumulators across its query heads would chain G units of different dQ hand-offs into one: the unit order and the
+// deadlock argument above would have to change.)
 // HD = 64 (chained, aligned, square; round 4): the bodies generated for head_dim 64 (40 MFMAs per sub-tile).  The dQ tile of a
 // sub-tile is 32 x 64: wave w forms columns 32 (w & 1) .. + 31 over the 128 keys of half w >> 1 of the workgroup's 256, so a
 // sub-tile has TWO running sums per column block (one per key half), each handed from key block to key block exactly like the one
@@ -420,7 +425,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(39))) f
     // as the unit is known -- for every unit but a workgroup's first that is BEFORE the previous unit's epilogue, whose
     // dK / dV stores then overlap these loads (round 4; the change-over was ticket, loads, stores one after the other).
     auto issue_unit_loads = [&](int head_, int cb_) {
-        const size_t slab_ = (size_t)head_ * KHS * ROWB;
+        const size_t slab_ = (size_t)(head_ / p.kv_group) * KHS * ROWB;      // kv_group query heads share a K/V head
         const char* Kh_ = (const char*)p.K + slab_;
         const char* Vh_ = (const char*)p.V + slab_;
         const int kw0_ = cb_ * 256 + wave * 64;
@@ -749,6 +754,29 @@ __global__ void __launch_bounds__(256) fa2_bwd_fused_dq_out_chain64_kernel(const
     }
 }
 
+// Grouped-query attention: dK, dV (bf16 [BH / G][n8 x 8]) = the sum, in ascending query-head order in fp32, of the G per-query-head
+// partials the single kernel stored (bf16 [BH][n8 x 8] each, dK already scaled); n8 = N d / 8 chunks per head, nkv = BH / G.
+__global__ void __launch_bounds__(256) fa2_bwd_fused_dkdv_out_kernel(const bf16x8* __restrict__ pK, const bf16x8* __restrict__ pV,
+                                                                      bf16x8* __restrict__ dK, bf16x8* __restrict__ dV, size_t n8, size_t nkv, int G)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < 2 * nkv * n8; i += stride) {
+        const bool isv = i >= nkv * n8;
+        const size_t o = isv ? i - nkv * n8 : i, kvh = o / n8, r = o % n8;
+        const bf16x8* src = (isv ? pV : pK) + kvh * (size_t)G * n8 + r;
+        float s[8] = {};
+        for (int g = 0; g < G; ++g) {
+            const bf16x8 x = src[(size_t)g * n8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += (float)x[e];
+        }
+        bf16x8 out;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[e] = (__bf16)s[e];
+        (isv ? dV : dK)[o] = out;
+    }
+}
+
 // ragged launches: the row-constant planes [2][BH][N] copied to [2][BH][NP] with (-1e30, 0) in the rows past the end -- a row
 // that does not exist then has S' = -1e30, P = exp2(-huge) = 0 and dS = 0 whatever the (zero) Q / dO rows give
 __global__ void __launch_bounds__(256) fa2_bwd_fused_rcpad_kernel(const float* __restrict__ rc, float* __restrict__ out, int BH, int N, int NP)
@@ -796,6 +824,7 @@ hipError_t bwd_fused_clear_error(int* ctl, hipStream_t stream)
 }
 
 // (the last 8 ints per unit are only written by -DFA2_FUSED_STATS builds: tools/gpu_stats_fused.py)
+size_t bwd_fused_kvpart_bytes(int BH, int N, int d) { return (size_t)2 * BH * N * d * 2; }
 size_t bwd_fused_ctl_bytes(int BH, int N) { return (size_t)(kCtlHeadmap + 16 * (BH + kHmPad) + 9 * BH * ((N + 255) / 256)) * sizeof(int); }
 
 // the chained instance of a dense square problem at head_dim HD
@@ -809,7 +838,7 @@ static hipError_t launch_chained_square(bool causal, bool ragged, dim3 grid, int
                   : launch_lds<fa2_bwd_fused_kernel<true, false, false, false, HD>>(grid, dim3(256), lds, stream, fa);
 }
 
-hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int mode, hipStream_t stream, float* rcpad)
+hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int mode, hipStream_t stream, float* rcpad, void* kvpart)
 {
     const int npad = (a.Nk + 255) / 256 * 256;
     const bool ragged = npad != a.Nk;            // chained form only: needs `rcpad` (2 BH npad floats)
@@ -821,6 +850,8 @@ hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int m
     if (rect && (mode != 1 || a.causal || ragged || a.Nq % 32 != 0 || a.q_row0 < 0 || a.q_hs < a.q_row0 + a.Nq || a.k_hs < a.Nk))
         return hipErrorInvalidValue;
     if (ragged && (mode != 1 || !rcpad)) return hipErrorInvalidValue;
+    const bool grouped = a.kv_group > 1;         // chained, dense square problems only: needs `kvpart`
+    if (a.kv_group < 1 || a.BH % a.kv_group != 0 || (grouped && (mode != 1 || rect || !kvpart))) return hipErrorInvalidValue;
     if (a.causal && (mode != 1 || a.causal_shift != 0)) return hipErrorInvalidValue;
     hipError_t e = hipSuccess;
     if (a.phases & 1) {
@@ -840,6 +871,11 @@ hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int m
         if (e != hipSuccess) return e;
     }
     FusedArgs fa{a, dQacc, ctl, npad, ragged ? (const float*)rcpad : (const float*)a.RC, g_hook_fault};
+    const size_t part_elems = (size_t)a.BH * a.Nk * a.d;      // one tensor's partials: a [Nk][d] slab per QUERY head
+    if (grouped) {
+        fa.b.dK = kvpart;
+        fa.b.dV = (__bf16*)kvpart + part_elems;
+    }
     const int lds = (a.d == 64 ? FA2_FUSED64_LDS : FA2_FUSED_LDS) + 16;
     if (mode == 0) {
         e = launch_fill_f32(dQacc, elems, 0.0f, stream);
@@ -889,6 +925,10 @@ hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int m
     else
         hipLaunchKernelGGL(fa2_bwd_fused_dq_out_chain_kernel, dim3(4096), dim3(256), 0, stream, dQacc, (__bf16*)a.dQ, elems / 4, a.scale,
                            ctl + kCtlError, rect ? a.Nq : a.Nk, rect ? a.Nq : npad, rect ? a.q_hs : a.Nk);
+    e = hipGetLastError();
+    if (e != hipSuccess || !grouped) return e;
+    hipLaunchKernelGGL(fa2_bwd_fused_dkdv_out_kernel, dim3(4096), dim3(256), 0, stream, (const bf16x8*)fa.b.dK, (const bf16x8*)fa.b.dV,
+                       (bf16x8*)a.dK, (bf16x8*)a.dV, (size_t)a.Nk * a.d / 8, (size_t)(a.BH / a.kv_group), a.kv_group);
     return hipGetLastError();
 }
 

@@ -107,6 +107,17 @@ const char* fa2_status_string(int s)
     return "unknown status";
 }
 
+// the bf16 forward of H query heads against H / kv_group K/V heads (fa2_forward: kv_group = 1)
+static int forward_bf16(const void* Q, const void* K, const void* V, void* O, float* L, int B, int H, int kv_group, int seq_len,
+                        int head_dim, float softmax_scale, int causal, void* stream)
+{
+    fa2::FwdArgs a{};
+    a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L; a.Oacc = nullptr; a.M = nullptr;
+    a.BH = B * H; a.Nq = seq_len; a.Nk = seq_len; a.d = head_dim; a.scale = softmax_scale;
+    a.causal = causal ? 1 : 0; a.causal_shift = 0; a.resume = 0; a.finalize = 1; a.kv_group = kv_group;
+    return hip_status(fa2::launch_fwd1_bf16(a, (hipStream_t)stream));
+}
+
 int fa2_forward(const void* Q, const void* K, const void* V, void* O, float* L,
                 int B, int H, int seq_len, int head_dim, float softmax_scale,
                 int dtype, int causal, void* stream)
@@ -116,13 +127,7 @@ int fa2_forward(const void* Q, const void* K, const void* V, void* O, float* L,
     if (st) return st;
     st = check_dim(head_dim, dtype);
     if (st) return st;
-    if (dtype == FA2_DTYPE_BF16) {
-        fa2::FwdArgs a{};
-        a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L; a.Oacc = nullptr; a.M = nullptr;
-        a.BH = B * H; a.Nq = seq_len; a.Nk = seq_len; a.d = head_dim; a.scale = softmax_scale;
-        a.causal = causal ? 1 : 0; a.causal_shift = 0; a.resume = 0; a.finalize = 1;
-        return hip_status(fa2::launch_fwd1_bf16(a, (hipStream_t)stream));
-    }
+    if (dtype == FA2_DTYPE_BF16) return forward_bf16(Q, K, V, O, L, B, H, 1, seq_len, head_dim, softmax_scale, causal, stream);
     if (dtype == FA2_DTYPE_FP8_E4M3) {      // workspace from the stream-ordered allocator
         const size_t need = fa2_forward_fp8_workspace_bytes(B, H, seq_len, head_dim);
         void* ws = nullptr;
@@ -137,6 +142,20 @@ int fa2_forward(const void* Q, const void* K, const void* V, void* O, float* L,
     a.BH = B * H; a.N = seq_len; a.d = head_dim; a.scale = softmax_scale; a.causal = causal ? 1 : 0;
     a.Nk = seq_len; a.M = nullptr; a.resume = 0; a.finalize = 1;
     return hip_status(fa2::launch_fwd_f32(a, (hipStream_t)stream));
+}
+
+int fa2_forward_gqa(const void* Q, const void* K, const void* V, void* O, float* L,
+                    int B, int H_q, int H_kv, int seq_len, int head_dim, float softmax_scale,
+                    int dtype, int causal, void* stream)
+{
+    if (!Q || !K || !V || !O || !L) return FA2_ERR_NULL_POINTER;
+    int st = check_common(B, H_q, seq_len, head_dim, softmax_scale);
+    if (st) return st;
+    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
+    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;      // grouped-query attention: bf16 in this version
+    st = check_dim(head_dim, dtype);
+    if (st) return st;
+    return forward_bf16(Q, K, V, O, L, B, H_q, H_q / H_kv, seq_len, head_dim, softmax_scale, causal, stream);
 }
 
 size_t fa2_forward_fp8_workspace_bytes(int B, int H, int seq_len, int head_dim)
@@ -195,9 +214,12 @@ static bool bwd_fused_shape(int seq_len, int head_dim, int dtype)
 
 // The backward workspace for `rows` rows per head (a block's q_head_stride), each part 256-byte aligned: D [BH][rows] | RC
 // [2][BH][rows] (-L/scale, -D) | then, where the single kernel takes the shape (`single`), its fp32 dQ sums [BH][NP][128]
-// (128 floats per row at either head_dim) | control block | (ragged rows only) RC padded to NP rows (NP = roundup(rows, 256)).
-struct BwdWs { bool single; float *D, *RC, *acc; int* ctl; float* rcpad; size_t base_bytes, bytes; };
-static BwdWs bwd_ws(const void* base, int B, int H, int rows, int head_dim, int dtype)
+// (128 floats per row at either head_dim) | control block | (ragged rows only) RC padded to NP rows (NP = roundup(rows, 256)) |
+// (grouped-query attention, kv_group > 1, only) the single kernel's per-query-head dK / dV partials, bf16 [2][BH][rows][head_dim].
+// The partials come LAST: everything in front of them lies where it lies for the multi-head problem (B, H, rows, head_dim), so
+// fa2_backward_status finds the control block of a grouped launch with those four numbers.
+struct BwdWs { bool single; float *D, *RC, *acc; int* ctl; float* rcpad; size_t base_bytes, bytes; void* kvpart; };
+static BwdWs bwd_ws(const void* base, int B, int H, int rows, int head_dim, int dtype, int kv_group = 1)
 {
     const int np = fused_npad(rows);
     const bool single = bwd_fused_shape(rows, head_dim, dtype);
@@ -205,8 +227,10 @@ static BwdWs bwd_ws(const void* base, int B, int H, int rows, int head_dim, int 
     const size_t ctl = single ? align256(fa2::bwd_fused_ctl_bytes(B * H, np)) : 0;
     const size_t pad = np != rows ? align256((size_t)2 * B * H * np * 4) : 0;
     char* b = (char*)const_cast<void*>(base);
+    const size_t mha = 3 * plane + (single ? acc + ctl + pad : 0);
+    const size_t part = single && kv_group > 1 ? align256(fa2::bwd_fused_kvpart_bytes(B * H, rows, head_dim)) : 0;
     return BwdWs{single, (float*)b, (float*)(b + plane), (float*)(b + 3 * plane), (int*)(b + 3 * plane + acc),
-                 pad ? (float*)(b + 3 * plane + acc + ctl) : nullptr, 3 * plane, 3 * plane + (single ? acc + ctl + pad : 0)};
+                 pad ? (float*)(b + 3 * plane + acc + ctl) : nullptr, 3 * plane, mha + part, part ? b + mha : nullptr};
 }
 
 // FA2_BACKWARD_PATH=two_kernel keeps fa2_backward on the two deterministic kernels for every shape (A/B runs, triage)
@@ -233,8 +257,10 @@ struct Route {
 
 // The one place the backward is routed (the rule: include/fa2_mi355x.h, fa2_backward): validation in the order of the asking
 // entry point, then what to run, its arguments and its workspace.  `t` holds the nine tensors (none for status and plan);
-// `phases` is fa2_backward_fused's mode.
-static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int q_len, int kv_len, int q_stride, int kv_stride,
+// `phases` is fa2_backward_fused's mode.  `kv_heads`: 0 = as many K/V heads as query heads (every multi-head entry point); anything
+// else comes from the grouped-query entry points (phases and plan only), is validated here and changes nothing about WHICH
+// implementation runs -- rule (a) depends on seq_len and head_dim alone.
+static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int kv_heads, int q_len, int kv_len, int q_stride, int kv_stride,
                        int q_row0, int d, int dtype, int causal, int shift, float scale, int phases, const void* ws, size_t ws_bytes)
 {
     Route r;
@@ -244,12 +270,17 @@ static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int q_l
     if (entry <= Entry::fused && (!t.Q || !t.K || !t.V || !t.O || !t.L || !t.dO || !t.dQ || !t.dK || !t.dV))
         return fail(FA2_ERR_NULL_POINTER);
     const int q_hs = q_stride ? q_stride : q_len, k_hs = kv_stride ? kv_stride : kv_len;
+    const bool gqa = kv_heads != 0;           // asked through a grouped-query entry point (bf16 only, whatever the group size)
+    const auto kv_heads_ok = [&] { return kv_heads > 0 && H % kv_heads == 0; };
+    const int kv_group = gqa && kv_heads > 0 && H > 0 ? H / kv_heads : 1;
     switch (entry) {
     case Entry::phases:      // phases: 1 = D and the row constants, 2 = dQ kernel, 4 = dK/dV kernel, 8 = the single kernel
         if ((r.status = check_common(B, H, q_len, d, scale))) return r;
+        if (gqa && !kv_heads_ok()) return fail(FA2_ERR_INVALID_SHAPE);
         if (dtype == FA2_DTYPE_FP8_E4M3) return fail(FA2_ERR_UNSUPPORTED_DTYPE);      // fp8 is forward only
+        if (gqa && dtype != FA2_DTYPE_BF16) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
         if ((r.status = check_dim(d, dtype))) return r;
-        r.ws = bwd_ws(ws, B, H, q_len, d, dtype);
+        r.ws = bwd_ws(ws, B, H, q_len, d, dtype, kv_group);
         if (!ws || ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
         if (dtype == FA2_DTYPE_F32) { r.path = Path::f32; r.args.phases = phases & 7; break; }
         if ((r.status = check_bwd_planes(B, H, q_len))) return r;
@@ -305,7 +336,8 @@ static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int q_l
         break;
     case Entry::plan:
         if (B <= 0 || H <= 0 || q_len <= 0) return fail(FA2_ERR_INVALID_SHAPE);
-        if (dtype == FA2_DTYPE_FP8_E4M3) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
+        if (gqa && !kv_heads_ok()) return fail(FA2_ERR_INVALID_SHAPE);
+        if (dtype == FA2_DTYPE_FP8_E4M3 || (gqa && dtype != FA2_DTYPE_BF16)) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
         if ((r.status = check_dim(d, dtype))) return r;
         r.path = dtype == FA2_DTYPE_F32 ? Path::f32 : Path::two_kernel;
         if (dtype == FA2_DTYPE_F32) r.why = "fp32 path (exact f32 MFMA kernels)";
@@ -321,6 +353,7 @@ static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int q_l
     a.Q = t.Q; a.K = t.K; a.V = t.V; a.O = t.O; a.dO = t.dO; a.L = t.L; a.dQ = t.dQ; a.dK = t.dK; a.dV = t.dV;
     a.D = r.ws.D; a.RC = r.ws.RC; a.BH = B * H; a.Nq = q_len; a.Nk = kv_len; a.d = d;
     a.q_hs = q_hs; a.k_hs = k_hs; a.q_row0 = q_row0; a.scale = scale; a.causal = causal ? 1 : 0; a.causal_shift = causal ? shift : 0;
+    a.kv_group = kv_group;
     return r;
 }
 
@@ -333,7 +366,7 @@ static int bwd_launch(const Route& r, void* stream)
         const hipError_t e = fa2::bwd_fused_clear_error(r.ws.ctl, s);
         if (e != hipSuccess) return hip_status(e);
     }
-    if (r.path == Path::single) return hip_status(fa2::launch_bwd_fused_bf16(a, r.ws.acc, r.ws.ctl, r.mode, s, r.ws.rcpad));
+    if (r.path == Path::single) return hip_status(fa2::launch_bwd_fused_bf16(a, r.ws.acc, r.ws.ctl, r.mode, s, r.ws.rcpad, r.ws.kvpart));
     if (r.path == Path::two_kernel) return hip_status(fa2::launch_bwd_bf16(a, s));
     const fa2::F32Args f{(const float*)a.Q, (const float*)a.K, (const float*)a.V, (float*)a.O, (float*)a.L, (const float*)a.dO,
                          (float*)a.dQ, (float*)a.dK, (float*)a.dV, a.D, a.BH, a.Nq, a.d, a.scale, a.causal, a.phases};
@@ -367,7 +400,7 @@ int fa2_backward_phases(const void* Q, const void* K, const void* V, const void*
                         int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream,
                         int phases)
 {
-    return bwd_launch(bwd_route(Entry::phases, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, seq_len, seq_len, 0, 0, 0, head_dim, dtype,
+    return bwd_launch(bwd_route(Entry::phases, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, 0, seq_len, seq_len, 0, 0, 0, head_dim, dtype,
                                 causal, 0, softmax_scale, phases, workspace, workspace_bytes), stream);
 }
 
@@ -377,7 +410,7 @@ int fa2_backward_block(const void* Q, const void* K, const void* V, const void* 
                        int q_head_stride, int kv_head_stride, int q_row0, int causal, int causal_shift,
                        void* workspace, size_t workspace_bytes, void* stream, int phases)
 {
-    return bwd_launch(bwd_route(Entry::block, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, q_len, kv_len, q_head_stride, kv_head_stride,
+    return bwd_launch(bwd_route(Entry::block, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, 0, q_len, kv_len, q_head_stride, kv_head_stride,
                                 q_row0, head_dim, dtype, causal, causal_shift, softmax_scale, phases, workspace, workspace_bytes), stream);
 }
 
@@ -386,13 +419,37 @@ int fa2_backward_fused(const void* Q, const void* K, const void* V, const void* 
                        int B, int H, int seq_len, int head_dim, float softmax_scale, int mode,
                        void* workspace, size_t workspace_bytes, void* stream)
 {
-    return bwd_launch(bwd_route(Entry::fused, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, seq_len, seq_len, 0, 0, 0, head_dim,
+    return bwd_launch(bwd_route(Entry::fused, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, 0, seq_len, seq_len, 0, 0, 0, head_dim,
                                 FA2_DTYPE_BF16, 0, 0, softmax_scale, mode, workspace, workspace_bytes), stream);
 }
 
 int fa2_backward_plan(int B, int H, int seq_len, int head_dim, int dtype, int causal, const char** reason)
 {
-    const Route r = bwd_route(Entry::plan, {}, B, H, seq_len, seq_len, 0, 0, 0, head_dim, dtype, causal, 0, 1.0f, 0, nullptr, 0);
+    const Route r = bwd_route(Entry::plan, {}, B, H, 0, seq_len, seq_len, 0, 0, 0, head_dim, dtype, causal, 0, 1.0f, 0, nullptr, 0);
+    if (reason) *reason = r.status ? "" : r.why;
+    return r.status ? r.status : r.path == Path::single ? 1 : 2;
+}
+
+size_t fa2_backward_gqa_workspace_bytes(int B, int H_q, int H_kv, int seq_len, int head_dim, int dtype)
+{
+    if (B <= 0 || H_q <= 0 || H_kv <= 0 || H_q % H_kv != 0 || seq_len <= 0) return 0;
+    return bwd_ws(nullptr, B, H_q, seq_len, head_dim, dtype, H_q / H_kv).bytes;
+}
+
+int fa2_backward_gqa(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                     void* dQ, void* dK, void* dV,
+                     int B, int H_q, int H_kv, int seq_len, int head_dim, float softmax_scale,
+                     int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases)
+{
+    // (H_kv = 0 must not read as "multi-head": -1 is as invalid and stays so through the route)
+    return bwd_launch(bwd_route(Entry::phases, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H_q, H_kv ? H_kv : -1, seq_len, seq_len, 0, 0, 0,
+                                head_dim, dtype, causal, 0, softmax_scale, phases, workspace, workspace_bytes), stream);
+}
+
+int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, int dtype, int causal, const char** reason)
+{
+    const Route r = bwd_route(Entry::plan, {}, B, H_q, H_kv ? H_kv : -1, seq_len, seq_len, 0, 0, 0, head_dim, dtype, causal, 0, 1.0f, 0,
+                              nullptr, 0);
     if (reason) *reason = r.status ? "" : r.why;
     return r.status ? r.status : r.path == Path::single ? 1 : 2;
 }
@@ -400,7 +457,7 @@ int fa2_backward_plan(int B, int H, int seq_len, int head_dim, int dtype, int ca
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,
                         void* stream)
 {
-    const Route r = bwd_route(Entry::status, {}, B, H, seq_len, seq_len, 0, 0, 0, head_dim, dtype, 0, 0, 1.0f, 0, workspace,
+    const Route r = bwd_route(Entry::status, {}, B, H, 0, seq_len, seq_len, 0, 0, 0, head_dim, dtype, 0, 0, 1.0f, 0, workspace,
                               workspace_bytes);
     if (r.status) return r.status;
     if (r.path != Path::single) return hip_status(hipStreamSynchronize((hipStream_t)stream));
@@ -458,7 +515,7 @@ int fa2_forward_step_strided(const void* Q, const void* K, const void* V,
     a.BH = B * H; a.Nq = q_len; a.Nk = kv_len; a.d = head_dim; a.scale = softmax_scale;
     a.causal = causal ? 1 : 0; a.causal_shift = causal ? causal_shift : 0;
     a.resume = first ? 0 : 1; a.finalize = last ? 1 : 0;
-    a.q_hs = q_head_stride; a.k_hs = kv_head_stride;
+    a.q_hs = q_head_stride; a.k_hs = kv_head_stride; a.kv_group = 1;
     return hip_status(fa2::launch_fwd1_bf16(a, (hipStream_t)stream));
 }
 

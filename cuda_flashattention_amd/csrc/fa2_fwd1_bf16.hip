@@ -242,8 +242,9 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
     const int Nq = p.Nq, Nk = p.Nk;
     const size_t qhs = p.q_hs ? p.q_hs : Nq, khs = p.k_hs ? p.k_hs : Nk;
     const char* Qh = (const char*)p.Q + (size_t)head * qhs * ROWB;
-    const char* Kh = (const char*)p.K + (size_t)head * khs * ROWB;
-    const char* Vh = (const char*)p.V + (size_t)head * khs * ROWB;
+    const size_t kvhead = (size_t)(head / p.kv_group);       // grouped-query attention: kv_group query heads share one K/V head
+    const char* Kh = (const char*)p.K + kvhead * khs * ROWB;
+    const char* Vh = (const char*)p.V + kvhead * khs * ROWB;
     const int q0 = rb * kF1Rows + wave * WROWS;           // first query row of this wave
 
     // key blocks that hold a visible key for some row of the WORKGROUP (the tile barriers need every wave in every body);
@@ -602,6 +603,7 @@ static hipError_t launch_one1(const FwdArgs& a, hipStream_t stream)
 hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream)
 {
     const bool state = a.resume || !a.finalize;
+    if (a.kv_group < 1 || a.BH % a.kv_group != 0) return hipErrorInvalidValue;
     if (a.d == 128) {
         if (state) return a.causal ? launch_one1<128, true, true>(a, stream) : launch_one1<128, false, true>(a, stream);
         return a.causal ? launch_one1<128, true, false>(a, stream) : launch_one1<128, false, false>(a, stream);

@@ -7,13 +7,14 @@
 
 namespace fa2 {
 
-// One forward problem: BH independent [Nq, d] query slabs against [Nk, d] key/value slabs.
+// One forward problem: BH independent [Nq, d] query slabs against [Nk, d] key/value slabs
+// (BH / kv_group of them: query head h reads K/V slab h / kv_group).
 // Plain attention has Nq == Nk; a ring step runs Nq local query rows against the Nk rows of
 // the resident K/V shard and carries (Oacc, Lrun, Mrun) between launches.
 struct FwdArgs {
     const void* Q;    // [BH][Nq][d]   bf16
-    const void* K;    // [BH][Nk][d]   bf16
-    const void* V;    // [BH][Nk][d]   bf16
+    const void* K;    // [BH / kv_group][Nk][d]   bf16
+    const void* V;    // [BH / kv_group][Nk][d]   bf16
     void* O;          // [BH][Nq][d]   bf16 (written when finalize != 0)
     float* L;         // [BH][Nq]      natural-log LSE when finalize, running sum l otherwise
     float* Oacc;      // [BH][Nq][d]   fp32 un-normalised accumulator (ring state) or nullptr
@@ -26,6 +27,7 @@ struct FwdArgs {
     int finalize;     // 1: write O = acc / l and L = m + ln l; 0: store state
     int q_hs, k_hs;   // rows between consecutive heads of Q/O/Oacc/L/M and of K/V (0: Nq, Nk -- dense slabs).
                       // Larger strides address a row range of every head (the zig-zag chunks of the causal ring).
+    int kv_group;     // query heads per K/V head (>= 1, divides the head count; 1 = multi-head attention)
 };
 
 hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream);     // generated main loop: one wave per SIMD (d = 128), two (d = 64)
@@ -64,6 +66,8 @@ struct BwdArgs {
     int causal_shift;
     int phases;       // bit 0: D = rowsum(dO o O), bit 1: dQ kernel, bit 2: dK/dV kernel (7 = all)
     int reserve_cus;  // single-kernel form: CUs its persistent grid leaves free (for a communication kernel on another stream)
+    int kv_group;     // grouped-query attention: query heads per K/V head (>= 1, divides BH; 1 = multi-head).  K, V, dK, dV
+                      // then hold BH / kv_group slabs and query head h works against slab h / kv_group; dense square problems only
 };
 
 hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream);
@@ -74,7 +78,12 @@ hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream);
 // atomics (N % 256 == 0 only), 1 = dQ handed from key block to key block in a fixed order (deterministic; any N: a ragged
 // launch also needs rcpad, 2 BH NP floats, for the padded row-constant planes).  hipErrorInvalidValue for shapes it does not take.
 size_t bwd_fused_ctl_bytes(int BH, int N);
-hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int mode, hipStream_t stream, float* rcpad = nullptr);
+// kv_group > 1 (dense square problems, mode 1): the kernel stores every unit's dK / dV per QUERY head into `kvpart`
+// (bwd_fused_kvpart_bytes: bf16 dK [BH][Nk][d] | dV [BH][Nk][d]) and fa2_bwd_fused_dkdv_out_kernel adds the kv_group partials of
+// every K/V head, in ascending query-head order in fp32, into dK / dV.
+size_t bwd_fused_kvpart_bytes(int BH, int N, int d);
+hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int mode, hipStream_t stream, float* rcpad = nullptr,
+                                 void* kvpart = nullptr);
 // Whether the current device has the layout the ordered hand-off (mode 1) was validated on; *why = a static sentence.
 bool bwd_fused_device_ok(const char** why);
 // Synchronises `stream` and reads the error word a chained launch leaves in its control block (non-zero: a bounded wait

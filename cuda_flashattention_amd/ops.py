@@ -55,6 +55,26 @@ def _like(x, name, ref, shape, dtype):
     return x
 
 
+def _kv_shape(Q, K, V, shape):
+    """K's shape for a Q of `shape`: Q's own, or (grouped-query attention, [B, H_kv, N, d] with H_kv dividing H) fewer heads.
+    V must match K; both must have Q's dtype.  Grouped tensors are bf16."""
+    B, H, N, d = shape
+    kshape = _bhnd(K, "K")
+    if Q.dim() != 4 or K.dim() != 4 or kshape == shape:
+        _like(K, "K", Q, shape, Q.dtype)
+        kshape = shape
+    else:
+        Hkv = kshape[1]
+        if (kshape[0], kshape[2], kshape[3]) != (B, N, d) or Hkv < 1 or H % Hkv != 0:
+            raise ValueError(f"K: shape {tuple(K.shape)} does not match {shape} (grouped-query attention: [B, H_kv, N, d] "
+                             f"with H_kv dividing H = {H})")
+        _like(K, "K", Q, kshape, Q.dtype)
+        if Q.dtype != torch.bfloat16:
+            raise ValueError(f"K: {Hkv} key/value heads against {H} query heads needs bf16 tensors, got {Q.dtype}")
+    _like(V, "V", Q, kshape, Q.dtype)
+    return kshape
+
+
 def _rows(x, name, ref, B, H, N):
     if not isinstance(x, torch.Tensor) or not x.is_cuda or not x.is_contiguous():
         raise ValueError(f"{name} must be a contiguous device tensor")
@@ -72,12 +92,12 @@ def flash_attention_2_forward(Q, K, V, softmax_scale=None, causal=False, O=None,
                               descale=None):
     """O, L = FA2 forward.  Mirrors flash_attention_2_forward(Q,K,V,O,L,seq_len,head_dim,scale)
     (reference 02_forward/flash_attention_kernel.cu:300-309) with B,H,dtype,causal,stream added.
-    Tensors [N,d] or [B,H,N,d]; L is fp32 [.., N] natural-log LSE.  fp8 (e4m3) inputs only: workspace= a caller-owned
+    Tensors [N,d] or [B,H,N,d]; L is fp32 [.., N] natural-log LSE.  Grouped-query attention (bf16): K and V may be
+    [B,H_kv,N,d] with H_kv dividing H -- query head h attends K/V head h // (H // H_kv).  fp8 (e4m3) inputs only: workspace= a caller-owned
     scratch tensor (forward_fp8_workspace; without it every call takes one from the stream-ordered allocator), descale=
     (q, k, v) per-tensor descales of tensors stored as x / descale (fa2_forward_fp8_scaled)."""
     B, H, N, d = shape = _bhnd(Q, "Q")
-    for n, t in (("K", K), ("V", V)):
-        _like(t, n, Q, shape, Q.dtype)
+    Hkv = _kv_shape(Q, K, V, shape)[1]
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
     odt = torch.bfloat16 if Q.dtype == torch.float8_e4m3fn else Q.dtype      # fp8 inputs (OCP e4m3, d = 128) produce a bf16 O
     if O is None:
@@ -99,6 +119,11 @@ def flash_attention_2_forward(Q, K, V, softmax_scale=None, causal=False, O=None,
         return O, L
     if workspace is not None or descale is not None:
         raise ValueError("workspace= / descale= belong to the fp8 (float8_e4m3fn) forward")
+    if Hkv != H:
+        st = _capi.lib().fa2_forward_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+                                         B, H, Hkv, N, d, scale, _dtype_code(Q), 1 if causal else 0, _stream_ptr(stream))
+        check(st, "fa2_forward_gqa")
+        return O, L
     st = _capi.lib().fa2_forward(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
                                  B, H, N, d, scale, _dtype_code(Q), 1 if causal else 0, _stream_ptr(stream))
     check(st, "fa2_forward")
@@ -109,22 +134,33 @@ def flash_attention_2_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=Fal
                                dQ=None, dK=None, dV=None, workspace=None, stream=None, phases=7):
     """dQ, dK, dV = FA2 backward.  Mirrors flash_attention_2_backward(Q,K,V,O,L,dO,dQ,dK,dV,...)
     (reference 02_backward/flash_attention_backward_kernel.cu:249-262).  dO must be contiguous (autograd often hands
-    over an expanded or transposed view: call .contiguous() on it first -- the C ABI reads a dense tensor)."""
+    over an expanded or transposed view: call .contiguous() on it first -- the C ABI reads a dense tensor).
+    Grouped-query attention (bf16): K, V and with them dK, dV may be [B,H_kv,N,d] with H_kv dividing H."""
     B, H, N, d = shape = _bhnd(Q, "Q")
     gdt = torch.bfloat16 if Q.dtype == torch.float8_e4m3fn else Q.dtype       # what the forward produced for fp8 inputs
-    for n, t, dt in (("K", K, Q.dtype), ("V", V, Q.dtype), ("O", O, gdt), ("dO", dO, gdt)):
+    kshape = _kv_shape(Q, K, V, shape)
+    Hkv = kshape[1]
+    for n, t, dt in (("O", O, gdt), ("dO", dO, gdt)):
         _like(t, n, Q, shape, dt)
     _rows(L, "L", Q, B, H, N)
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
     dQ = torch.empty_like(Q) if dQ is None else _like(dQ, "dQ", Q, shape, Q.dtype)
-    dK = torch.empty_like(K) if dK is None else _like(dK, "dK", Q, shape, Q.dtype)
-    dV = torch.empty_like(V) if dV is None else _like(dV, "dV", Q, shape, Q.dtype)
+    dK = torch.empty_like(K) if dK is None else _like(dK, "dK", Q, kshape, Q.dtype)
+    dV = torch.empty_like(V) if dV is None else _like(dV, "dV", Q, kshape, Q.dtype)
     lib = _capi.lib()
-    need = lib.fa2_backward_workspace_bytes(B, H, N, d, _dtype_code(Q))
+    need = lib.fa2_backward_gqa_workspace_bytes(B, H, Hkv, N, d, _dtype_code(Q))
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
     if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
         raise ValueError("workspace must be a contiguous device tensor on Q's device")
+    if Hkv != H:
+        st = lib.fa2_backward_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+                                  dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(),
+                                  B, H, Hkv, N, d, scale, _dtype_code(Q), 1 if causal else 0,
+                                  workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                  _stream_ptr(stream), int(phases))
+        check(st, "fa2_backward_gqa")
+        return dQ, dK, dV
     st = lib.fa2_backward_phases(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
                                  dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(),
                                  B, H, N, d, scale, _dtype_code(Q), 1 if causal else 0,
@@ -180,6 +216,7 @@ class _Attention(torch.autograd.Function):
 
 def attention(Q, K, V, softmax_scale=None, causal=False):
     """softmax(scale Q K^T [causal]) V for [B, H, N, d] bf16 (d = 64 | 128) or fp32 (non-causal) device tensors, with gradients.
+    bf16 K and V may have fewer heads ([B, H_kv, N, d], H_kv dividing H: grouped-query attention); their gradients have their shape.
     A convenience for callers that live in torch autograd; tests and bench.py call the two halves directly."""
     return _Attention.apply(Q, K, V, softmax_scale, causal)
 

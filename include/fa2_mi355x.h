@@ -172,7 +172,43 @@ int fa2_backward_plan(int B, int H, int seq_len, int head_dim, int dtype, int ca
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,
                         void* stream);
 
-/* The same, restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
+/* ---- Grouped-query attention (GQA; H_kv = 1: multi-query attention), bf16, head_dim 64 or 128, causal or not, any seq_len.
+ * H_q query heads share H_kv key/value heads, H_q % H_kv == 0 (any group size G = H_q / H_kv, powers of two or not): query head h
+ * attends K/V head h / G.  Layouts stay dense: Q, O, dO, dQ are [B][H_q][N][d], K, V, dK, dV are [B][H_kv][N][d], L is
+ * [B][H_q][N] -- no expanded copy of K / V and no [B][H_q] copy of dK / dV is ever formed by the caller.
+ * fa2_forward_gqa: the forward kernels of fa2_forward with the K/V slab of head h / G; a query head's arithmetic does not depend
+ * on where its K/V live, so O and L are bit-identical to fa2_forward on K, V repeated to H_q heads.
+ * fa2_backward_gqa: `phases` as in fa2_backward_phases (7 = the routing rule picks; 6 = the two kernels whatever the shape, on
+ * what a call with bit 0 left in the workspace; 8 or 8|1 = the single kernel, FA2_ERR_UNSUPPORTED where it does not apply).  THE ROUTING RULE is that of fa2_backward
+ * for the multi-head problem (B, H_q, seq_len, head_dim) -- rule (a) depends on seq_len and head_dim only, (b) and (c) on the
+ * process and the device -- and fa2_backward_gqa_plan reports it (always equal to fa2_backward_plan(B, H_q, ...)).
+ *   - two kernels: the dQ kernel reads K/V of head h / G; a dK/dV workgroup owns 256 keys of a K/V head and walks the query tiles
+ *     of its G query heads one after the other on top of the same accumulators (grid: key blocks x B H_kv), storing once;
+ *   - single kernel: a unit stays (query head, key block) and the dQ hand-off is unchanged; every unit stores its dK / dV per
+ *     query head as bf16 partials into the workspace, and a reduction kernel adds the G partials of every K/V head in ascending
+ *     query-head order in fp32 and writes bf16 dK / dV (G == 1: no partials, no extra launch).
+ * dQ is bit-identical to fa2_backward's on the repeated K, V.  DETERMINISTIC like fa2_backward: every sum has a fixed order, no
+ * floating-point atomics.
+ * WORKSPACE: fa2_backward_gqa_workspace_bytes = fa2_backward_workspace_bytes(B, H_q, ...) plus, where rule (a) admits the single
+ * kernel and G > 1, the partials (2 B H_q seq_len head_dim x 2 bytes), placed BEHIND everything the multi-head layout holds:
+ * fa2_backward_status(workspace, bytes, B, H_q, seq_len, head_dim, dtype, stream) finds the control block where it always was
+ * and works on the workspace of a grouped launch.  With H_kv == H_q the three calls enqueue exactly what fa2_forward /
+ * fa2_backward_phases enqueue, and the workspace is that of fa2_backward_workspace_bytes.
+ * Status codes: H_kv <= 0 or H_q % H_kv != 0 -> FA2_ERR_INVALID_SHAPE; fp32 and fp8 -> FA2_ERR_UNSUPPORTED_DTYPE (GQA is bf16 in
+ * this version); everything else as in the multi-head calls, checked in the same order.  Not covered: the ring, the resumable
+ * forward steps and fa2_backward_block. */
+int fa2_forward_gqa(const void* Q, const void* K, const void* V, void* O, float* L,
+                    int B, int H_q, int H_kv, int seq_len, int head_dim, float softmax_scale,
+                    int dtype, int causal, void* stream);
+size_t fa2_backward_gqa_workspace_bytes(int B, int H_q, int H_kv, int seq_len, int head_dim, int dtype);
+int fa2_backward_gqa(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                     void* dQ, void* dK, void* dV,
+                     int B, int H_q, int H_kv, int seq_len, int head_dim, float softmax_scale,
+                     int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases);
+int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, int dtype, int causal,
+                          const char** reason);
+
+/* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output
  * pass (FA2_ERR_UNSUPPORTED for shapes or devices it does not take, and in combination with bits 1 or 2).  7 = fa2_backward (which picks the implementation);
  * 6 = the two-kernel form whatever the shape.  For profiling and for callers that overlap the two independent
