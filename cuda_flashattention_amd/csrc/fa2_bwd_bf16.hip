@@ -30,7 +30,7 @@
 // per-element subtraction (rows are registers there, not lanes).
 #include <type_traits>
 
-#include "fa2_common.h"
+#include "fa2_regfile.h"
 #include "fa2_launch.h"
 
 namespace fa2 {
@@ -74,9 +74,9 @@ __global__ void __launch_bounds__(256) fa2_bwd_delta_kernel(const __bf16* __rest
 // --------------------------------------------------------------------------- kernel 1: dQ
 // Workgroup = 4 waves = 256 query rows of one head, ONE wave per SIMD; a wave owns 64 rows (two
 // 32-row blocks).  Everything long-lived sits in the accumulator half of the register file as
-// literal AGPR ranges owned by asm (fa2_common.h: acc_*): the dQ^T accumulators
-// (2 x D/32 tiles), and the resident Q and dO fragments, which the S^T and dP^T products take
-// straight from AGPRs as their B operand (mfma_bagpr).  The architectural VGPRs are left to the
+// literal AGPR ranges owned by asm (fa2_regfile.h): the dQ^T accumulators
+// (2 x D/32 tiles), and the resident Q and dO fragments, which the S^T and dP^T products of the
+// generated bodies take straight from AGPRs as their B operand.  The architectural VGPRs are left to the
 // S^T/dP^T tiles of a 64-key tile, the packed dS and the streamed fragments.  K/V tiles (64 keys)
 // arrive by LDS-DMA into a double-buffered swizzled image; every K/V row fragment and every K^T
 // transposed fragment read from LDS feeds both row blocks.
@@ -85,24 +85,21 @@ constexpr int kDqWaves = 4;
 constexpr int kDqKV = 64;       // keys per streamed tile in kernel 1
 constexpr int kDkQ = 32;        // query rows per sub-tile in kernel 2
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
 #include "fa2_bwd_dq_body.inc"
 
-#define FA2_DQ_CLOBBERS "memory", "vcc", "v255", FA2_ACC_CLOBBERS
+#define FA2_DQ_CLOBBERS "memory", "vcc", FA2_RF512
 #define FA2_DQ_OPS_128 [r0] "v"(roff[0]), [r1] "v"(roff[1]), [r2] "v"(roff[2]), [r3] "v"(roff[3]), [r4] "v"(roff[4]), [r5] "v"(roff[5]), \
     [r6] "v"(roff[6]), [r7] "v"(roff[7]), [t0] "v"(toff[0]), [t1] "v"(toff[1]), [t2] "v"(toff[2]), [t3] "v"(toff[3]), [t4] "v"(toff[4]),     \
     [t5] "v"(toff[5]), [t6] "v"(toff[6]), [t7] "v"(toff[7])
 #define FA2_DQ_OPS_64 [r0] "v"(roff[0]), [r1] "v"(roff[1]), [r2] "v"(roff[2]), [r3] "v"(roff[3]), [t0] "v"(toff[0]), [t1] "v"(toff[1]),    \
     [t2] "v"(toff[2]), [t3] "v"(toff[3])
 
-// One literal VGPR move (see dkdv_vset below): seeds registers the generated bodies own.
-template <int R>
-__device__ __forceinline__ void dq_vset(float x)
-{
-    asm volatile("v_mov_b32 v%c1, %0" : : "v"(x), "i"(R) : "v255");
-}
+// Both kernels of this file: one wave per SIMD.  A statement that seeds a body-owned VGPR reserves the top register only
+// (CL_TOP: that is what makes the kernel descriptor cover the registers the bodies name); one that writes an accumulator
+// carries the accumulator list (CL_ACC).
+constexpr int kBwdRegFile = RF512;
 
 template <int D, int BUF, bool MASKED>
 __device__ __forceinline__ void dq_body(const uint32_t (&roff)[D / 16], const uint32_t (&toff)[D / 16], float c2, float lq0, float lq1,
@@ -195,12 +192,12 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
         const int qld = qrow[qb] < Nq ? qrow[qb] : Nq - 1;
         static_for<KS>([&](auto S) {
             constexpr int sidx = decltype(S)::value;
-            acc_write_frag<A_QF + (qb * KS + sidx) * 4>(
+            awrite_frag<kBwdRegFile, CL_ACC, A_QF + (qb * KS + sidx) * 4>(
                 *reinterpret_cast<const bf16x8*>(Qh + (size_t)qld * ROWB + 16 * (2 * sidx + h)));
-            acc_write_frag<A_GF + (qb * KS + sidx) * 4>(
+            awrite_frag<kBwdRegFile, CL_ACC, A_GF + (qb * KS + sidx) * 4>(
                 *reinterpret_cast<const bf16x8*>(Gh + (size_t)qld * ROWB + 16 * (2 * sidx + h)));
         });
-        static_for<16 * DT>([&](auto R) { acc_write<A_DQ + qb * DT * 16 + decltype(R)::value>(0.0f); });
+        static_for<16 * DT>([&](auto R) { awrite<kBwdRegFile, CL_ACC, A_DQ + qb * DT * 16 + decltype(R)::value>(0.0f); });
         Lq[qb] = p.L[(size_t)head * p.q_hs + qld] * kLog2e;
         Dq[qb] = p.D[(size_t)head * p.q_hs + p.q_row0 + qld];
     });
@@ -215,15 +212,12 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
     // SET1 (S^T / dP^T of "key block 1 of the tile before the first"): P = exp2(-huge) = 0 and dP' = 0, so the first body's
     // Q1 stage adds exactly zero
     static_for<32>([&](auto R) {
-        dq_vset<SET1 + decltype(R)::value>(-1.0e30f);
-        dq_vset<SET1 + 32 + decltype(R)::value>(0.0f);
+        vset<kBwdRegFile, CL_TOP, SET1 + decltype(R)::value>(-1.0e30f);
+        vset<kBwdRegFile, CL_TOP, SET1 + 32 + decltype(R)::value>(0.0f);
     });
 
     // ---- LDS-DMA staging (as in fa2_fwd: one per-lane voffset, wave-uniform soffset, range-checked)
-    const int drow = lane / CPR;
-    const int dslot = lane % CPR;
-    const int prow = wave * RPI + drow;
-    const int doff = drow * ROWB + 16 * ((lds_off<D>(prow, dslot) - ROWB * prow) >> 4);
+    const int doff = lds_dma_off<D>(wave * RPI, lane);
     const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kh, 0, N * ROWB, 0x00020000);
     const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Vh, 0, N * ROWB, 0x00020000);
     auto stage = [&](int t, int buf) {
@@ -255,7 +249,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
 
     static_for<KS>([&](auto S) {               // row-read addresses of the V ring
         constexpr int sidx = decltype(S)::value;
-        dq_vset<ROFFV + sidx>(__uint_as_float(roff[sidx] + VRING));
+        vset<kBwdRegFile, CL_TOP, ROFFV + sidx>(roff[sidx] + VRING);
     });
 
     __syncthreads();                         // tile 0 has landed (vmcnt(0) inside)
@@ -295,8 +289,8 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
             constexpr int dt = decltype(G)::value / 4, g = decltype(G)::value % 4;
             constexpr int R = A_DQ + (qb * DT + dt) * 16 + 4 * g;
             bf16x4 o;
-            o[0] = (__bf16)(acc_read<R>() * p.scale); o[1] = (__bf16)(acc_read<R + 1>() * p.scale);
-            o[2] = (__bf16)(acc_read<R + 2>() * p.scale); o[3] = (__bf16)(acc_read<R + 3>() * p.scale);
+            o[0] = (__bf16)(aread<R>() * p.scale); o[1] = (__bf16)(aread<R + 1>() * p.scale);
+            o[2] = (__bf16)(aread<R + 2>() * p.scale); o[3] = (__bf16)(aread<R + 3>() * p.scale);
             if (qrow[qb] < Nq)
                 *reinterpret_cast<bf16x4*>((char*)p.dQ + slab + (size_t)qrow[qb] * ROWB + 2 * (32 * dt + 8 * g + 4 * h)) = o;
         });
@@ -331,15 +325,7 @@ constexpr int kDkKeys = 64 * kDkWaves;      // keys per workgroup
 
 #include "fa2_bwd_dkdv_body.inc"
 
-// One literal VGPR move / accumulator access per call; the clobber of v255 is what makes the kernel descriptor
-// allocate the registers the bodies name (a reserved register to hipcc: it never allocates it).
-template <int R>
-__device__ __forceinline__ void dkdv_vset(uint32_t x)
-{
-    asm volatile("v_mov_b32 v%c1, %0" : : "v"(x), "i"(R) : "v255");
-}
-
-#define FA2_DKDV_CLOBBERS "memory", "vcc", "s10", "s11", "v255", FA2_ACC_CLOBBERS
+#define FA2_DKDV_CLOBBERS "memory", "vcc", "s10", "s11", FA2_RF512
 
 template <int D, int BUF, int SH, bool MASKED>
 __device__ __forceinline__ void dkdv_body(const uint32_t (&roff)[D / 16], const uint32_t (&toff)[D / 16], uint32_t rc, float c2,
@@ -411,10 +397,10 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
         static_for<KS>([&](auto S) {
             constexpr int sidx = decltype(S)::value;
             const u32x4 w = *reinterpret_cast<const u32x4*>(Kh + (size_t)kr * ROWB + 16 * (2 * sidx + h));
-            dkdv_vset<KF + 4 * (kb * KS + sidx) + 0>(w[0]);
-            dkdv_vset<KF + 4 * (kb * KS + sidx) + 1>(w[1]);
-            dkdv_vset<KF + 4 * (kb * KS + sidx) + 2>(w[2]);
-            dkdv_vset<KF + 4 * (kb * KS + sidx) + 3>(w[3]);
+            vset<kBwdRegFile, CL_TOP, KF + 4 * (kb * KS + sidx) + 0>(w[0]);
+            vset<kBwdRegFile, CL_TOP, KF + 4 * (kb * KS + sidx) + 1>(w[1]);
+            vset<kBwdRegFile, CL_TOP, KF + 4 * (kb * KS + sidx) + 2>(w[2]);
+            vset<kBwdRegFile, CL_TOP, KF + 4 * (kb * KS + sidx) + 3>(w[3]);
         });
     });
     // V image: the workgroup's 256 keys, swizzled like every other tile.
@@ -426,8 +412,8 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
             *reinterpret_cast<const u32x4*>(Vh + (size_t)kr * ROWB + 16 * ch);
     }
     static_for<32 * DT>([&](auto R) {
-        acc_write<A_DK + decltype(R)::value>(0.0f);
-        acc_write<A_DV + decltype(R)::value>(0.0f);
+        awrite<kBwdRegFile, CL_ACC, A_DK + decltype(R)::value>(0.0f);
+        awrite<kBwdRegFile, CL_ACC, A_DV + decltype(R)::value>(0.0f);
     });
 
     const int ntiles = (Nq + TROWS - 1) / TROWS;
@@ -440,15 +426,10 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
     const float c2 = p.scale * kLog2e;
 
     // ---- LDS-DMA staging.  Wave w issues pieces w, w+4, ... of the 2*NINS pieces of a tile; a piece is RPI rows =
-    // 1 KiB written linearly, lane l -> row l / CPR, slot l % CPR; the slot must hold chunk (slot ^ f(row)), f being
-    // lds_off's swizzle: so the SOURCE address is permuted, the LDS side stays linear.  The swizzle term depends on the
-    // row modulo 16 only, so ONE per-lane byte offset (voffset) serves every DMA of the wave; the tile/piece part is
-    // wave-uniform (soffset) and the slab is described by a buffer resource whose range check turns rows past the end
-    // of the sequence into zeros.
-    const int drow = lane / CPR;
-    const int dslot = lane % CPR;
-    const int prow = wave * RPI + drow;                                   // row inside the tile (first piece)
-    const int doff = drow * ROWB + 16 * ((lds_off<D>(prow, dslot) - ROWB * prow) >> 4);
+    // 1 KiB written linearly from a pre-swizzled source (lds_dma_off: ONE per-lane voffset serves every DMA of the wave);
+    // the tile/piece part is wave-uniform (soffset) and the slab is described by a buffer resource whose range check
+    // turns rows past the end of the sequence into zeros.
+    const int doff = lds_dma_off<D>(wave * RPI, lane);
     const auto rc_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.RC, 0, (int)(2 * rc_plane * 4), 0x00020000);
 
     // ---- loop-invariant per-lane LDS addresses (byte addresses; buffer / sub-tile parts are immediates in the bodies)
@@ -468,7 +449,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
     // this wave's 64 V rows (same swizzle phase as row ki)
     static_for<KS>([&](auto S) {
         constexpr int sidx = decltype(S)::value;
-        dkdv_vset<ROFFV + sidx>(roff[sidx] + 2 * BUFB + 64 * wave * ROWB);
+        vset<kBwdRegFile, CL_TOP, ROFFV + sidx>(roff[sidx] + 2 * BUFB + 64 * wave * ROWB);
     });
 
     // ---- the query heads of the group (one, unless grouped-query attention), one after the other
@@ -539,10 +520,10 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
             constexpr int dt = decltype(G)::value / 4, g = decltype(G)::value % 4;
             constexpr int RK = A_DK + 16 * (kb * DT + dt) + 4 * g, RV = A_DV + 16 * (kb * DT + dt) + 4 * g;
             bf16x4 a, b;
-            a[0] = (__bf16)(acc_read<RK>() * p.scale); a[1] = (__bf16)(acc_read<RK + 1>() * p.scale);
-            a[2] = (__bf16)(acc_read<RK + 2>() * p.scale); a[3] = (__bf16)(acc_read<RK + 3>() * p.scale);
-            b[0] = (__bf16)acc_read<RV>(); b[1] = (__bf16)acc_read<RV + 1>();
-            b[2] = (__bf16)acc_read<RV + 2>(); b[3] = (__bf16)acc_read<RV + 3>();
+            a[0] = (__bf16)(aread<RK>() * p.scale); a[1] = (__bf16)(aread<RK + 1>() * p.scale);
+            a[2] = (__bf16)(aread<RK + 2>() * p.scale); a[3] = (__bf16)(aread<RK + 3>() * p.scale);
+            b[0] = (__bf16)aread<RV>(); b[1] = (__bf16)aread<RV + 1>();
+            b[2] = (__bf16)aread<RV + 2>(); b[3] = (__bf16)aread<RV + 3>();
             if (key < N) {
                 *reinterpret_cast<bf16x4*>(dKk + 2 * (32 * dt + 8 * g + 4 * h)) = a;
                 *reinterpret_cast<bf16x4*>(dVk + 2 * (32 * dt + 8 * g + 4 * h)) = b;

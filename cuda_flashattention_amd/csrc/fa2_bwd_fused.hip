@@ -20,7 +20,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "fa2_common.h"
+#include "fa2_regfile.h"
 #include "fa2_launch.h"
 
 namespace fa2 {
@@ -44,16 +44,18 @@ typedef __attribute__((address_space(3))) void* fused_lptr_t;
 #define FA2_FUSED_DIAG 0
 #endif
 
-template <int R>
-__device__ __forceinline__ void fused_vset(uint32_t x)
-{
-    asm volatile("v_mov_b32 v%c1, %0" : : "v"(x), "i"(R) : "v255");
-}
+// One wave per SIMD.  As in fa2_bwd_bf16.hip: seeding a body-owned VGPR reserves the top register only (CL_TOP), a statement
+// that writes an accumulator carries the accumulator list (CL_ACC).
+constexpr int kFusedRegFile = RF512;
 
-#define FA2_FUSED_CLOBBERS "memory", "vcc", "v255", FA2_ACC_CLOBBERS
-#define FA2_FUSED_OPS [r0] "v"(roff[0]), [r1] "v"(roff[1]), [r2] "v"(roff[2]), [r3] "v"(roff[3]), [r4] "v"(roff[4]), [r5] "v"(roff[5]),  \
+#define FA2_FUSED_CLOBBERS "memory", "vcc", FA2_RF512
+// the eight (head_dim 64: four) row-read and transposed-read addresses of a body, its row-constant address and the exponent scale
+#define FA2_FUSED_OPS_128 [r0] "v"(roff[0]), [r1] "v"(roff[1]), [r2] "v"(roff[2]), [r3] "v"(roff[3]), [r4] "v"(roff[4]), [r5] "v"(roff[5]),  \
     [r6] "v"(roff[6]), [r7] "v"(roff[7]), [t0] "v"(toff[0]), [t1] "v"(toff[1]), [t2] "v"(toff[2]), [t3] "v"(toff[3]), [t4] "v"(toff[4]),   \
     [t5] "v"(toff[5]), [t6] "v"(toff[6]), [t7] "v"(toff[7]), [rc] "v"(rcv), [c2] "s"(c2)
+// head_dim 64 (round 4): the same bodies generated for KS = 4, DT = 2 (FA2_FUSED64_*)
+#define FA2_FUSED_OPS_64 [r0] "v"(roff[0]), [r1] "v"(roff[1]), [r2] "v"(roff[2]), [r3] "v"(roff[3]), [t0] "v"(toff[0]), [t1] "v"(toff[1]),    \
+    [t2] "v"(toff[2]), [t3] "v"(toff[3]), [rc] "v"(rcv), [c2] "s"(c2)
 
 // chained kernel: everything a step does is inside the body (tools/gen_fused_body.py lists the operands)
 struct FusedStep {
@@ -61,59 +63,28 @@ struct FusedStep {
     uint32_t dso, lso, qso, rcso, pvo, mso;
     int need, pval;
 };
-// head_dim 64 (round 4): the same bodies generated for KS = 4, DT = 2 (FA2_FUSED64_*): four row-read and four transposed-read
-// addresses instead of eight
-#define FA2_FUSED_OPS64 [r0] "v"(roff[0]), [r1] "v"(roff[1]), [r2] "v"(roff[2]), [r3] "v"(roff[3]), [t0] "v"(toff[0]), [t1] "v"(toff[1]),    \
-    [t2] "v"(toff[2]), [t3] "v"(toff[3]), [rc] "v"(rcv), [c2] "s"(c2)
-template <int BUF, int PAR, int VMW, bool MASKED>
-__device__ __forceinline__ void fused_cbody(const uint32_t (&roff)[4], const uint32_t (&toff)[4], uint32_t rcv, float c2, uint32_t dqv,
+// One chained step.  TEXT: the body; DD: head_dim (selects the address operands); the masked bodies take two more operands.
+#define FA2_FUSED_STEP(TEXT, DD, ...)                                                                                                 \
+    asm volatile(TEXT                                                                                                                 \
+                 : [err] "+s"(err)                                                                                                    \
+                 : FA2_FUSED_OPS_##DD, [vm] "i"(VMW), [dqv] "v"(dqv), [drs] "s"(f.drs), [dso] "s"(f.dso), [lrs] "s"(f.lrs), [lso] "s"(f.lso), \
+                   [mw] "s"(mw), [mw2] "s"(mw2), [qrs] "s"(f.qrs), [grs] "s"(f.grs), [rcrs] "s"(f.rcrs), [qso] "s"(f.qso),               \
+                   [rcso] "s"(f.rcso), [dvo] "v"(dvo), [rcvo] "v"(rcvo), [wv] "s"(wv), [ctl] "s"(f.ctl), [pvo] "s"(f.pvo),               \
+                   [mso] "s"(f.mso), [need] "s"(f.need), [pval] "s"(f.pval) __VA_ARGS__                                                \
+                 : FA2_FUSED_CLOBBERS, "s12", "s13", "scc", "exec", "m0", "v39")
+template <int D, int BUF, int PAR, int VMW, bool MASKED>
+__device__ __forceinline__ void fused_cbody(const uint32_t (&roff)[D / 16], const uint32_t (&toff)[D / 16], uint32_t rcv, float c2, uint32_t dqv,
                                             uint32_t dvo, uint32_t rcvo, uint32_t mw, uint32_t mw2, int wv, const FusedStep& f, int& err,
                                             int lo0 = 0, int lo1 = 0)
 {
-#define FA2_FUSED_CASE(B, P)                                                                                                          \
-    if constexpr (BUF == B && PAR == P && MASKED)                                                                                     \
-        asm volatile(FA2_FUSED64_MBODY_B##B##_P##P                                                                                    \
-                     : [err] "+s"(err)                                                                                                \
-                     : FA2_FUSED_OPS64, [vm] "i"(VMW), [dqv] "v"(dqv), [drs] "s"(f.drs), [dso] "s"(f.dso), [lrs] "s"(f.lrs), [lso] "s"(f.lso), \
-                       [mw] "s"(mw), [mw2] "s"(mw2), [qrs] "s"(f.qrs), [grs] "s"(f.grs), [rcrs] "s"(f.rcrs), [qso] "s"(f.qso),           \
-                       [rcso] "s"(f.rcso), [dvo] "v"(dvo), [rcvo] "v"(rcvo), [wv] "s"(wv), [ctl] "s"(f.ctl), [pvo] "s"(f.pvo),           \
-                       [mso] "s"(f.mso), [need] "s"(f.need), [pval] "s"(f.pval), [lo0] "v"(lo0), [lo1] "v"(lo1)                        \
-                     : FA2_FUSED_CLOBBERS, "s12", "s13", "scc", "exec", "m0", "v39");                                                 \
-    if constexpr (BUF == B && PAR == P && !MASKED)                                                                                    \
-        asm volatile(FA2_FUSED64_CBODY_B##B##_P##P                                                                                    \
-                     : [err] "+s"(err)                                                                                                \
-                     : FA2_FUSED_OPS64, [vm] "i"(VMW), [dqv] "v"(dqv), [drs] "s"(f.drs), [dso] "s"(f.dso), [lrs] "s"(f.lrs), [lso] "s"(f.lso), \
-                       [mw] "s"(mw), [mw2] "s"(mw2), [qrs] "s"(f.qrs), [grs] "s"(f.grs), [rcrs] "s"(f.rcrs), [qso] "s"(f.qso),           \
-                       [rcso] "s"(f.rcso), [dvo] "v"(dvo), [rcvo] "v"(rcvo), [wv] "s"(wv), [ctl] "s"(f.ctl), [pvo] "s"(f.pvo),           \
-                       [mso] "s"(f.mso), [need] "s"(f.need), [pval] "s"(f.pval)                                                        \
-                     : FA2_FUSED_CLOBBERS, "s12", "s13", "scc", "exec", "m0", "v39");
-    FA2_FUSED_CASE(0, 0) FA2_FUSED_CASE(0, 1) FA2_FUSED_CASE(1, 0) FA2_FUSED_CASE(1, 1) FA2_FUSED_CASE(2, 0) FA2_FUSED_CASE(2, 1)
-#undef FA2_FUSED_CASE
-}
-
-template <int BUF, int PAR, int VMW, bool MASKED>
-__device__ __forceinline__ void fused_cbody(const uint32_t (&roff)[8], const uint32_t (&toff)[8], uint32_t rcv, float c2, uint32_t dqv,
-                                            uint32_t dvo, uint32_t rcvo, uint32_t mw, uint32_t mw2, int wv, const FusedStep& f, int& err,
-                                            int lo0 = 0, int lo1 = 0)
-{
-#define FA2_FUSED_CASE(B, P)                                                                                                          \
-    if constexpr (BUF == B && PAR == P && MASKED)                                                                                     \
-        asm volatile(FA2_FUSED_MBODY_B##B##_P##P                                                                                      \
-                     : [err] "+s"(err)                                                                                                \
-                     : FA2_FUSED_OPS, [vm] "i"(VMW), [dqv] "v"(dqv), [drs] "s"(f.drs), [dso] "s"(f.dso), [lrs] "s"(f.lrs), [lso] "s"(f.lso), \
-                       [mw] "s"(mw), [mw2] "s"(mw2), [qrs] "s"(f.qrs), [grs] "s"(f.grs), [rcrs] "s"(f.rcrs), [qso] "s"(f.qso),           \
-                       [rcso] "s"(f.rcso), [dvo] "v"(dvo), [rcvo] "v"(rcvo), [wv] "s"(wv), [ctl] "s"(f.ctl), [pvo] "s"(f.pvo),           \
-                       [mso] "s"(f.mso), [need] "s"(f.need), [pval] "s"(f.pval), [lo0] "v"(lo0), [lo1] "v"(lo1)                        \
-                     : FA2_FUSED_CLOBBERS, "s12", "s13", "scc", "exec", "m0", "v39");                                                 \
-    if constexpr (BUF == B && PAR == P && !MASKED)                                                                                    \
-        asm volatile(FA2_FUSED_CBODY_B##B##_P##P                                                                                      \
-                     : [err] "+s"(err)                                                                                                \
-                     : FA2_FUSED_OPS, [vm] "i"(VMW), [dqv] "v"(dqv), [drs] "s"(f.drs), [dso] "s"(f.dso), [lrs] "s"(f.lrs), [lso] "s"(f.lso), \
-                       [mw] "s"(mw), [mw2] "s"(mw2), [qrs] "s"(f.qrs), [grs] "s"(f.grs), [rcrs] "s"(f.rcrs), [qso] "s"(f.qso),           \
-                       [rcso] "s"(f.rcso), [dvo] "v"(dvo), [rcvo] "v"(rcvo), [wv] "s"(wv), [ctl] "s"(f.ctl), [pvo] "s"(f.pvo),           \
-                       [mso] "s"(f.mso), [need] "s"(f.need), [pval] "s"(f.pval)                                                        \
-                     : FA2_FUSED_CLOBBERS, "s12", "s13", "scc", "exec", "m0", "v39");
-    FA2_FUSED_CASE(0, 0) FA2_FUSED_CASE(0, 1) FA2_FUSED_CASE(1, 0) FA2_FUSED_CASE(1, 1) FA2_FUSED_CASE(2, 0) FA2_FUSED_CASE(2, 1)
+    // TAG: the generator's prefix of a head_dim (FA2_FUSED_* / FA2_FUSED64_*)
+#define FA2_FUSED_CASE(TAG, DD, B, P)                                                                                                 \
+    if constexpr (D == DD && BUF == B && PAR == P && MASKED) FA2_FUSED_STEP(FA2_FUSED##TAG##_MBODY_B##B##_P##P, DD, , [lo0] "v"(lo0), [lo1] "v"(lo1)); \
+    if constexpr (D == DD && BUF == B && PAR == P && !MASKED) FA2_FUSED_STEP(FA2_FUSED##TAG##_CBODY_B##B##_P##P, DD);
+#define FA2_FUSED_CASES(TAG, DD) \
+    FA2_FUSED_CASE(TAG, DD, 0, 0) FA2_FUSED_CASE(TAG, DD, 0, 1) FA2_FUSED_CASE(TAG, DD, 1, 0) FA2_FUSED_CASE(TAG, DD, 1, 1) FA2_FUSED_CASE(TAG, DD, 2, 0) FA2_FUSED_CASE(TAG, DD, 2, 1)
+    FA2_FUSED_CASES(, 128) FA2_FUSED_CASES(64, 64)
+#undef FA2_FUSED_CASES
 #undef FA2_FUSED_CASE
 }
 
@@ -121,7 +92,7 @@ template <int BUF, int PAR, int VMW>
 __device__ __forceinline__ void fused_body(const uint32_t (&roff)[8], const uint32_t (&toff)[8], uint32_t rcv, float c2)
 {
 #define FA2_FUSED_CASE(B, P) \
-    if constexpr (BUF == B && PAR == P) asm volatile(FA2_FUSED_BODY_B##B##_P##P : : FA2_FUSED_OPS, [vm] "i"(VMW) : FA2_FUSED_CLOBBERS);
+    if constexpr (BUF == B && PAR == P) asm volatile(FA2_FUSED_BODY_B##B##_P##P : : FA2_FUSED_OPS_128, [vm] "i"(VMW) : FA2_FUSED_CLOBBERS);
     FA2_FUSED_CASE(0, 0) FA2_FUSED_CASE(0, 1) FA2_FUSED_CASE(1, 0) FA2_FUSED_CASE(1, 1) FA2_FUSED_CASE(2, 0) FA2_FUSED_CASE(2, 1)
 #undef FA2_FUSED_CASE
 }
@@ -161,17 +132,10 @@ __device__ __forceinline__ void fused_load_vfrag(const char* v0, const char* v1)
                  : "memory", "v255");
 }
 
-template <int T>
-__device__ __forceinline__ void fused_acc_zero(u32x4 z)
-{
-    // (the compiler does not know this statement is an MFMA: the wait states between its writes of z and the read are ours)
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 a[%c1:%c2], %0, %0, 0" : : "v"(z), "i"(16 * T), "i"(16 * T + 15) : FA2_ACC_CLOBBERS);
-}
-
 template <int DQT>
 __device__ __forceinline__ void fused_dq_zero()
 {
-    static_for<16>([&](auto R) { fused_vset<DQT + decltype(R)::value>(0u); });
+    static_for<16>([&](auto R) { vset<kFusedRegFile, CL_TOP, DQT + decltype(R)::value>(0u); });
 }
 
 // ---- the chained form's control block (ints, zeroed by the launcher before every launch)
@@ -338,24 +302,22 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(39))) f
     const uint32_t rcv = lbase + QRING + 2 * TROWS * ROWB + 16 * h;
     static_for<KS>([&](auto S) {                   // this wave's K rows in the K image
         constexpr int sidx = decltype(S)::value;
-        fused_vset<ROFFK + sidx>(lbase + lds_off<D>(ki + 64 * wave, 2 * sidx + h));
+        vset<kFusedRegFile, CL_TOP, ROFFK + sidx>(lbase + lds_off<D>(ki + 64 * wave, 2 * sidx + h));
     });
     // E: this wave's 32 columns of dQ over "its" keys -- head_dim 128: column block = wave, all 256 keys; head_dim 64: column
     // block wave & 1, the 128 keys of half wave >> 1 (the bodies step 16 keys per immediate from these bases)
     const int ecol = W ? wave : (wave & 1), ekey0 = W ? 0 : 128 * (wave >> 1);
     static_for<2>([&](auto JJ) {                   // K^T for this wave's 32 columns; dS^T of the workgroup's tile
         constexpr int jj = decltype(JJ)::value;
-        fused_vset<KT + jj>(lbase + ekey0 * ROWB + lds_off<D>(8 * jj + 4 * h + trq, 4 * ecol + 2 * trcb + (trp >> 1)) + 8 * (trp & 1));
+        vset<kFusedRegFile, CL_TOP, KT + jj>(lbase + ekey0 * ROWB + lds_off<D>(8 * jj + 4 * h + trq, 4 * ecol + 2 * trcb + (trp >> 1)) + 8 * (trp & 1));
         const int row = 8 * jj + 4 * h + trq;
-        fused_vset<DSRD + jj>(lbase + DSB + (ekey0 + row) * 64 + 8 * ((4 * trcb + trp) ^ FA2_FUSED_DSKEY(row)));
+        vset<kFusedRegFile, CL_TOP, DSRD + jj>(lbase + DSB + (ekey0 + row) * 64 + 8 * ((4 * trcb + trp) ^ FA2_FUSED_DSKEY(row)));
     });
     static_for<4>([&](auto C) {                    // dS write addresses: 8-byte chunk (4 sp + 2 jp + h) of row 64 w + ki
         constexpr int c = decltype(C)::value;
-        fused_vset<DSWR + c>(lbase + DSB + (64 * wave + ki) * 64 + 8 * (((2 * c) | h) ^ FA2_FUSED_DSKEY(ki)));
+        vset<kFusedRegFile, CL_TOP, DSWR + c>(lbase + DSB + (64 * wave + ki) * 64 + 8 * (((2 * c) | h) ^ FA2_FUSED_DSKEY(ki)));
     });
-    const int drow = lane / CPR, dslot = lane % CPR;
-    const int prow = wave * RPI + drow;
-    const int doff = drow * ROWB + 16 * ((lds_off<D>(prow, dslot) - ROWB * prow) >> 4);
+    const int doff = lds_dma_off<D>(wave * RPI, lane);
     const uint32_t dqv = CHAIN ? (uint32_t)(wave * 4096 + lane * 16) : (uint32_t)(((4 * h) * D + 32 * wave + ki) * 4);
     const auto rc_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)fp.rc, 0, (int)(2 * rc_plane * 4), 0x00020000);
 
@@ -476,7 +438,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(39))) f
         // dK^T, dV^T <- 0: sixteen MFMAs on a zero fragment instead of 256 accumulator writes
         {
             const u32x4 z = {0u, 0u, 0u, 0u};
-            static_for<4 * DT>([&](auto T) { fused_acc_zero<decltype(T)::value>(z); });
+            static_for<4 * DT>([&](auto T) { azero16<kFusedRegFile, CL_ACC, 16 * decltype(T)::value>(z); });
         }
 
         // ---- LDS-DMA staging of a 32-row Q / dO tile + its row constants into ring slot `buf`
@@ -512,8 +474,8 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(39))) f
         fused_dq_zero<DQT>();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                 // V fragments, K image and the first tile have landed
-        if constexpr (W) asm volatile(FA2_FUSED_PRO : : FA2_FUSED_OPS, [vm] "i"(VMW) : FA2_FUSED_CLOBBERS);
-        else asm volatile(FA2_FUSED64_PRO : : FA2_FUSED_OPS64, [vm] "i"(VMW) : FA2_FUSED_CLOBBERS);
+        if constexpr (W) asm volatile(FA2_FUSED_PRO : : FA2_FUSED_OPS_128, [vm] "i"(VMW) : FA2_FUSED_CLOBBERS);
+        else asm volatile(FA2_FUSED64_PRO : : FA2_FUSED_OPS_64, [vm] "i"(VMW) : FA2_FUSED_CLOBBERS);
 
         const auto dq_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(fp.dQacc + (size_t)head * NPQ * DQW), 0, NPQ * DQW * 4, 0x00020000);
         int* const mine = prog_base + head * ncb + cb;
@@ -552,7 +514,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(39))) f
 #ifdef FA2_TEST_HOOKS
                 if (fp.fault && cb == 1) f.pval = 0;
 #endif
-                fused_cbody<buf, par, VMW, false>(roff, toff, rcv, c2, dqv, (uint32_t)doff, (uint32_t)rcoff, lbase + QRING + wave * 1024,
+                fused_cbody<D, buf, par, VMW, false>(roff, toff, rcv, c2, dqv, (uint32_t)doff, (uint32_t)rcoff, lbase + QRING + wave * 1024,
                                                   lbase + QRING + wave * 128, wave, f, err, 0, 0);
             } else if constexpr (CHAIN) {
                 // body of step t: DMA of the sub-tile of step t + 1; E forms the dQ tile of the sub-tile of step t - 1 on top of
@@ -589,7 +551,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(39))) f
 #ifdef FA2_FUSED_STATS2
                 const uint64_t b0 = __builtin_readcyclecounter();
 #endif
-                fused_cbody<buf, par, VMW, masked>(roff, toff, rcv, c2, dqv, (uint32_t)doff, (uint32_t)rcoff, lbase + QRING + wave * 1024,
+                fused_cbody<D, buf, par, VMW, masked>(roff, toff, rcv, c2, dqv, (uint32_t)doff, (uint32_t)rcoff, lbase + QRING + wave * 1024,
                                                    lbase + QRING + wave * 128, wave, f, err, lo0, lo1);
 #ifdef FA2_FUSED_STATS2
                 st_cycles += (int)(__builtin_readcyclecounter() - b0);       // cycles inside the bodies (reported as "waited")
@@ -674,10 +636,10 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(39))) f
                     if (!RAGGED || key < N) *reinterpret_cast<u32x4*>(dst + 2 * (32 * dt + 16 * gp)) = o;      // (ragged: keys past the end)
 #endif
                 };
-                emit(pack4(acc_read<RK>(), acc_read<RK + 1>(), acc_read<RK + 2>(), acc_read<RK + 3>(), p.scale),
-                     pack4(acc_read<RK + 4>(), acc_read<RK + 5>(), acc_read<RK + 6>(), acc_read<RK + 7>(), p.scale), dKk);
-                emit(pack4(acc_read<RV>(), acc_read<RV + 1>(), acc_read<RV + 2>(), acc_read<RV + 3>(), 1.0f),
-                     pack4(acc_read<RV + 4>(), acc_read<RV + 5>(), acc_read<RV + 6>(), acc_read<RV + 7>(), 1.0f), dVk);
+                emit(pack4(aread<RK>(), aread<RK + 1>(), aread<RK + 2>(), aread<RK + 3>(), p.scale),
+                     pack4(aread<RK + 4>(), aread<RK + 5>(), aread<RK + 6>(), aread<RK + 7>(), p.scale), dKk);
+                emit(pack4(aread<RV>(), aread<RV + 1>(), aread<RV + 2>(), aread<RV + 3>(), 1.0f),
+                     pack4(aread<RV + 4>(), aread<RV + 5>(), aread<RV + 6>(), aread<RV + 7>(), 1.0f), dVk);
             });
         });
 #ifdef FA2_FUSED_STATS

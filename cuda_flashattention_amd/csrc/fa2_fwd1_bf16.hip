@@ -36,7 +36,7 @@
 // Measured same-box: (4,16,4096,64) 945 -> ~990 TFLOP/s, (4,16,8192,128) 1.692 -> ~1.65 ms.
 #include <type_traits>
 
-#include "fa2_common.h"
+#include "fa2_fwd_softmax.h"
 #include "fa2_launch.h"
 
 namespace fa2 {
@@ -45,7 +45,6 @@ namespace fa2 {
 
 constexpr int kF1Rows = 256;                 // query rows per workgroup (4 waves x 64 or 8 waves x 32)
 constexpr int kF1Bufs = 4;                  // LDS ring depth (tools/gen_fwd_body.py: NBUF)
-constexpr float kF1RescaleThr = 6.0f;       // natural-log units of the scaled score
 constexpr float kF1SumLimit = 1.2089258e24f; // 2^80: a row sum at or above it sends the workgroup through its row block again, with maxima
 constexpr float kF1LiftAt = 1.0737418e9f;    // 2^30: between two rounds without maxima, a row whose sum has passed it moves its reference up ...
 constexpr float kF1LiftBy = 44.3614196f;     // ... by 64 ln 2 (its sums and O^T scale by 2^-64)
@@ -58,83 +57,9 @@ typedef __attribute__((address_space(3))) void* f1_lptr_t;
 //   QBS = 1  two waves per SIMD: 8 waves x 32 rows, 128 + 128 registers per wave (hipcc: v0..v39), a[0:128) -- for d = 64,
 //            where the VALU (4 instructions per S element against half the MFMAs of d = 128) is the bound and two waves
 //            issue VALU instructions at ~4.4 clocks each against ~7 for one wave alone (tools/probes/softmax_port.hip)
-#define FA2_ACC128_LIST                                                                                                        \
-    "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", "a16", "a17", "a18", "a19", \
-    "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", "a32", "a33", "a34", "a35", "a36", "a37",     \
-    "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55",     \
-    "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73",     \
-    "a74", "a75", "a76", "a77", "a78", "a79", "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91",     \
-    "a92", "a93", "a94", "a95", "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108",   \
-    "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124",   \
-    "a125", "a126", "a127"
-#define FA2_F1_REGS2 "v255", FA2_ACC_CLOBBERS
-#define FA2_F1_REGS1 "v127", FA2_ACC128_LIST
-#define FA2_F1_MISC "memory", "vcc", "scc", "s10", "s11", "s12", "m0"
-
-// every asm statement below exists twice: with the register-file clobbers of the one-wave and of the two-wave shape
-#define FA2_F1_ASM(QBS, TEXT, OUTS, INS)                                                  \
-    do {                                                                                   \
-        if constexpr (QBS == 2) asm volatile(TEXT : OUTS : INS : FA2_F1_MISC, FA2_F1_REGS2); \
-        else asm volatile(TEXT : OUTS : INS : FA2_F1_MISC, FA2_F1_REGS1);                  \
-    } while (0)
-#define FA2_F1_COMMA ,
-
-template <int QBS, int R>
-__device__ __forceinline__ void f1_vset(uint32_t x)
-{
-    FA2_F1_ASM(QBS, "v_mov_b32 v%c1, %0", , "v"(x) FA2_F1_COMMA "i"(R));
-}
-template <int QBS, int R>
-__device__ __forceinline__ void f1_vsetf(float x)
-{
-    FA2_F1_ASM(QBS, "v_mov_b32 v%c1, %0", , "v"(x) FA2_F1_COMMA "i"(R));
-}
-template <int R>
-__device__ __forceinline__ float f1_vget()
-{
-    float x;
-    asm volatile("v_mov_b32 %0, v%c1" : "=v"(x) : "i"(R));
-    return x;
-}
-template <int QBS, int R>
-__device__ __forceinline__ void f1_awrite(float x)
-{
-    FA2_F1_ASM(QBS, "v_accvgpr_write_b32 a[%c1], %0", , "v"(x) FA2_F1_COMMA "i"(R));
-}
-template <int R>
-__device__ __forceinline__ float f1_aread()
-{
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(x) : "i"(R));
-    return x;
-}
-template <int QBS, int LO>
-__device__ __forceinline__ void f1_awrite_frag(bf16x8 f)
-{
-    const u32x4 w = __builtin_bit_cast(u32x4, f);
-    FA2_F1_ASM(QBS, "v_accvgpr_write_b32 a[%c4], %0\n\tv_accvgpr_write_b32 a[%c5], %1\n\tv_accvgpr_write_b32 a[%c6], %2\n\t"
-                    "v_accvgpr_write_b32 a[%c7], %3", ,
-               "v"(w[0]) FA2_F1_COMMA "v"(w[1]) FA2_F1_COMMA "v"(w[2]) FA2_F1_COMMA "v"(w[3]) FA2_F1_COMMA "i"(LO) FA2_F1_COMMA "i"(LO + 1)
-                   FA2_F1_COMMA "i"(LO + 2) FA2_F1_COMMA "i"(LO + 3));
-}
-// four accumulator registers *= alpha (per lane = per query row)
-template <int QBS, int R>
-__device__ __forceinline__ void f1_scale4(float alpha)
-{
-    float t0, t1, t2, t3;
-    FA2_F1_ASM(QBS, "v_accvgpr_read_b32 %0, a[%c5]\n\tv_accvgpr_read_b32 %1, a[%c6]\n\t"
-                    "v_accvgpr_read_b32 %2, a[%c7]\n\tv_accvgpr_read_b32 %3, a[%c8]\n\t"
-                    "v_mul_f32 %0, %0, %4\n\tv_mul_f32 %1, %1, %4\n\tv_mul_f32 %2, %2, %4\n\tv_mul_f32 %3, %3, %4\n\t"
-                    "v_accvgpr_write_b32 a[%c5], %0\n\tv_accvgpr_write_b32 a[%c6], %1\n\t"
-                    "v_accvgpr_write_b32 a[%c7], %2\n\tv_accvgpr_write_b32 a[%c8], %3",
-               "=&v"(t0) FA2_F1_COMMA "=&v"(t1) FA2_F1_COMMA "=&v"(t2) FA2_F1_COMMA "=&v"(t3),
-               "v"(alpha) FA2_F1_COMMA "i"(R) FA2_F1_COMMA "i"(R + 1) FA2_F1_COMMA "i"(R + 2) FA2_F1_COMMA "i"(R + 3));
-}
-template <int QBS, int R>
-__device__ __forceinline__ void f1_acc_zero(u32x4 z)
-{
-    FA2_F1_ASM(QBS, "s_nop 1\n\tv_mfma_f32_32x32x16_bf16 a[%c1:%c2], %0, %0, 0", , "v"(z) FA2_F1_COMMA "i"(R) FA2_F1_COMMA "i"(R + 15));
-}
+// Every statement that names a body-owned register is compiled with the clobbers of its shape (fa2_regfile.h), the bodies and
+// everything that seeds their registers with the bodies' own class, CL_ORDER.
+template <int QBS> constexpr int kF1RegFile = QBS == 2 ? RF512 : RF128;
 
 struct F1Dma {
     __amdgpu_buffer_rsrc_t krs, vrs;
@@ -148,10 +73,10 @@ __device__ __forceinline__ void f1_body(float c2, int& need, const int (&hi)[2],
 {
 #define FA2_F1_CASE(TAG, DD, QQ, B, K, MV, M)                                                                                      \
     if constexpr (D == DD && QBS == QQ && BUF == B && KB == K && MODE == MV)                                                         \
-        FA2_F1_ASM(QQ, FA2_FWD_BODY_##TAG##_B##B##_K##K##_##M, [need] "=&s"(need),                                                     \
-                   [c2] "s"(c2) FA2_F1_COMMA [hi0] "v"(hi[0]) FA2_F1_COMMA [hi1] "v"(hi[1]) FA2_F1_COMMA [ninf] "v"(-INFINITY)           \
-                       FA2_F1_COMMA [mw] "s"(dma.mw) FA2_F1_COMMA [dvo] "v"(dma.dvo) FA2_F1_COMMA [krs] "s"(dma.krs)                     \
-                       FA2_F1_COMMA [vrs] "s"(dma.vrs) FA2_F1_COMMA [kso] "s"(dma.kso));
+        FA2_RF_ASM(kF1RegFile<QQ>, CL_ORDER, FA2_FWD_BODY_##TAG##_B##B##_K##K##_##M, [need] "=&s"(need),                                                     \
+                   [c2] "s"(c2) FA2_COMMA [hi0] "v"(hi[0]) FA2_COMMA [hi1] "v"(hi[1]) FA2_COMMA [ninf] "v"(-INFINITY)           \
+                       FA2_COMMA [mw] "s"(dma.mw) FA2_COMMA [dvo] "v"(dma.dvo) FA2_COMMA [krs] "s"(dma.krs)                     \
+                       FA2_COMMA [vrs] "s"(dma.vrs) FA2_COMMA [kso] "s"(dma.kso));
 #define FA2_F1_CASES_B(TAG, DD, QQ, K, MV, M) \
     FA2_F1_CASE(TAG, DD, QQ, 0, K, MV, M) FA2_F1_CASE(TAG, DD, QQ, 1, K, MV, M) FA2_F1_CASE(TAG, DD, QQ, 2, K, MV, M) FA2_F1_CASE(TAG, DD, QQ, 3, K, MV, M)
 #define FA2_F1_CASES_V(TAG, DD, QQ, K) \
@@ -167,28 +92,21 @@ __device__ __forceinline__ void f1_body(float c2, int& need, const int (&hi)[2],
 template <int D, int QBS>
 __device__ __forceinline__ void f1_prologue()
 {
-    if constexpr (D == 128) FA2_F1_ASM(2, FA2_FWD_PRO_D128Q2, , );
-    else if constexpr (QBS == 2) FA2_F1_ASM(2, FA2_FWD_PRO_D64Q2, , );
-    else FA2_F1_ASM(1, FA2_FWD_PRO_D64Q1, , );
+    if constexpr (D == 128) FA2_RF_ASM(RF512, CL_ORDER, FA2_FWD_PRO_D128Q2, , );
+    else if constexpr (QBS == 2) FA2_RF_ASM(RF512, CL_ORDER, FA2_FWD_PRO_D64Q2, , );
+    else FA2_RF_ASM(RF128, CL_ORDER, FA2_FWD_PRO_D64Q1, , );
 }
 
 // generator constants of a configuration
 template <int D, int QBS> struct F1Map;
-template <> struct F1Map<128, 2> {
-    static constexpr int KV = FA2_FWD_D128Q2_KV, SET0 = FA2_FWD_D128Q2_SET0, SET1 = FA2_FWD_D128Q2_SET1, PF0 = FA2_FWD_D128Q2_PF0,
-                         ROFF = FA2_FWD_D128Q2_ROFF, TOFFV = FA2_FWD_D128Q2_TOFFV, ST = FA2_FWD_D128Q2_STATE, V0 = FA2_FWD_D128Q2_V0,
-                         A_QF = FA2_FWD_D128Q2_A_QF;
-};
-template <> struct F1Map<64, 2> {
-    static constexpr int KV = FA2_FWD_D64Q2_KV, SET0 = FA2_FWD_D64Q2_SET0, SET1 = FA2_FWD_D64Q2_SET1, PF0 = FA2_FWD_D64Q2_PF0,
-                         ROFF = FA2_FWD_D64Q2_ROFF, TOFFV = FA2_FWD_D64Q2_TOFFV, ST = FA2_FWD_D64Q2_STATE, V0 = FA2_FWD_D64Q2_V0,
-                         A_QF = FA2_FWD_D64Q2_A_QF;
-};
-template <> struct F1Map<64, 1> {
-    static constexpr int KV = FA2_FWD_D64Q1_KV, SET0 = FA2_FWD_D64Q1_SET0, SET1 = FA2_FWD_D64Q1_SET1, PF0 = FA2_FWD_D64Q1_PF0,
-                         ROFF = FA2_FWD_D64Q1_ROFF, TOFFV = FA2_FWD_D64Q1_TOFFV, ST = FA2_FWD_D64Q1_STATE, V0 = FA2_FWD_D64Q1_V0,
-                         A_QF = FA2_FWD_D64Q1_A_QF;
-};
+#define FA2_F1_MAP(TAG, DD, QQ)                                                                                                 \
+    template <> struct F1Map<DD, QQ> {                                                                                          \
+        static constexpr int KV = FA2_FWD_##TAG##_KV, SET0 = FA2_FWD_##TAG##_SET0, SET1 = FA2_FWD_##TAG##_SET1,                 \
+                             PF0 = FA2_FWD_##TAG##_PF0, ROFF = FA2_FWD_##TAG##_ROFF, TOFFV = FA2_FWD_##TAG##_TOFFV,             \
+                             ST = FA2_FWD_##TAG##_STATE, V0 = FA2_FWD_##TAG##_V0, A_QF = FA2_FWD_##TAG##_A_QF;                 \
+    };
+FA2_F1_MAP(D128Q2, 128, 2) FA2_F1_MAP(D64Q2, 64, 2) FA2_F1_MAP(D64Q1, 64, 1)
+#undef FA2_F1_MAP
 
 template <int D, int QBS, bool CAUSAL, bool STATE>
 __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
@@ -196,6 +114,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ROWB = D * 2;
     using M = F1Map<D, QBS>;
+    constexpr int RF = kF1RegFile<QBS>, CL = CL_ORDER;
     constexpr int kF1Waves = 8 / QBS;                                    // 4 waves x 64 rows or 8 waves x 32 rows
     constexpr int WROWS = 32 * QBS;                                      // query rows per wave
     constexpr int KV = M::KV;                                            // keys per tile
@@ -257,9 +176,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
     const int JB = J + 2;
 
     // ---- LDS-DMA staging (per-lane source offset pre-swizzled, wave-uniform soffset, rows >= Nk read as zeros)
-    const int drow = lane / CPR, dslot = lane % CPR;
-    const int prow = wave * RPI + drow;
-    const int doff = drow * ROWB + 16 * ((lds_off<D>(prow, dslot) - ROWB * prow) >> 4);
+    const int doff = lds_dma_off<D>(wave * RPI, lane);
     const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Kh, 0, Nk * ROWB, 0x00020000);
     const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Vh, 0, Nk * ROWB, 0x00020000);
     auto stage = [&](int t, int buf) {
@@ -280,7 +197,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
         const int qld = qrow[qb] < Nq ? qrow[qb] : Nq - 1;
         static_for<KS>([&](auto S) {
             constexpr int sidx = decltype(S)::value;
-            f1_awrite_frag<QBS, A_QF + (qb * KS + sidx) * 4>(*reinterpret_cast<const bf16x8*>(Qh + (size_t)qld * ROWB + 16 * (2 * sidx + h)));
+            awrite_frag<RF, CL, A_QF + (qb * KS + sidx) * 4>(*reinterpret_cast<const bf16x8*>(Qh + (size_t)qld * ROWB + 16 * (2 * sidx + h)));
         });
     });
 
@@ -309,31 +226,31 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
                 static_for<4 * DT>([&](auto G) {
                     constexpr int dt = decltype(G)::value / 4, g = decltype(G)::value % 4;
                     const f32x4 v = *reinterpret_cast<const f32x4*>(Oa + 32 * dt + 8 * g + 4 * h);
-                    static_for<4>([&](auto E) { f1_awrite<QBS, A_O + (qb * DT + dt) * 16 + 4 * g + decltype(E)::value>(v[decltype(E)::value]); });
+                    static_for<4>([&](auto E) { awrite<RF, CL, A_O + (qb * DT + dt) * 16 + 4 * g + decltype(E)::value>(v[decltype(E)::value]); });
                 });
                 m_run[qb] = p.M[(size_t)head * qhs + qld];
-                f1_vsetf<QBS, ST + 2 * qb>(h == 0 ? p.L[(size_t)head * qhs + qld] : 0.0f);
-                f1_vsetf<QBS, ST + 2 * qb + 1>(0.0f);
-                f1_vsetf<QBS, ST_MB + qb>(m_run[qb] == -INFINITY ? 0.0f : m_run[qb] * kLog2e);
-                f1_vsetf<QBS, ST_TH + qb>((m_run[qb] + kF1RescaleThr) * inv_scale);
+                vset<RF, CL, ST + 2 * qb>(h == 0 ? p.L[(size_t)head * qhs + qld] : 0.0f);
+                vset<RF, CL, ST + 2 * qb + 1>(0.0f);
+                vset<RF, CL, ST_MB + qb>(m_run[qb] == -INFINITY ? 0.0f : m_run[qb] * kLog2e);
+                vset<RF, CL, ST_TH + qb>((m_run[qb] + kFwdRescaleThr) * inv_scale);
             });
         } else {
             const u32x4 z = {0u, 0u, 0u, 0u};
-            static_for<QBS * DT>([&](auto T) { f1_acc_zero<QBS, A_O + 16 * decltype(T)::value>(z); });
+            static_for<QBS * DT>([&](auto T) { azero16<RF, CL, A_O + 16 * decltype(T)::value>(z); });
             static_for<QBS>([&](auto QB) {
                 constexpr int qb = decltype(QB)::value;
                 m_run[qb] = -INFINITY;
-                f1_vsetf<QBS, ST + 2 * qb>(0.0f);
-                f1_vsetf<QBS, ST + 2 * qb + 1>(0.0f);
-                f1_vsetf<QBS, ST_MB + qb>(0.0f);
-                f1_vsetf<QBS, ST_TH + qb>(-INFINITY);
+                vset<RF, CL, ST + 2 * qb>(0.0f);
+                vset<RF, CL, ST + 2 * qb + 1>(0.0f);
+                vset<RF, CL, ST_MB + qb>(0.0f);
+                vset<RF, CL, ST_TH + qb>(-INFINITY);
             });
         }
         // S sets and packed P of "the blocks before the first": exp2(-huge) = 0 and P = 0, so the first two bodies add exactly zero
         static_for<16 * QBS>([&](auto R) {
-            f1_vsetf<QBS, SET0 + decltype(R)::value>(-1.0e30f);
-            f1_vsetf<QBS, SET1 + decltype(R)::value>(-1.0e30f);
-            f1_vset<QBS, PF0 + decltype(R)::value>(0u);
+            vset<RF, CL, SET0 + decltype(R)::value>(-1.0e30f);
+            vset<RF, CL, SET1 + decltype(R)::value>(-1.0e30f);
+            vset<RF, CL, PF0 + decltype(R)::value>(0u);
         });
     };
 
@@ -343,11 +260,11 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
         const int trq = (lane & 15) >> 2, trp = lane & 3, trcb = (lane >> 4) & 1;
         static_for<KS>([&](auto S) {
             constexpr int sidx = decltype(S)::value;
-            f1_vset<QBS, ROFF + sidx>(lbase + lds_off<D>(qi, 2 * sidx + h));
+            vset<RF, CL, ROFF + sidx>(lbase + lds_off<D>(qi, 2 * sidx + h));
         });
         static_for<2 * DT>([&](auto I) {
             constexpr int dt = decltype(I)::value / 2, jj = decltype(I)::value % 2;
-            f1_vset<QBS, TOFFV + decltype(I)::value>(lbase + KRING + lds_off<D>(8 * jj + 4 * h + trq, 4 * dt + 2 * trcb + (trp >> 1)) + 8 * (trp & 1));
+            vset<RF, CL, TOFFV + decltype(I)::value>(lbase + KRING + lds_off<D>(8 * jj + 4 * h + trq, 4 * dt + 2 * trcb + (trp >> 1)) + 8 * (trp & 1));
         });
     }
     const float c2 = p.scale * kLog2e;
@@ -371,7 +288,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
             mfma_acc_settle();
             static_for<QBS>([&](auto QB) {
                 constexpr int qb = decltype(QB)::value;
-                static_for<4 * DT>([&](auto R4) { f1_scale4<QBS, A_O + qb * DT * 16 + 4 * decltype(R4)::value>(pend[qb]); });
+                fwd_rescale_o<RF, CL, A_O + qb * DT * 16, 4 * DT>(pend[qb]);
                 pend[qb] = 1.0f;
             });
             have_pend = false;
@@ -381,18 +298,11 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
             bool any_scale = false;
             static_for<QBS>([&](auto QB) {
                 constexpr int qb = decltype(QB)::value;
-                const float mx = half_max(f1_vget<ST_RM + qb>()) * p.scale;
-                const bool grow = mx > m_run[qb] + kF1RescaleThr;        // also true from m_run = -inf
-                const bool any_grow = __any(grow);
-                const float m_new = any_grow ? fmaxf(m_run[qb], mx) : m_run[qb];
+                const float mx = half_max(vget<ST_RM + qb>()) * p.scale;
                 // O only needs scaling if some row already accumulated something at an older reference
-                const bool sc = any_grow && __any(m_run[qb] != -INFINITY && m_new != m_run[qb]);
-                const float alpha = m_new == -INFINITY ? 1.0f : __builtin_amdgcn_exp2f((m_run[qb] - m_new) * kLog2e);
+                FA2_FWD_NEW_REFERENCE(m_run[qb], mx);
                 m_run[qb] = m_new;
-                f1_vsetf<QBS, ST_MB + qb>(m_new == -INFINITY ? 0.0f : m_new * kLog2e);      // a row with no visible key yet keeps p = 0
-                f1_vsetf<QBS, ST_TH + qb>((m_new + kF1RescaleThr) * inv_scale);
-                f1_vsetf<QBS, ST + 2 * qb>(f1_vget<ST + 2 * qb>() * alpha);
-                f1_vsetf<QBS, ST + 2 * qb + 1>(f1_vget<ST + 2 * qb + 1>() * alpha);
+                fwd_write_reference<RF, CL, ST + 2 * qb, ST_MB + qb, ST_TH + qb>(m_new, alpha, inv_scale);
                 pend[qb] = sc ? alpha : 1.0f;
                 any_scale = any_scale || sc;
             });
@@ -416,7 +326,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
         for (int qb = 0; qb < QBS; ++qb) over[qb] = false;
         static_for<QBS>([&](auto QB) {
             constexpr int qb = decltype(QB)::value;
-            const float lt = f1_vget<ST + 2 * qb>() + f1_vget<ST + 2 * qb + 1>();      // this lane's half of the row's sum
+            const float lt = vget<ST + 2 * qb>() + vget<ST + 2 * qb + 1>();      // this lane's half of the row's sum
             out_of_range = out_of_range || !(lt < kF1SumLimit);                          // also true for NaN / inf
             over[qb] = half_max(lt) > kF1LiftAt;      // both lanes of a row agree
             any = any || over[qb];
@@ -429,10 +339,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
             const float m_new = over[qb] ? m_run[qb] + kF1LiftBy : m_run[qb];
             const float alpha = over[qb] ? __builtin_amdgcn_exp2f((m_run[qb] - m_new) * kLog2e) : 1.0f;
             m_run[qb] = m_new;
-            f1_vsetf<QBS, ST_MB + qb>(m_new == -INFINITY ? 0.0f : m_new * kLog2e);
-            f1_vsetf<QBS, ST_TH + qb>((m_new + kF1RescaleThr) * inv_scale);
-            f1_vsetf<QBS, ST + 2 * qb>(f1_vget<ST + 2 * qb>() * alpha);
-            f1_vsetf<QBS, ST + 2 * qb + 1>(f1_vget<ST + 2 * qb + 1>() * alpha);
+            fwd_write_reference<RF, CL, ST + 2 * qb, ST_MB + qb, ST_TH + qb>(m_new, alpha, inv_scale);
             pend[qb] = alpha;
         });
         have_pend = true;
@@ -480,8 +387,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
     int nfull_wg = Nk / KV;
     if (CAUSAL) nfull_wg = min(nfull_wg, max(0, (rb * kF1Rows + (kF1Waves - 1) * WROWS + p.causal_shift + 1) / KV));
     nfull_wg = min(nfull_wg, J / NH) & ~3;
-    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+    using I0 = Int<0>; using I1 = Int<1>; using I2 = Int<2>; using I3 = Int<3>;
     // Pass 0: lane maxima in the first tile only (see the header).  Pass 1 (`safe`), entered only when a row
     // sum of the workgroup left the range pass 0 vouches for: maxima in every body.
     int* const redo_flag = reinterpret_cast<int*>(smem + 2 * KRING);
@@ -503,15 +409,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
                 run_tile(I0{}, I2{}, t); run_tile(I1{}, I2{}, t + 1); run_tile(I2{}, I2{}, t + 2); run_tile(I3{}, I2{}, t + 3);
             }
         }
-        for (; t < ntl; t += 4) {
-            run_tile(I0{}, I1{}, t);
-            if (t + 1 >= ntl) break;
-            run_tile(I1{}, I1{}, t + 1);
-            if (t + 2 >= ntl) break;
-            run_tile(I2{}, I1{}, t + 2);
-            if (t + 3 >= ntl) break;
-            run_tile(I3{}, I1{}, t + 3);
-        }
+        FA2_FWD_TAIL_TILES(run_tile, t, ntl);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");       // the last bodies' look-ahead DMA and reads
         // Did any row of the WORKGROUP leave the range the X rounds vouch for?  (Every decision here is workgroup-uniform:
         // the restart goes through the tile barriers again.  nfull_wg: the workgroup's last wave has the most full rounds.)
@@ -519,7 +417,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
         bool bad = out_of_range;         // a sum seen out of range by a lift, although lifted back since
         static_for<QBS>([&](auto QB) {
             constexpr int qb = decltype(QB)::value;
-            bad = bad || !(half_sum(f1_vget<ST + 2 * qb>() + f1_vget<ST + 2 * qb + 1>()) < kF1SumLimit);      // also true for NaN
+            bad = bad || !(half_sum(vget<ST + 2 * qb>() + vget<ST + 2 * qb + 1>()) < kF1SumLimit);      // also true for NaN
         });
         if (tid == 0) *redo_flag = 0;
         __syncthreads();
@@ -534,26 +432,17 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
     const bool fin = !STATE || p.finalize;
     static_for<QBS>([&](auto QB) {
         constexpr int qb = decltype(QB)::value;
-        const float l_tot = half_sum(f1_vget<ST + 2 * qb>() + f1_vget<ST + 2 * qb + 1>());
+        const float l_tot = half_sum(vget<ST + 2 * qb>() + vget<ST + 2 * qb + 1>());
         const size_t qoff = (size_t)head * qhs + qrow[qb];
         const float pa = pend[qb];                 // an O rescale still pending from the last update (1 otherwise)
         const float inv = (fin ? (l_tot > 0.0f ? 1.0f / l_tot : 0.0f) : 1.0f) * pa;
-        // a lane holds 4 consecutive columns of its row per register quad, its partner lane (+32) the next 4: for the bf16
-        // output one v_permlane32_swap per packed dword pairs them up, so that every lane stores 16 contiguous bytes
         static_for<2 * DT>([&](auto G) {
             constexpr int dt = decltype(G)::value / 2, gp = decltype(G)::value % 2;
             constexpr int R = A_O + (qb * DT + dt) * 16 + 8 * gp;
             f32x4 v, w;
-            v[0] = f1_aread<R>() * inv; v[1] = f1_aread<R + 1>() * inv; v[2] = f1_aread<R + 2>() * inv; v[3] = f1_aread<R + 3>() * inv;
-            w[0] = f1_aread<R + 4>() * inv; w[1] = f1_aread<R + 5>() * inv; w[2] = f1_aread<R + 6>() * inv; w[3] = f1_aread<R + 7>() * inv;
+            fwd_read_o8<R>(inv, v, w);
             if (fin) {
-                bf16x4 x, y;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { x[e] = (__bf16)v[e]; y[e] = (__bf16)w[e]; }
-                const u32x2 xu = __builtin_bit_cast(u32x2, x), yu = __builtin_bit_cast(u32x2, y);
-                const auto s0 = __builtin_amdgcn_permlane32_swap(xu[0], yu[0], false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(xu[1], yu[1], false, false);
-                const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+                const u32x4 o = fwd_pack_o8_bf16(v, w);
                 if (qrow[qb] < Nq) *reinterpret_cast<u32x4*>((char*)p.O + qoff * ROWB + 2 * (32 * dt + 16 * gp + 8 * h)) = o;
             } else if (qrow[qb] < Nq) {
                 *reinterpret_cast<f32x4*>(p.Oacc + qoff * D + 32 * dt + 16 * gp + 4 * h) = v;

@@ -35,7 +35,7 @@
 // the first round (no reference yet), the sequence tail and the causal diagonal run the bodies with maxima.
 #include <type_traits>
 
-#include "fa2_common.h"
+#include "fa2_fwd_softmax.h"
 #include "fa2_launch.h"
 
 namespace fa2 {
@@ -47,71 +47,14 @@ constexpr int kF8Rows = 32 * kF8Waves;
 constexpr int kF8KV = FA2_F8_KV;            // keys per LDS tile (two bodies of 64)
 constexpr int kF8Bufs = FA2_F8_NBUF;
 constexpr int kF8D = 128;
-constexpr float kF8RescaleThr = 6.0f;
 
 typedef __attribute__((address_space(3))) void* f8_lds_ptr_t;
 
-#define FA2_F8_CLOBBERS \
-    "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", \
-    "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", \
-    "a32", "a33", "a34", "a35", "a36", "a37", "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", \
-    "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55", "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", \
-    "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73", "a74", "a75", "a76", "a77", "a78", "a79", \
-    "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91", "a92", "a93", "a94", "a95", \
-    "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", \
-    "a110", "a111", "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", \
-    "a124", "a125", "a126", "a127"
-// every statement that names a body-owned register: the whole accumulator file and v127 (so that the kernel is allocated all
-// 128 VGPRs: hipcc itself stays below FA2_F8_V0, amdgpu_num_vgpr)
-#define FA2_F8_REGS "v127", FA2_F8_CLOBBERS
-#define FA2_F8_MISC "memory", "vcc", "scc", "s10", "s11", "s12", "m0"
-
-template <int R>
-__device__ __forceinline__ void f8_vset(uint32_t x)
-{
-    asm volatile("v_mov_b32 v%c1, %0" : : "v"(x), "i"(R) : FA2_F8_REGS);
-}
-template <int R>
-__device__ __forceinline__ void f8_vsetf(float x)
-{
-    asm volatile("v_mov_b32 v%c1, %0" : : "v"(x), "i"(R) : FA2_F8_REGS);
-}
-template <int R>
-__device__ __forceinline__ float f8_vget()
-{
-    float x;
-    asm volatile("v_mov_b32 %0, v%c1" : "=v"(x) : "i"(R));
-    return x;
-}
-template <int R>
-__device__ __forceinline__ void f8_acc_write(uint32_t x)
-{
-    asm volatile("v_accvgpr_write_b32 a[%c1], %0" : : "v"(x), "i"(R) : FA2_F8_REGS);
-}
-template <int R>
-__device__ __forceinline__ float f8_acc_read()
-{
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(x) : "i"(R));
-    return x;
-}
-template <int R>
-__device__ __forceinline__ void f8_acc_scale4(float alpha)
-{
-    float t0, t1, t2, t3;
-    asm volatile("v_accvgpr_read_b32 %0, a[%c5]\n\tv_accvgpr_read_b32 %1, a[%c6]\n\t"
-                 "v_accvgpr_read_b32 %2, a[%c7]\n\tv_accvgpr_read_b32 %3, a[%c8]\n\t"
-                 "v_mul_f32 %0, %0, %4\n\tv_mul_f32 %1, %1, %4\n\tv_mul_f32 %2, %2, %4\n\tv_mul_f32 %3, %3, %4\n\t"
-                 "v_accvgpr_write_b32 a[%c5], %0\n\tv_accvgpr_write_b32 a[%c6], %1\n\t"
-                 "v_accvgpr_write_b32 a[%c7], %2\n\tv_accvgpr_write_b32 a[%c8], %3"
-                 : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
-                 : "v"(alpha), "i"(R), "i"(R + 1), "i"(R + 2), "i"(R + 3) : FA2_F8_REGS);
-}
-template <int R>
-__device__ __forceinline__ void f8_acc_zero(u32x4 z)
-{
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 a[%c1:%c2], %0, %0, 0" : : "v"(z), "i"(R), "i"(R + 15) : FA2_F8_REGS);
-}
+// Two waves per SIMD: every statement that names a body-owned register states the 128 + 128 shape (fa2_regfile.h), so that
+// the kernel is allocated all 128 VGPRs (hipcc itself stays below FA2_F8_V0, amdgpu_num_vgpr).  The bodies carry the whole
+// list (CL_ORDER); the statements that seed their registers only the file (CL_FILE): with 32 compiler registers the wider
+// list moves hipcc's prologue.
+constexpr int kF8RegFile = RF128, kF8Seed = CL_FILE;
 
 // a wave-uniform float into an SGPR (the builtin is typed int: the value goes through it as bits)
 __device__ __forceinline__ float f8_uniform(float x)
@@ -199,11 +142,10 @@ __device__ __forceinline__ void f8_body(float c2, int& need, int hi, const F8Dma
 {
 #define FA2_F8_CASE(B, K, MV, M)                                                                                              \
     if constexpr (BUF == B && KB == K && MODE == MV)                                                                           \
-        asm volatile(FA2_F8_BODY_B##B##_K##K##_##M                                                                             \
-                     : [need] "=&s"(need)                                                                                      \
-                     : [c2] "s"(c2), [hi] "v"(hi), [ninf] "v"(-INFINITY), [mw] "s"(dma.mw), [dvk] "v"(dma.dvk), [dvv] "v"(dma.dvv), \
-                       [krs] "s"(dma.krs), [vrs] "s"(dma.vrs), [kso] "s"(dma.kso), [vso] "s"(dma.vso)                           \
-                     : FA2_F8_MISC, FA2_F8_REGS);
+        FA2_RF_ASM(RF128, CL_ORDER, FA2_F8_BODY_B##B##_K##K##_##M, [need] "=&s"(need),                                            \
+                   [c2] "s"(c2) FA2_COMMA [hi] "v"(hi) FA2_COMMA [ninf] "v"(-INFINITY) FA2_COMMA [mw] "s"(dma.mw)                 \
+                       FA2_COMMA [dvk] "v"(dma.dvk) FA2_COMMA [dvv] "v"(dma.dvv) FA2_COMMA [krs] "s"(dma.krs)                     \
+                       FA2_COMMA [vrs] "s"(dma.vrs) FA2_COMMA [kso] "s"(dma.kso) FA2_COMMA [vso] "s"(dma.vso));
 #define FA2_F8_CASES(K, MV, M) FA2_F8_CASE(0, K, MV, M) FA2_F8_CASE(1, K, MV, M) FA2_F8_CASE(2, K, MV, M) FA2_F8_CASE(3, K, MV, M)
     FA2_F8_CASES(0, F8_PLAIN, M0) FA2_F8_CASES(1, F8_PLAIN, M0) FA2_F8_CASES(0, F8_MASKED, M1) FA2_F8_CASES(1, F8_MASKED, M1)
     FA2_F8_CASES(0, F8_NOMAX, X) FA2_F8_CASES(1, F8_NOMAX, X)
@@ -222,6 +164,7 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
     constexpr int DT = kF8D / 32;
     constexpr int SET0 = FA2_F8_SET0, SET1 = FA2_F8_SET1, PF0 = FA2_F8_PF0, KA = FA2_F8_KA, VA = FA2_F8_VA, ST = FA2_F8_STATE;
     constexpr int ST_RM = ST + 2, ST_MB = ST + 3, ST_TH = ST + 4, A_QF = FA2_F8_A_QF;
+    constexpr int RF = kF8RegFile, CL = kF8Seed;
     static_assert(TILEB == 16384 && NH == 2 && kF8Bufs == 4, "LDS ring as the generator lays it out");
 
     const int tid = threadIdx.x;
@@ -297,8 +240,8 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
         const u32x4 hi = *reinterpret_cast<const u32x4*>(Qh + (size_t)qld * ROWB + 64 * s + 32 * h + 16);
         static_for<4>([&](auto E) {
             constexpr int e = decltype(E)::value;
-            f8_acc_write<A_QF + 8 * s + e>(lo[e]);
-            f8_acc_write<A_QF + 8 * s + 4 + e>(hi[e]);
+            awrite<RF, CL, A_QF + 8 * s + e>(lo[e]);
+            awrite<RF, CL, A_QF + 8 * s + 4 + e>(hi[e]);
             const auto a = __builtin_amdgcn_cvt_pk_f32_fp8(lo[e], false), b = __builtin_amdgcn_cvt_pk_f32_fp8(lo[e], true);
             const auto c = __builtin_amdgcn_cvt_pk_f32_fp8(hi[e], false), d = __builtin_amdgcn_cvt_pk_f32_fp8(hi[e], true);
             qss += a[0] * a[0] + a[1] * a[1] + b[0] * b[0] + b[1] * b[1] + c[0] * c[0] + c[1] * c[1] + d[0] * d[0] + d[1] * d[1];
@@ -311,7 +254,7 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
     const float* knh = p.kn + (size_t)head * (Npad / 64);
     {
         const u32x4 z = {0u, 0u, 0u, 0u};
-        static_for<DT>([&](auto T) { f8_acc_zero<16 * decltype(T)::value>(z); });
+        static_for<DT>([&](auto T) { azero16<RF, CL, 16 * decltype(T)::value>(z); });
     }
 
     // ---- running state.  m_run (the reference, natural units) and the deferred O scale are hipcc's; the row sums (two partial
@@ -321,16 +264,16 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
     float m_run = -INFINITY, pend = 1.0f;
     float m_min6 = -INFINITY;             // wave-uniform: the smallest threshold (reference + 6, natural units) among the wave's rows
     bool have_pend = false;
-    f8_vsetf<ST>(0.0f);
-    f8_vsetf<ST + 1>(0.0f);
-    f8_vsetf<ST_MB>(0.0f);
-    f8_vsetf<ST_TH>(-INFINITY);
+    vset<RF, CL, ST>(0.0f);
+    vset<RF, CL, ST + 1>(0.0f);
+    vset<RF, CL, ST_MB>(0.0f);
+    vset<RF, CL, ST_TH>(-INFINITY);
     // S sets and packed P of "the keys before the first": exp2(-huge) = 0 and P = 0, so the first two bodies add exactly zero
     static_for<32>([&](auto R) {
-        f8_vsetf<SET0 + decltype(R)::value>(-1.0e30f);
-        f8_vsetf<SET1 + decltype(R)::value>(-1.0e30f);
+        vset<RF, CL, SET0 + decltype(R)::value>(-1.0e30f);
+        vset<RF, CL, SET1 + decltype(R)::value>(-1.0e30f);
     });
-    static_for<16>([&](auto R) { f8_vset<PF0 + decltype(R)::value>(0u); });
+    static_for<16>([&](auto R) { vset<RF, CL, PF0 + decltype(R)::value>(0u); });
 
     // ---- loop-invariant LDS addresses into the registers the bodies name.  K fragment (blk, s), half i: row pi(qi) + 32 blk
     // (+ 64 per body), chunk 4 s + 2 h + i; V^T fragment dt: row 32 dt + qi of a half, chunks h (keys 16 h ..) and 2 + h
@@ -340,10 +283,10 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
         const int prow = f8_pi(qi);
         static_for<4>([&](auto I) {
             constexpr int s = decltype(I)::value / 2, i = decltype(I)::value % 2;
-            f8_vset<KA + decltype(I)::value>(lbase + prow * ROWB + 16 * ((4 * s + 2 * h + i) ^ f8_fk(prow)));
+            vset<RF, CL, KA + decltype(I)::value>(lbase + prow * ROWB + 16 * ((4 * s + 2 * h + i) ^ f8_fk(prow)));
         });
-        f8_vset<VA>(lbase + KRING + qi * 64 + 16 * (h ^ f8_fv(qi)));
-        f8_vset<VA + 1>(lbase + KRING + qi * 64 + 16 * ((2 + h) ^ f8_fv(qi)));
+        vset<RF, CL, VA>(lbase + KRING + qi * 64 + 16 * (h ^ f8_fv(qi)));
+        vset<RF, CL, VA + 1>(lbase + KRING + qi * 64 + 16 * ((2 + h) ^ f8_fv(qi)));
     }
     const float c2 = p.scale * kLog2e;
     F8Dma dma;
@@ -360,7 +303,7 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
 #ifndef FA2_F8_NO_SETPRIO
     if (wave >= kF8Waves / 2) __builtin_amdgcn_s_setprio(1);
 #endif
-    asm volatile(FA2_F8_PRO : : : FA2_F8_MISC, FA2_F8_REGS);
+    FA2_RF_ASM(RF128, CL_ORDER, FA2_F8_PRO, , );
 
     // ---- the rare path between two bodies: first the O^T rescale left over from the previous update, then a new reference
     // (fa2_fwd1_bf16.hip: at that point O^T holds the products through the keys j - 2, the row sums through j - 1, and P(j-1)
@@ -369,30 +312,23 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
         if (have_pend) {
             asm volatile("; fa2-cold: deferred O rescale");
             mfma_acc_settle();
-            static_for<4 * DT>([&](auto R4) { f8_acc_scale4<4 * decltype(R4)::value>(pend); });
+            fwd_rescale_o<RF, CL, 0, 4 * DT>(pend);
             pend = 1.0f;
             have_pend = false;
         }
         if (need) {
             asm volatile("; fa2-cold: new softmax reference");
-            const float mx = half_max(f8_vget<ST_RM>()) * p.scale;
-            const bool grow = mx > m_run + kF8RescaleThr;        // also true from m_run = -inf
-            const bool any_grow = __any(grow);
-            const float m_new = any_grow ? fmaxf(m_run, mx) : m_run;
+            const float mx = half_max(vget<ST_RM>()) * p.scale;
             // O only needs scaling if some row already accumulated something at an older reference
-            const bool sc = any_grow && __any(m_run != -INFINITY && m_new != m_run);
-            const float alpha = m_new == -INFINITY ? 1.0f : __builtin_amdgcn_exp2f((m_run - m_new) * kLog2e);
+            FA2_FWD_NEW_REFERENCE(m_run, mx);
             m_run = m_new;
-            f8_vsetf<ST_MB>(m_new == -INFINITY ? 0.0f : m_new * kLog2e);      // a row with no visible key yet keeps p = 0
-            f8_vsetf<ST_TH>((m_new + kF8RescaleThr) * inv_scale);
-            f8_vsetf<ST>(f8_vget<ST>() * alpha);
-            f8_vsetf<ST + 1>(f8_vget<ST + 1>() * alpha);
+            fwd_write_reference<RF, CL, ST, ST_MB, ST_TH>(m_new, alpha, inv_scale);
             pend = sc ? alpha : 1.0f;
             have_pend = sc;
             float mm = m_new;
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) mm = fminf(mm, __shfl_xor(mm, o));
-            m_min6 = f8_uniform(mm) + kF8RescaleThr;
+            m_min6 = f8_uniform(mm) + kFwdRescaleThr;
         }
     };
 
@@ -433,8 +369,7 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
     int nfull = N / KV;
     if (CAUSAL) nfull = min(nfull, (q0 + 1) / KV);
     nfull = min(nfull, J / NH) & ~3;                       // whole rounds of the ring of four
-    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+    using I0 = Int<0>; using I1 = Int<1>; using I2 = Int<2>; using I3 = Int<3>;
     int t = 0;
     for (; t < nfull; t += 4) {
         // one round of the ring = 512 keys = 8 entries of kn: can any of their scores pass any row's threshold?
@@ -450,36 +385,20 @@ __global__ void __launch_bounds__(64 * kF8Waves, 1) __attribute__((amdgpu_num_vg
             run_tile(I0{}, I0{}, t); run_tile(I1{}, I0{}, t + 1); run_tile(I2{}, I0{}, t + 2); run_tile(I3{}, I0{}, t + 3);
         }
     }
-    for (; t < ntl; t += 4) {
-        run_tile(I0{}, I1{}, t);
-        if (t + 1 >= ntl) break;
-        run_tile(I1{}, I1{}, t + 1);
-        if (t + 2 >= ntl) break;
-        run_tile(I2{}, I1{}, t + 2);
-        if (t + 3 >= ntl) break;
-        run_tile(I3{}, I1{}, t + 3);
-    }
+    FA2_FWD_TAIL_TILES(run_tile, t, ntl);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");       // the last bodies' look-ahead DMA and reads
 
-    // ---- epilogue (as fa2_fwd1_bf16.hip: a lane holds 4 consecutive columns of its row per register quad, its partner lane
-    // (+32) the next 4; one v_permlane32_swap per packed dword pairs them up so that every lane stores 16 contiguous bytes)
+    // ---- epilogue
     mfma_acc_settle();
-    const float l_tot = half_sum(f8_vget<ST>() + f8_vget<ST + 1>());
+    const float l_tot = half_sum(vget<ST>() + vget<ST + 1>());
     const size_t qoff = (size_t)head * N + qrow;
     const float inv = (l_tot > 0.0f ? 1.0f / l_tot : 0.0f) * pend * p.o_scale;      // pend: an O rescale still pending from the last update; o_scale: V's descale
     static_for<2 * DT>([&](auto G) {
         constexpr int dt = decltype(G)::value / 2, gp = decltype(G)::value % 2;
         constexpr int R = dt * 16 + 8 * gp;
         f32x4 v, w;
-        v[0] = f8_acc_read<R>() * inv; v[1] = f8_acc_read<R + 1>() * inv; v[2] = f8_acc_read<R + 2>() * inv; v[3] = f8_acc_read<R + 3>() * inv;
-        w[0] = f8_acc_read<R + 4>() * inv; w[1] = f8_acc_read<R + 5>() * inv; w[2] = f8_acc_read<R + 6>() * inv; w[3] = f8_acc_read<R + 7>() * inv;
-        bf16x4 x, y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { x[e] = (__bf16)v[e]; y[e] = (__bf16)w[e]; }
-        const u32x2 xu = __builtin_bit_cast(u32x2, x), yu = __builtin_bit_cast(u32x2, y);
-        const auto s0 = __builtin_amdgcn_permlane32_swap(xu[0], yu[0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(xu[1], yu[1], false, false);
-        const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+        fwd_read_o8<R>(inv, v, w);
+        const u32x4 o = fwd_pack_o8_bf16(v, w);
         if (qrow < N) *reinterpret_cast<u32x4*>((char*)p.O + qoff * (kF8D * 2) + 2 * (32 * dt + 16 * gp + 8 * h)) = o;
     });
     if (qrow < N && h == 0) p.L[qoff] = m_run + __builtin_logf(l_tot);
