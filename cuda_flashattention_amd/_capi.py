@@ -44,6 +44,11 @@ SIGNATURES = {
     "fa2_backward_gqa_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "fa2_backward_gqa": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp, _i]),
     "fa2_backward_gqa_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p)]),
+    "fa2_varlen_plan_bytes": (_sz, [_i, _i]),
+    "fa2_varlen_plan_build": (_i, [_vp, _i, _vp, _sz]),
+    "fa2_forward_varlen": (_i, [_vp] * 5 + [_i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
+    "fa2_backward_varlen_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "fa2_backward_varlen": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "fa2_backward_fused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fa2_backward_fused": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "fa2_backward_block": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),

@@ -15,6 +15,9 @@
 //                                them, K/V fragments resident in registers), streams Q/dO
 //                                tiles, keeps dK^T and dV^T in accumulators
 //
+// Kernels 1 and 2 also exist as table-driven instances for packed variable-length batches (fa2_backward_varlen: one launch
+// over every sequence of a ragged batch, bwd_varlen_view below); the bodies and the arithmetic are the same.
+//
 // No atomics, no memset, bitwise reproducible.  The price is that S and dP are formed in both
 // kernels (7 block products instead of 5); on MI355X the alternative -- fp32 atomics for dQ --
 // is bounded by the chip-wide float-atomic rate (~1.3 TB/s): dQ alone would be
@@ -134,8 +137,9 @@ __device__ __forceinline__ void dq_prologue(const uint32_t (&roff)[D / 16], cons
 // a tile's second block run in the NEXT body, against the K image that is still in the ring of three LDS buffers.
 // One barrier per tile, inside the body (vmcnt(0) + s_barrier in front of its first read of the next tile): every wave
 // past it has also finished with the tile before the previous one, so its buffer may take the next DMA.
+// `head` and `rb` (the row block) are the caller's: the dense kernel takes them from blockIdx.x, the packed one from its table.
 template <int D, bool CAUSAL>
-__global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) fa2_bwd_dq_kernel(BwdArgs p)
+__device__ __forceinline__ void bwd_dq_impl(const BwdArgs& p, const int head, const int rb)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ROWB = D * 2;
@@ -159,11 +163,6 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
     const int qi = lane & 31;
     const int h = lane >> 5;
     const int Nq = p.Nq, N = p.Nk;           // N: keys of the block (every key-side bound below)
-
-    const int nrb = (Nq + kBwdRows - 1) / kBwdRows;
-    int head, rb;
-    map_block(blockIdx.x, p.BH, nrb, head, rb);
-    if (CAUSAL) rb = nrb - 1 - rb;
 
     const size_t slab = (size_t)head * p.q_hs * ROWB;          // Q, dO, dQ
     const size_t kslab = (size_t)(head / p.kv_group) * p.k_hs * ROWB;      // K, V: kv_group query heads share a K/V head
@@ -297,6 +296,48 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
     });
 }
 
+template <int D, bool CAUSAL>
+__global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) fa2_bwd_dq_kernel(BwdArgs p)
+{
+    const int nrb = (p.Nq + kBwdRows - 1) / kBwdRows;
+    int head, rb;
+    map_block(blockIdx.x, p.BH, nrb, head, rb);
+    if (CAUSAL) rb = nrb - 1 - rb;          // heaviest row blocks first
+    bwd_dq_impl<D, CAUSAL>(p, head, rb);
+}
+
+// Packed variable-length batches (fa2_backward_varlen; the forward's scheme, fa2_fwd1_bf16.hip): the grid is (items of the
+// plan) x heads, a workgroup reads its item from the device table (wave-uniform: uniform_item) and runs on a view of that ONE
+// sequence -- tensor pointers at its first row, Nq / Nk its lengths, so every buffer resource ends where the sequence ends;
+// heads T rows apart; q_row0 = its first row, which indexes the dense [H_q][T] D / RC planes exactly as a row range of a
+// larger tensor does for fa2_backward_block.  O is not read by these two kernels.
+template <int D>
+__device__ __forceinline__ BwdArgs bwd_varlen_view(const BwdArgs& a, const VarlenItem& it)
+{
+    constexpr size_t ROWB = D * 2;
+    BwdArgs p = a;
+    p.Q = (const char*)a.Q + (size_t)it.q_row0 * ROWB;
+    p.dO = (const char*)a.dO + (size_t)it.q_row0 * ROWB;
+    p.dQ = (char*)a.dQ + (size_t)it.q_row0 * ROWB;
+    p.L = a.L + it.q_row0;
+    p.K = (const char*)a.K + (size_t)it.k_row0 * ROWB;
+    p.V = (const char*)a.V + (size_t)it.k_row0 * ROWB;
+    p.dK = (char*)a.dK + (size_t)it.k_row0 * ROWB;
+    p.dV = (char*)a.dV + (size_t)it.k_row0 * ROWB;
+    p.Nq = it.len_q; p.Nk = it.len_k; p.q_row0 = it.q_row0;
+    return p;
+}
+
+// row-block items: a sequence's blocks descend, the heaviest first under the causal mask
+template <int D, bool CAUSAL>
+__global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) fa2_bwd_dq_varlen_kernel(VarlenBwdArgs v)
+{
+    int head, idx;
+    map_block(blockIdx.x, v.a.BH, v.n_row_items, head, idx);
+    const VarlenItem it = uniform_item(v.row_items, idx);
+    bwd_dq_impl<D, CAUSAL>(bwd_varlen_view<D>(v.a, it), head, it.block);
+}
+
 // --------------------------------------------------------------------------- kernel 2: dK, dV
 // Workgroup = 4 waves = 256 keys of one head, ONE wave per SIMD so that each wave may use the whole 512-entry
 // register file: a wave owns 64 keys (two 32-key blocks) and keeps dK^T and dV^T of those keys -- 2 x 2 x (D/32)
@@ -350,8 +391,9 @@ __device__ __forceinline__ void dkdv_prologue(const uint32_t (&roff)[D / 16], co
     else asm volatile(FA2_DKDV_PRO_D64_M0 : : FA2_DKDV_OPS_64, [rc] "v"(rc) : FA2_DKDV_CLOBBERS);
 }
 
+// `kvhead` and `cb` (the key block) are the caller's, as in bwd_dq_impl.
 template <int D, bool CAUSAL>
-__global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) fa2_bwd_dkdv_kernel(BwdArgs p)
+__device__ __forceinline__ void bwd_dkdv_impl(const BwdArgs& p, const int kvhead, const int cb)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ROWB = D * 2;
@@ -374,10 +416,6 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
     const int ki = lane & 31;
     const int h = lane >> 5;
     const int N = p.Nk, Nq = p.Nq;          // N: keys of the block
-
-    const int ncb = (N + kDkKeys - 1) / kDkKeys;
-    int kvhead, cb;
-    map_block(blockIdx.x, p.BH / p.kv_group, ncb, kvhead, cb);     // causal: key block 0 is the heaviest, already first
 
     const size_t slab = (size_t)kvhead * p.k_hs * ROWB;        // K, V, dK, dV
     const char* Kh = (const char*)p.K + slab;
@@ -532,6 +570,25 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
     });
 }
 
+template <int D, bool CAUSAL>
+__global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) fa2_bwd_dkdv_kernel(BwdArgs p)
+{
+    const int ncb = (p.Nk + kDkKeys - 1) / kDkKeys;
+    int kvhead, cb;
+    map_block(blockIdx.x, p.BH / p.kv_group, ncb, kvhead, cb);     // causal: key block 0 is the heaviest, already first
+    bwd_dkdv_impl<D, CAUSAL>(p, kvhead, cb);
+}
+
+// key-block items of a packed batch: a sequence's blocks ascend (key block 0 is the heaviest under the causal mask)
+template <int D, bool CAUSAL>
+__global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) fa2_bwd_dkdv_varlen_kernel(VarlenBwdArgs v)
+{
+    int kvhead, idx;
+    map_block(blockIdx.x, v.a.BH / v.a.kv_group, v.n_key_items, kvhead, idx);
+    const VarlenItem it = uniform_item(v.key_items, idx);
+    bwd_dkdv_impl<D, CAUSAL>(bwd_varlen_view<D>(v.a, it), kvhead, it.block);
+}
+
 // --------------------------------------------------------------------------- launch
 template <int D, bool CAUSAL>
 static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream)
@@ -557,6 +614,34 @@ static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream)
         e = launch_lds<fa2_bwd_dkdv_kernel<D, CAUSAL>>(dim3((unsigned)(ncb * (a.BH / a.kv_group))), dim3(256), lds_dk, stream, a);
     }
     return e;
+}
+
+// Packed batches: D over the whole [H_q][T] tensors in one dense launch (no table), then the two table-driven kernels.
+template <int D, bool CAUSAL>
+static hipError_t launch_bwd_varlen_one(const VarlenBwdArgs& v, hipStream_t stream)
+{
+    const BwdArgs& a = v.a;
+    const size_t rows = (size_t)a.BH * a.q_hs;
+    hipLaunchKernelGGL((fa2_bwd_delta_kernel<D>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, stream,
+                       (const __bf16*)a.dO, (const __bf16*)a.O, a.L, a.D, a.RC, rows, a.q_hs, a.q_hs, 0, rows, 1.0f / a.scale);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    constexpr int lds_dq = 3 * 2 * kDqKV * D * 2;
+    constexpr int lds_dk = kDkKeys * D * 2 + 2 * (2 * 2 * kDkQ * D * 2 + 512);
+    e = launch_lds<fa2_bwd_dq_varlen_kernel<D, CAUSAL>>(dim3((unsigned)(v.n_row_items * a.BH)), dim3(256), lds_dq, stream, v);
+    if (e != hipSuccess) return e;
+    return launch_lds<fa2_bwd_dkdv_varlen_kernel<D, CAUSAL>>(dim3((unsigned)(v.n_key_items * (a.BH / a.kv_group))), dim3(256), lds_dk,
+                                                            stream, v);
+}
+
+hipError_t launch_bwd_varlen_bf16(const VarlenBwdArgs& v, hipStream_t stream)
+{
+    const BwdArgs& a = v.a;
+    if (a.kv_group < 1 || a.BH % a.kv_group != 0 || v.n_row_items < 1 || v.n_key_items < 1 || !v.row_items || !v.key_items)
+        return hipErrorInvalidValue;
+    if (a.d == 128) return a.causal ? launch_bwd_varlen_one<128, true>(v, stream) : launch_bwd_varlen_one<128, false>(v, stream);
+    if (a.d == 64) return a.causal ? launch_bwd_varlen_one<64, true>(v, stream) : launch_bwd_varlen_one<64, false>(v, stream);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream)

@@ -9,7 +9,10 @@
 #include "fa2_launch.h"
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <mutex>
+#include <numeric>
+#include <vector>
 
 namespace {
 
@@ -74,6 +77,31 @@ struct ScratchCache {
 } g_scratch;
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The plan of a packed variable-length batch (fa2_varlen_plan_build): this header, the row-block items, the key-block items.
+struct VarlenHeader { int magic, version, n_seqs, total, n_row_items, n_key_items, max_len, reserved; };
+constexpr int kVarlenMagic = 0x4c564146;      // "FAVL"
+constexpr int kVarlenVersion = 1;
+constexpr int kVarlenBlock = 256;             // rows per row-block item = keys per key-block item (kF1Rows, kBwdRows, kDkKeys)
+constexpr int kVarlenMaxRows = 0x7fffffff / (128 * 4);      // check_common's plane rule at the widest row (head_dim 128, 4 bytes)
+inline size_t varlen_bytes(long long n_row, long long n_key)
+{
+    return sizeof(VarlenHeader) + (size_t)(n_row + n_key) * sizeof(fa2::VarlenItem);
+}
+
+// What a launch believes of the HOST copy of a plan (nothing of the device copy is read on the host)
+inline int varlen_check(const void* plan_host, const void* plan_dev, size_t plan_bytes, int total_rows, int heads, VarlenHeader* out)
+{
+    if (plan_bytes < sizeof(VarlenHeader) || ((uintptr_t)plan_dev & 3)) return FA2_ERR_INVALID_SHAPE;
+    VarlenHeader h;
+    memcpy(&h, plan_host, sizeof h);
+    if (h.magic != kVarlenMagic || h.version != kVarlenVersion) return FA2_ERR_INVALID_SHAPE;
+    if (h.total != total_rows || h.n_row_items < 1 || h.n_key_items < 1) return FA2_ERR_INVALID_SHAPE;
+    if (plan_bytes < varlen_bytes(h.n_row_items, h.n_key_items)) return FA2_ERR_INVALID_SHAPE;
+    if ((long long)std::max(h.n_row_items, h.n_key_items) * heads > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;      // the grid
+    *out = h;
+    return FA2_OK;
+}
 
 }  // namespace
 
@@ -156,6 +184,70 @@ int fa2_forward_gqa(const void* Q, const void* K, const void* V, void* O, float*
     st = check_dim(head_dim, dtype);
     if (st) return st;
     return forward_bf16(Q, K, V, O, L, B, H_q, H_q / H_kv, seq_len, head_dim, softmax_scale, causal, stream);
+}
+
+// ---- packed variable-length batches ---------------------------------------------------------------------------------------
+size_t fa2_varlen_plan_bytes(int n_seqs, int total_rows)
+{
+    if (n_seqs < 1 || total_rows < 1) return 0;
+    // a sequence of len rows has ceil(len / 256) <= len / 256 + 1 blocks, and only non-empty sequences have any
+    const long long most = (long long)total_rows / kVarlenBlock + std::min(n_seqs, total_rows);
+    return varlen_bytes(most, most);
+}
+
+int fa2_varlen_plan_build(const int* cu_seqlens_host, int n_seqs, void* plan_host, size_t plan_bytes)
+{
+    if (!cu_seqlens_host || !plan_host) return FA2_ERR_NULL_POINTER;
+    if (n_seqs < 1 || cu_seqlens_host[0] != 0) return FA2_ERR_INVALID_SHAPE;
+    for (int i = 0; i < n_seqs; ++i)
+        if (cu_seqlens_host[i + 1] < cu_seqlens_host[i]) return FA2_ERR_INVALID_SHAPE;
+    const int total = cu_seqlens_host[n_seqs];
+    if (total < 1 || total > kVarlenMaxRows) return FA2_ERR_INVALID_SHAPE;
+    // sequences by descending length, ties by index; empty ones have no work
+    std::vector<int> order(n_seqs);
+    std::iota(order.begin(), order.end(), 0);
+    const auto len = [&](int i) { return cu_seqlens_host[i + 1] - cu_seqlens_host[i]; };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len(a) > len(b); });
+    long long n_items = 0;
+    for (int i = 0; i < n_seqs; ++i) n_items += (len(i) + kVarlenBlock - 1) / kVarlenBlock;
+    if (plan_bytes < varlen_bytes(n_items, n_items)) return FA2_ERR_WORKSPACE;
+    const VarlenHeader h{kVarlenMagic, kVarlenVersion, n_seqs, total, (int)n_items, (int)n_items, len(order[0]), 0};
+    memcpy(plan_host, &h, sizeof h);
+    // (written through memcpy: the caller's buffer has no alignment beyond a byte's)
+    char* out = (char*)plan_host + sizeof h;
+    const auto put = [&](int seq, int block) {
+        const int r0 = cu_seqlens_host[seq];
+        const fa2::VarlenItem it{r0, r0, len(seq), len(seq), block};
+        memcpy(out, &it, sizeof it);
+        out += sizeof it;
+    };
+    for (int seq : order)      // row blocks: descending within a sequence (the heaviest first under a causal mask)
+        for (int b = (len(seq) + kVarlenBlock - 1) / kVarlenBlock - 1; b >= 0; --b) put(seq, b);
+    for (int seq : order)      // key blocks: ascending (key block 0 is the heaviest)
+        for (int b = 0; b < (len(seq) + kVarlenBlock - 1) / kVarlenBlock; ++b) put(seq, b);
+    return FA2_OK;
+}
+
+int fa2_forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
+                       int H_q, int H_kv, int total_rows, int head_dim, float softmax_scale, int dtype, int causal,
+                       const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
+{
+    if (!Q || !K || !V || !O || !L || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
+    int st = check_common(1, H_q, total_rows, head_dim, softmax_scale);
+    if (st) return st;
+    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
+    VarlenHeader h;
+    if ((st = varlen_check(plan_host, plan_dev, plan_bytes, total_rows, H_q, &h))) return st;
+    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;      // whatever the dtype: head_dim comes first
+    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    fa2::VarlenFwdArgs v{};
+    fa2::FwdArgs& a = v.a;
+    a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L;
+    a.BH = H_q; a.d = head_dim; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.finalize = 1;
+    a.q_hs = a.k_hs = total_rows; a.kv_group = H_q / H_kv;
+    v.items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
+    v.n_items = h.n_row_items;
+    return hip_status(fa2::launch_fwd1_varlen_bf16(v, (hipStream_t)stream));
 }
 
 size_t fa2_forward_fp8_workspace_bytes(int B, int H, int seq_len, int head_dim)
@@ -452,6 +544,41 @@ int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, i
                               nullptr, 0);
     if (reason) *reason = r.status ? "" : r.why;
     return r.status ? r.status : r.path == Path::single ? 1 : 2;
+}
+
+// D [H_q][T] and the two row-constant planes, laid out as the front of every other backward workspace
+size_t fa2_backward_varlen_workspace_bytes(int H_q, int H_kv, int total_rows, int head_dim, int dtype)
+{
+    if (H_q <= 0 || H_kv <= 0 || H_q % H_kv != 0 || total_rows <= 0) return 0;
+    return bwd_ws(nullptr, 1, H_q, total_rows, head_dim, dtype).base_bytes;
+}
+
+int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                        void* dQ, void* dK, void* dV,
+                        int H_q, int H_kv, int total_rows, int head_dim, float softmax_scale, int dtype, int causal,
+                        const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                        void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!Q || !K || !V || !O || !L || !dO || !dQ || !dK || !dV || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
+    int st = check_common(1, H_q, total_rows, head_dim, softmax_scale);
+    if (st) return st;
+    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
+    if ((st = check_bwd_planes(1, H_q, total_rows))) return st;
+    VarlenHeader h;
+    if ((st = varlen_check(plan_host, plan_dev, plan_bytes, total_rows, H_q, &h))) return st;
+    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
+    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    const BwdWs ws = bwd_ws(workspace, 1, H_q, total_rows, head_dim, dtype);
+    if (!workspace || workspace_bytes < ws.base_bytes) return FA2_ERR_WORKSPACE;
+    fa2::VarlenBwdArgs v{};
+    fa2::BwdArgs& a = v.a;
+    a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.L = L; a.dQ = dQ; a.dK = dK; a.dV = dV;
+    a.D = ws.D; a.RC = ws.RC; a.BH = H_q; a.Nq = a.Nk = total_rows; a.d = head_dim;
+    a.q_hs = a.k_hs = total_rows; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.phases = 7; a.kv_group = H_q / H_kv;
+    const auto* items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
+    v.row_items = items; v.n_row_items = h.n_row_items;
+    v.key_items = items + h.n_row_items; v.n_key_items = h.n_key_items;
+    return hip_status(fa2::launch_bwd_varlen_bf16(v, (hipStream_t)stream));
 }
 
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,

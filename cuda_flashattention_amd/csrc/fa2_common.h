@@ -106,4 +106,21 @@ __device__ __forceinline__ void map_block(int bid, int n_heads, int nrb, int& he
     }
 }
 
+// One entry of a table that every lane of the workgroup reads at the same index (the packed launches' work items), word by
+// word through readfirstlane: the values are wave-uniform and the compiler knows it -- they end up in buffer resources and
+// in branches around workgroup barriers.
+template <typename Item>
+__device__ __forceinline__ Item uniform_item(const Item* items, int i)
+{
+    static_assert(sizeof(Item) % sizeof(int) == 0 && alignof(Item) == alignof(int), "a table of ints");
+    constexpr int W = sizeof(Item) / sizeof(int);
+    const int* src = reinterpret_cast<const int*>(items + i);
+    int w[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) w[k] = __builtin_amdgcn_readfirstlane(src[k]);
+    Item it;
+    __builtin_memcpy(&it, w, sizeof(Item));
+    return it;
+}
+
 }  // namespace fa2

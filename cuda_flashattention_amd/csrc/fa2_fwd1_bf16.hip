@@ -33,6 +33,8 @@
 // maxima in every body (`safe`), as before.  (What stays outside the contract: |V| beyond ~2^47, where P < 2^80 against a
 // lagging reference can take P V out of fp32 although O itself would fit.)
 // Tail, diagonal and drain bodies keep their maxima either way.
+// Packed variable-length batches (fa2_forward_varlen) run the same row-block code from a table of (sequence, row block) items:
+// fwd1_varlen_impl below.
 // Measured same-box: (4,16,4096,64) 945 -> ~990 TFLOP/s, (4,16,8192,128) 1.692 -> ~1.65 ms.
 #include <type_traits>
 
@@ -108,8 +110,10 @@ template <int D, int QBS> struct F1Map;
 FA2_F1_MAP(D128Q2, 128, 2) FA2_F1_MAP(D64Q2, 64, 2) FA2_F1_MAP(D64Q1, 64, 1)
 #undef FA2_F1_MAP
 
+// `head` and `wi` (the workgroup's index among its head's workgroups) are the caller's: the dense kernels take them from
+// blockIdx.x through map_block, the packed ones from their table (fwd1_varlen_impl below), with `p` the view of one sequence.
 template <int D, int QBS, bool CAUSAL, bool STATE>
-__device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
+__device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p, const int head, const int wi)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ROWB = D * 2;
@@ -144,9 +148,6 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
     // together on one XCD (K / V through its L2), as before.
     constexpr bool PAIRED = CAUSAL && !STATE;
     const int nrb = (p.Nq + kF1Rows - 1) / kF1Rows;
-    const int nwg = PAIRED ? (nrb + 1) / 2 : nrb;          // workgroups per head
-    int head, wi;
-    map_block(blockIdx.x, p.BH, nwg, head, wi);
 #pragma nounroll
     for (int half = 0; half < (PAIRED ? 2 : 1); ++half) {
     int rb = CAUSAL ? nrb - 1 - wi : wi;              // (not paired) heaviest row blocks first
@@ -461,17 +462,64 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p)
     }      // the pair's second row block
 }
 
+// dense launches: (head, workgroup of the head) from blockIdx.x, XCD-aware (map_block)
+template <int D, int QBS, bool CAUSAL, bool STATE>
+__device__ __forceinline__ void fwd1_dense_impl(const FwdArgs& p)
+{
+    const int nrb = (p.Nq + kF1Rows - 1) / kF1Rows;
+    const int nwg = (CAUSAL && !STATE) ? (nrb + 1) / 2 : nrb;          // workgroups per head (plain causal launches: pairs)
+    int head, wi;
+    map_block(blockIdx.x, p.BH, nwg, head, wi);
+    fa2_fwd1_impl<D, QBS, CAUSAL, STATE>(p, head, wi);
+}
+
+// Packed variable-length launches (fa2_forward_varlen): the grid is (row-block items of the plan) x heads, a workgroup reads
+// its item -- {first Q row, first K row, lengths, row block} of ONE sequence -- from the device table and runs the row block
+// on a view of that sequence: pointers at its first row, Nq / Nk its lengths (so the K / V buffer resources end where the
+// sequence ends: a DMA row past it reads zeros, never the next sequence's keys), heads T rows apart (v.a.q_hs = k_hs = T).
+// One row block per workgroup, causal or not (the STATE schedule; the plan lists a sequence's row blocks heaviest first).
+// Everything taken from the table is wave-uniform (uniform_item): the resources, J / nfull / nfull_wg and the branches around
+// the tile barriers all hang on it.  A block's arithmetic is that of the dense kernels on the sequence alone.
+template <int D, int QBS, bool CAUSAL>
+__device__ __forceinline__ void fwd1_varlen_impl(const VarlenFwdArgs& v)
+{
+    constexpr size_t ROWB = D * 2;
+    int head, idx;
+    map_block(blockIdx.x, v.a.BH, v.n_items, head, idx);
+    const VarlenItem it = uniform_item(v.items, idx);
+    FwdArgs p = v.a;
+    p.Q = (const char*)p.Q + (size_t)it.q_row0 * ROWB;
+    p.O = (char*)p.O + (size_t)it.q_row0 * ROWB;
+    p.L += it.q_row0;
+    p.K = (const char*)p.K + (size_t)it.k_row0 * ROWB;
+    p.V = (const char*)p.V + (size_t)it.k_row0 * ROWB;
+    p.Nq = it.len_q; p.Nk = it.len_k;
+    p.resume = 0; p.finalize = 1;          // (known here: the state branches of the STATE instance fold away)
+    const int nrb = (it.len_q + kF1Rows - 1) / kF1Rows;
+    fa2_fwd1_impl<D, QBS, CAUSAL, true>(p, head, CAUSAL ? nrb - 1 - it.block : it.block);
+}
+
 // the two shapes as kernels: the register budgets differ (one wave per SIMD: hipcc keeps to v0..v63 of 512 registers; two waves
 // per SIMD: to v0..v39 of 128 + 128)
 template <int D, bool CAUSAL, bool STATE>
 __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) fa2_fwd1_bf16_kernel(FwdArgs p)
 {
-    fa2_fwd1_impl<D, 2, CAUSAL, STATE>(p);
+    fwd1_dense_impl<D, 2, CAUSAL, STATE>(p);
 }
 template <int D, bool CAUSAL, bool STATE>
 __global__ void __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(40))) fa2_fwd1x2_bf16_kernel(FwdArgs p)
 {
-    fa2_fwd1_impl<D, 1, CAUSAL, STATE>(p);
+    fwd1_dense_impl<D, 1, CAUSAL, STATE>(p);
+}
+template <int D, bool CAUSAL>
+__global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) fa2_fwd1_varlen_kernel(VarlenFwdArgs v)
+{
+    fwd1_varlen_impl<D, 2, CAUSAL>(v);
+}
+template <int D, bool CAUSAL>
+__global__ void __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(40))) fa2_fwd1x2_varlen_kernel(VarlenFwdArgs v)
+{
+    fwd1_varlen_impl<D, 1, CAUSAL>(v);
 }
 
 #ifndef FA2_FWD64_QBS
@@ -501,6 +549,24 @@ hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream)
         if (state) return a.causal ? launch_one1<64, true, true>(a, stream) : launch_one1<64, false, true>(a, stream);
         return a.causal ? launch_one1<64, true, false>(a, stream) : launch_one1<64, false, false>(a, stream);
     }
+    return hipErrorInvalidValue;
+}
+
+template <int D, bool CAUSAL>
+static hipError_t launch_varlen1(const VarlenFwdArgs& v, hipStream_t stream)
+{
+    constexpr int lds = 2 * kF1Bufs * 16384 + 16;
+    const dim3 grid((unsigned)(v.n_items * v.a.BH));
+    if constexpr (D == 64 && FA2_FWD64_QBS == 1)
+        return launch_lds<fa2_fwd1x2_varlen_kernel<D, CAUSAL>>(grid, dim3(512), lds, stream, v);
+    else
+        return launch_lds<fa2_fwd1_varlen_kernel<D, CAUSAL>>(grid, dim3(256), lds, stream, v);
+}
+hipError_t launch_fwd1_varlen_bf16(const VarlenFwdArgs& v, hipStream_t stream)
+{
+    if (v.a.kv_group < 1 || v.a.BH % v.a.kv_group != 0 || v.n_items < 1 || !v.items) return hipErrorInvalidValue;
+    if (v.a.d == 128) return v.a.causal ? launch_varlen1<128, true>(v, stream) : launch_varlen1<128, false>(v, stream);
+    if (v.a.d == 64) return v.a.causal ? launch_varlen1<64, true>(v, stream) : launch_varlen1<64, false>(v, stream);
     return hipErrorInvalidValue;
 }
 

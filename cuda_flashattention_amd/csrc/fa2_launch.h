@@ -31,6 +31,19 @@ struct FwdArgs {
 };
 
 hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream);     // generated main loop: one wave per SIMD (d = 128), two (d = 64)
+
+// Packed variable-length batches (fa2_forward_varlen / fa2_backward_varlen): tensors are head slabs [H][T][d] in which sequence
+// i owns rows [cu_seqlens[i], cu_seqlens[i + 1]); one launch covers every sequence.  A workgroup's unit of work is one item
+// of a table the host built (fa2_varlen_plan_build) and the caller uploaded: a 256-row block of one sequence's queries (forward,
+// dQ kernel) or a 256-key block of its keys (dK/dV kernel).
+struct VarlenItem {
+    int q_row0, k_row0;   // the sequence's first row in Q / O / dO / dQ / L and in K / V / dK / dV
+    int len_q, len_k;     // its lengths on the two sides (equal in this version)
+    int block;            // which 256-row (256-key) block of the sequence
+};
+// a: the whole packed problem -- BH = H_q, q_hs = k_hs = T, pointers at row 0 of head 0; Nq, Nk, resume, finalize are per item
+struct VarlenFwdArgs { FwdArgs a; const VarlenItem* items; int n_items; };      // items: DEVICE memory, row-block items
+hipError_t launch_fwd1_varlen_bf16(const VarlenFwdArgs& v, hipStream_t stream);
 // acc (fp32) = (init) or += src (bf16): `rows` runs of `cols` elements, `pitch` elements apart in both.
 hipError_t launch_accumulate_bf16(float* acc, const void* src, size_t rows, size_t cols, size_t pitch, int init, hipStream_t stream);
 // Ring epilogue: O = bf16(Oacc / l), L = m + ln l for `rows` consecutive rows (l arrives in L).
@@ -71,6 +84,14 @@ struct BwdArgs {
 };
 
 hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream);
+// The two-kernel backward over a packed variable-length batch.  a: the whole packed problem -- BH = H_q, q_hs = k_hs = T, Nq = T for
+// the D kernel (one dense launch over H_q x T rows), q_row0 / Nq / Nk per item in the other two; D / RC dense [H_q][T] planes.
+struct VarlenBwdArgs {
+    BwdArgs a;
+    const VarlenItem* row_items; const VarlenItem* key_items;      // DEVICE memory
+    int n_row_items, n_key_items;
+};
+hipError_t launch_bwd_varlen_bf16(const VarlenBwdArgs& v, hipStream_t stream);
 // Single-kernel five-product backward (fa2_bwd_fused.hip): d = 128 or 64, a dense square problem or (d = 128, mode 1) an unmasked
 // rectangular block; causal with mode 1 only.  Which problems come here: the routing rule at fa2_backward (include/fa2_mi355x.h),
 // applied by fa2_capi.cpp alone (device check included).

@@ -8,6 +8,7 @@ through ctypes.  torch is plumbing here: allocation, streams, nothing numerical.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -219,6 +220,177 @@ def attention(Q, K, V, softmax_scale=None, causal=False):
     bf16 K and V may have fewer heads ([B, H_kv, N, d], H_kv dividing H: grouped-query attention); their gradients have their shape.
     A convenience for callers that live in torch autograd; tests and bench.py call the two halves directly."""
     return _Attention.apply(Q, K, V, softmax_scale, causal)
+
+
+class VarlenPlan:
+    """The work plan of a packed variable-length batch (fa2_varlen_plan_build): built on the host from cu_seqlens -- a list, a
+    numpy array or a CPU integer tensor of n_seqs + 1 non-decreasing offsets starting at 0 -- when the object is made (no GPU
+    needed), uploaded to a device the first time a call needs it there and kept for every later call: make one per batch
+    layout and reuse it for every layer and step (and make the first call before capturing a graph: the upload is a copy).
+    Sequence i owns rows [cu_seqlens[i], cu_seqlens[i+1]) of every head of the packed [H, T, d] tensors."""
+
+    _HEADER_INTS, _ITEM_INTS = 8, 5
+
+    def __init__(self, cu_seqlens):
+        if isinstance(cu_seqlens, torch.Tensor):
+            if cu_seqlens.is_cuda:
+                raise ValueError("cu_seqlens must be host data (a list, a numpy array or a CPU tensor): the plan is built on the host")
+            if cu_seqlens.is_floating_point() or cu_seqlens.is_complex() or cu_seqlens.dtype == torch.bool:
+                raise ValueError(f"cu_seqlens must hold integers, got {cu_seqlens.dtype}")
+            cu_seqlens = cu_seqlens.numpy()
+        cu = np.asarray(cu_seqlens)
+        if cu.ndim != 1 or cu.size < 2 or not np.issubdtype(cu.dtype, np.integer):
+            raise ValueError("cu_seqlens: expected n_seqs + 1 >= 2 integer offsets in one dimension")
+        if int(cu.max()) > 2 ** 31 - 1 or int(cu.min()) < 0:
+            raise ValueError("cu_seqlens: offsets must be non-negative and fit 32 bits")
+        self.cu_seqlens = np.ascontiguousarray(cu, dtype=np.int32)
+        self.cu_seqlens.setflags(write=False)
+        lib = _capi.lib()
+        n_seqs, total = self.cu_seqlens.size - 1, int(self.cu_seqlens[-1])
+        blob = np.zeros(max(lib.fa2_varlen_plan_bytes(n_seqs, total), 4 * self._HEADER_INTS), dtype=np.uint8)
+        st = lib.fa2_varlen_plan_build(self.cu_seqlens.ctypes.data, n_seqs, blob.ctypes.data, blob.size)
+        if st:
+            raise ValueError(f"cu_seqlens {self.cu_seqlens.tolist()[:8]}{'...' if n_seqs > 7 else ''}: fa2_varlen_plan_build status {st} "
+                             f"({lib.fa2_status_string(st).decode()}): offsets start at 0, never decrease and end at T >= 1")
+        head = blob[:4 * self._HEADER_INTS].view(np.int32)
+        self.n_seqs, self.total, n_row, n_key, self.max_len = int(head[2]), int(head[3]), int(head[4]), int(head[5]), int(head[6])
+        lo, mid = 4 * self._HEADER_INTS, 4 * (self._HEADER_INTS + self._ITEM_INTS * n_row)
+        self._blob = np.ascontiguousarray(blob[:mid + 4 * self._ITEM_INTS * n_key])      # what the launches validate and the devices hold
+        self._blob.setflags(write=False)
+        # rows of (q_row0, k_row0, len_q, len_k, block), in launch order
+        self.row_items = self._blob[lo:mid].view(np.int32).reshape(n_row, self._ITEM_INTS)
+        self.key_items = self._blob[mid:].view(np.int32).reshape(n_key, self._ITEM_INTS)
+        self._dev = {}
+
+    @property
+    def nbytes(self):
+        return self._blob.size
+
+    def host_ptr(self):
+        return self._blob.ctypes.data
+
+    def device(self, device):
+        """The plan's copy on `device` (uploaded once per device)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"the plan is uploaded to GPUs, not to {device}")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._dev:
+            self._dev[device] = torch.from_numpy(self._blob.copy()).to(device)
+        return self._dev[device]
+
+
+def _htd(x, name, dtype=torch.bfloat16):
+    """A packed tensor [H, T, d]: shape first (a 3-D tensor), then what the C ABI takes on trust -- device, contiguity, dtype."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if x.dim() != 3:
+        raise ValueError(f"{name}: expected a packed [H, T, d] tensor, got {tuple(x.shape)} (transpose a [T, H, d] tensor first)")
+    if not x.is_cuda:
+        raise ValueError(f"{name} must be a device tensor")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous [H][T][d] (got strides {tuple(x.stride())}; call .contiguous())")
+    if x.dtype != dtype:
+        raise ValueError(f"{name}: dtype {x.dtype}, expected {dtype} (packed variable-length attention is bf16 in this version)")
+    return tuple(x.shape)
+
+
+def _varlen_shapes(Q, K, V, plan):
+    """(H, H_kv, T, d) of a packed problem, every relation between Q, K, V and the plan checked."""
+    if not isinstance(plan, VarlenPlan):
+        raise ValueError("plan must be a VarlenPlan")
+    for n, t in (("Q", Q), ("K", K), ("V", V)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{n}: expected a packed [H, T, d] tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
+                             "(transpose a [T, H, d] tensor first)")
+    H, T, d = Q.shape
+    if T != plan.total:
+        raise ValueError(f"Q: {T} rows per head, the plan's cu_seqlens end at T = {plan.total}")
+    Hkv = K.shape[0]
+    if Hkv < 1 or H % Hkv != 0:
+        raise ValueError(f"K: {Hkv} key/value heads do not divide {H} query heads")
+    if tuple(K.shape) != (Hkv, T, d) or tuple(V.shape) != (Hkv, T, d):
+        raise ValueError(f"K {tuple(K.shape)} / V {tuple(V.shape)}: expected {(Hkv, T, d)} beside Q {tuple(Q.shape)}")
+    for n, t in (("Q", Q), ("K", K), ("V", V)):
+        _htd(t, n)
+        if t.device != Q.device:
+            raise ValueError(f"{n} is on {t.device}, expected {Q.device}")
+    return H, Hkv, T, d
+
+
+def _packed(x, name, ref, shape):
+    if _htd(x, name) != shape:
+        raise ValueError(f"{name}: shape {tuple(x.shape)} does not match {shape}")
+    if x.device != ref.device:
+        raise ValueError(f"{name} is on {x.device}, expected {ref.device}")
+    return x
+
+
+def flash_attention_2_varlen_forward(Q, K, V, plan, softmax_scale=None, causal=False, O=None, L=None, stream=None):
+    """O, L = FA2 forward over a packed variable-length batch (fa2_forward_varlen): Q [H, T, d], K and V [H_kv, T, d] (H_kv
+    dividing H), bf16, d = 64 | 128; sequence i owns rows plan.cu_seqlens[i] : plan.cu_seqlens[i+1] of every head and attends only
+    itself (causal: within itself).  L is fp32 [H, T].  A [T, H, d] tensor must be transposed (and made contiguous) first."""
+    H, Hkv, T, d = _varlen_shapes(Q, K, V, plan)
+    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    O = torch.empty_like(Q) if O is None else _packed(O, "O", Q, (H, T, d))
+    L = torch.empty(H, T, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, 1, H, T)
+    st = _capi.lib().fa2_forward_varlen(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), H, Hkv, T, d, scale,
+                                        FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(),
+                                        plan.nbytes, _stream_ptr(stream))
+    check(st, "fa2_forward_varlen")
+    return O, L
+
+
+def flash_attention_2_varlen_backward(Q, K, V, O, L, dO, plan, softmax_scale=None, causal=False,
+                                      dQ=None, dK=None, dV=None, workspace=None, stream=None):
+    """dQ, dK, dV = FA2 backward over a packed variable-length batch (fa2_backward_varlen; the two deterministic kernels): the
+    tensors of flash_attention_2_varlen_forward, dO like O, dK / dV like K / V.  workspace: a uint8 device tensor of
+    fa2_backward_varlen_workspace_bytes (allocated per call when omitted -- pass one for graph capture)."""
+    H, Hkv, T, d = _varlen_shapes(Q, K, V, plan)
+    for n, t in (("O", O), ("dO", dO)):
+        _packed(t, n, Q, (H, T, d))
+    _rows(L, "L", Q, 1, H, T)
+    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    dQ = torch.empty_like(Q) if dQ is None else _packed(dQ, "dQ", Q, (H, T, d))
+    dK = torch.empty_like(K) if dK is None else _packed(dK, "dK", Q, (Hkv, T, d))
+    dV = torch.empty_like(V) if dV is None else _packed(dV, "dV", Q, (Hkv, T, d))
+    lib = _capi.lib()
+    if workspace is None:
+        workspace = torch.empty(lib.fa2_backward_varlen_workspace_bytes(H, Hkv, T, d, FA2_DTYPE_BF16), dtype=torch.uint8, device=Q.device)
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
+        raise ValueError("workspace must be a contiguous device tensor on Q's device")
+    st = lib.fa2_backward_varlen(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
+                                 dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), H, Hkv, T, d, scale, FA2_DTYPE_BF16, 1 if causal else 0,
+                                 plan.host_ptr(), plan.device(Q.device).data_ptr(), plan.nbytes,
+                                 workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr(stream))
+    check(st, "fa2_backward_varlen")
+    return dQ, dK, dV
+
+
+class _AttentionVarlen(torch.autograd.Function):
+    """flash_attention_2_varlen_forward / _backward as one differentiable op (as _Attention)."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, plan, softmax_scale, causal):
+        Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
+        scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
+        O, L = flash_attention_2_varlen_forward(Q, K, V, plan, scale, causal=causal)
+        ctx.save_for_backward(Q, K, V, O, L)
+        ctx.plan, ctx.scale, ctx.causal = plan, scale, bool(causal)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, O, L = ctx.saved_tensors
+        dQ, dK, dV = flash_attention_2_varlen_backward(Q, K, V, O, L, dO.contiguous(), ctx.plan, ctx.scale, causal=ctx.causal)
+        return dQ, dK, dV, None, None, None
+
+
+def attention_varlen(Q, K, V, plan, softmax_scale=None, causal=False):
+    """attention() over a packed variable-length batch: Q [H, T, d], K and V [H_kv, T, d] bf16 device tensors (d = 64 | 128, H_kv
+    dividing H), plan a VarlenPlan of the batch's cu_seqlens; every sequence attends itself only.  With gradients."""
+    return _AttentionVarlen.apply(Q, K, V, plan, softmax_scale, causal)
 
 
 def read_clocks(stream=None):

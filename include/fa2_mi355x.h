@@ -208,6 +208,54 @@ int fa2_backward_gqa(const void* Q, const void* K, const void* V, const void* O,
 int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, int dtype, int causal,
                           const char** reason);
 
+/* ---- Packed variable-length attention ("varlen", cu_seqlens), bf16, head_dim 64 or 128, causal (within each sequence) or
+ * not, H_q % H_kv == 0 (multi-head, GQA and MQA).  A ragged batch -- documents of 37, 300 and 5000 tokens -- in ONE launch
+ * sequence, without padding and without a loop of per-document calls.  Self-attention: a sequence has the same length on the
+ * query and on the key side.
+ * LAYOUT: packed head slabs, as everywhere in this ABI.  With T = cu_seqlens[n_seqs], Q, O, dO, dQ are [H_q][T][d], K, V, dK, dV
+ * are [H_kv][T][d], L is [H_q][T] fp32; sequence i owns rows [cu_seqlens[i], cu_seqlens[i+1]) of every head.  A caller that
+ * holds [T][H][d] transposes first.  Sequences of length 0 are allowed and cost nothing.
+ * THE PLAN.  cu_seqlens is HOST data, like every other size here.  fa2_varlen_plan_build (pure host code, no device needed)
+ * validates it and writes a blob of at most fa2_varlen_plan_bytes(n_seqs, T) bytes into plan_host: a header (magic, version,
+ * n_seqs, T, the two item counts, the longest length, one reserved word: 8 ints) and two lists of items, each five ints
+ * {q_row0, k_row0, len_q, len_k, block} -- both sides are carried although they are equal today, so that different query and key
+ * lengths need no new format.  ROW-BLOCK items (256 query rows of one sequence) are the units of the forward and of the dQ
+ * kernel, KEY-BLOCK items (256 keys) those of the dK/dV kernel.  ORDER, deterministic and the same with or without the causal
+ * mask: sequences by descending length, ties by index; within a sequence row blocks descend and key blocks ascend (the heaviest
+ * first under a causal mask, indifferent without one); a sequence's blocks are adjacent, so its K / V stay in one XCD's L2.
+ * The caller copies the blob to the device ONCE per batch layout and reuses it for every layer and step.  The launch calls take
+ * both copies: the host copy for validation and grid sizes, the device copy (4-byte aligned) for the kernels to read; they
+ * must hold the same bytes.
+ * ROUTING.  Forward: the generated-body forward kernels of fa2_forward, one 256-row block per workgroup (the two-block pairing
+ * of the dense causal launch does not carry over), grid = row-block items x H_q.  Backward: ALWAYS the two kernels (D over all
+ * H_q x T rows in one dense launch, then dQ over row-block items x H_q and dK/dV over key-block items x H_kv, a dK/dV
+ * workgroup walking the G query heads of its group as in fa2_backward_gqa).  The single five-product kernel hands dQ sums
+ * through a persistent grid laid out for dense square heads; ragged units are a separate piece of work.  Workspace
+ * (fa2_backward_varlen_workspace_bytes): D and the two row-constant planes, nothing else.
+ * A block's arithmetic does not depend on where its sequence lives: sequence i of the packed forward is bit-identical to
+ * fa2_forward_gqa on that sequence alone as [1][H][len_i][d], and the packed backward to fa2_backward_gqa with phases 1, then 6.
+ * A sequence never reads another's rows: every buffer resource ends where the sequence ends.  DETERMINISTIC: no atomics, every
+ * sum in a fixed order.  Nothing synchronises and nothing is allocated: the launch calls may be captured in a graph.
+ * STATUS CODES, in this order: NULL pointers (the plan's included) -> FA2_ERR_NULL_POINTER; H_q, T, scale, H_kv not dividing
+ * H_q, total_rows different from the plan's T, a blob without the magic, plan_bytes smaller than the blob ->
+ * FA2_ERR_INVALID_SHAPE; head_dim -> FA2_ERR_UNSUPPORTED_HEAD_DIM; fp32 and fp8 -> FA2_ERR_UNSUPPORTED_DTYPE; workspace ->
+ * FA2_ERR_WORKSPACE.  fa2_varlen_plan_build: NULL -> FA2_ERR_NULL_POINTER; n_seqs < 1, cu_seqlens[0] != 0, a decreasing entry,
+ * T < 1 or T above 4194303 rows (the 2 GiB-per-plane rule of every call, at the widest row) -> FA2_ERR_INVALID_SHAPE; plan_bytes
+ * too small for this cu_seqlens -> FA2_ERR_WORKSPACE.  fa2_varlen_plan_bytes returns 0 for n_seqs < 1 or total_rows < 1.
+ * NOT COVERED in this version: different query and key lengths per sequence (the item format already carries them), the
+ * single-kernel backward on packed batches, fp32 and fp8, the ring, a paged KV cache. */
+size_t fa2_varlen_plan_bytes(int n_seqs, int total_rows);
+int fa2_varlen_plan_build(const int* cu_seqlens_host, int n_seqs, void* plan_host, size_t plan_bytes);
+int fa2_forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
+                       int H_q, int H_kv, int total_rows, int head_dim, float softmax_scale, int dtype, int causal,
+                       const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream);
+size_t fa2_backward_varlen_workspace_bytes(int H_q, int H_kv, int total_rows, int head_dim, int dtype);
+int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                        void* dQ, void* dK, void* dV,
+                        int H_q, int H_kv, int total_rows, int head_dim, float softmax_scale, int dtype, int causal,
+                        const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output
  * pass (FA2_ERR_UNSUPPORTED for shapes or devices it does not take, and in combination with bits 1 or 2).  7 = fa2_backward (which picks the implementation);
