@@ -4,3 +4,4 @@ is the thin host-side mirror used by tests and bench.py.  No CPU fallback exists
 from . import _capi  # noqa: F401
 from .ops import flash_attention_2_forward, flash_attention_2_backward, forward_step, attention  # noqa: F401
 from .ops import VarlenPlan, flash_attention_2_varlen_forward, flash_attention_2_varlen_backward, attention_varlen  # noqa: F401
+from .ops import flash_attention_2_qk_forward, flash_attention_2_qk_backward, attention_qk  # noqa: F401

@@ -49,6 +49,14 @@ SIGNATURES = {
     "fa2_forward_varlen": (_i, [_vp] * 5 + [_i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
     "fa2_backward_varlen_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "fa2_backward_varlen": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "fa2_forward_qk": (_i, [_vp] * 5 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    "fa2_backward_qk_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "fa2_backward_qk": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp, _i]),
+    "fa2_varlen_plan_bytes_qk": (_sz, [_i, _i, _i]),
+    "fa2_varlen_plan_build_qk": (_i, [_vp, _vp, _i, _vp, _sz]),
+    "fa2_forward_varlen_qk": (_i, [_vp] * 5 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
+    "fa2_backward_varlen_qk_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "fa2_backward_varlen_qk": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "fa2_backward_fused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fa2_backward_fused": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "fa2_backward_block": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),

@@ -42,6 +42,12 @@ namespace fa2 {
 // 16 lanes per row (16 bytes of dO and of O each per step), 4 rows per wave.  Besides D it
 // writes the two row constants kernel 2 preloads into its accumulators, already transformed:
 // RC[0][row] = -L/scale (so that exp2(c (S - L/scale)) = P) and RC[1][row] = -D.
+// A row that saw no key (rectangular problems: causal with more queries than keys, a packed sequence without keys) has
+// L = -inf, O = 0 and so D = 0; its first constant is kNoKeyRC, finite, as for the single kernel's rows past the end:
+// S' = -1e30, P = exp2(-huge) = 0, dS = 0, and no Inf reaches an accumulator.
+constexpr float kNoKeyRC = -1.0e30f;       // RC[0] of a row without a visible key
+constexpr float kNoKeyLq = 1.0e30f;        // and what the dQ kernel subtracts from its scores in place of L log2 e
+
 template <int D>
 __global__ void __launch_bounds__(256) fa2_bwd_delta_kernel(const __bf16* __restrict__ dO,
                                                             const __bf16* __restrict__ O,
@@ -69,7 +75,8 @@ __global__ void __launch_bounds__(256) fa2_bwd_delta_kernel(const __bf16* __rest
     for (int off = 8; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 16);
     if (r < rows && sub == 0) {
         Dv[prow] = acc;
-        RC[prow] = -L[row] * inv_scale;
+        const float l = L[row];
+        RC[prow] = l == -INFINITY ? kNoKeyRC : -l * inv_scale;
         RC[rc_plane + prow] = -acc;
     }
 }
@@ -197,7 +204,8 @@ __device__ __forceinline__ void bwd_dq_impl(const BwdArgs& p, const int head, co
                 *reinterpret_cast<const bf16x8*>(Gh + (size_t)qld * ROWB + 16 * (2 * sidx + h)));
         });
         static_for<16 * DT>([&](auto R) { awrite<kBwdRegFile, CL_ACC, A_DQ + qb * DT * 16 + decltype(R)::value>(0.0f); });
-        Lq[qb] = p.L[(size_t)head * p.q_hs + qld] * kLog2e;
+        const float l = p.L[(size_t)head * p.q_hs + qld];
+        Lq[qb] = l == -INFINITY ? kNoKeyLq : l * kLog2e;       // a row without a visible key: P = exp2(c2 s - 1e30) = 0, dQ = 0
         Dq[qb] = p.D[(size_t)head * p.q_hs + p.q_row0 + qld];
     });
     const float c2 = p.scale * kLog2e;
@@ -310,7 +318,8 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(64))) f
 // plan) x heads, a workgroup reads its item from the device table (wave-uniform: uniform_item) and runs on a view of that ONE
 // sequence -- tensor pointers at its first row, Nq / Nk its lengths, so every buffer resource ends where the sequence ends;
 // heads T rows apart; q_row0 = its first row, which indexes the dense [H_q][T] D / RC planes exactly as a row range of a
-// larger tensor does for fa2_backward_block.  O is not read by these two kernels.
+// larger tensor does for fa2_backward_block.  O is not read by these two kernels.  The two sides have their own first rows,
+// lengths and head strides (q_hs = T_q, k_hs = T_k); the causal mask is aligned to the sequence's last query and last key.
 template <int D>
 __device__ __forceinline__ BwdArgs bwd_varlen_view(const BwdArgs& a, const VarlenItem& it)
 {
@@ -325,6 +334,7 @@ __device__ __forceinline__ BwdArgs bwd_varlen_view(const BwdArgs& a, const Varle
     p.dK = (char*)a.dK + (size_t)it.k_row0 * ROWB;
     p.dV = (char*)a.dV + (size_t)it.k_row0 * ROWB;
     p.Nq = it.len_q; p.Nk = it.len_k; p.q_row0 = it.q_row0;
+    p.causal_shift = it.len_k - it.len_q;
     return p;
 }
 

@@ -79,7 +79,9 @@ struct ScratchCache {
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The plan of a packed variable-length batch (fa2_varlen_plan_build): this header, the row-block items, the key-block items.
-struct VarlenHeader { int magic, version, n_seqs, total, n_row_items, n_key_items, max_len, reserved; };
+// total / max_len: the query side's rows and longest sequence; total_k: 0 in a one-sided plan (one list for both sides), the key
+// side's rows (>= 1) in a two-sided one (fa2_varlen_plan_build_qk with a key list of its own).
+struct VarlenHeader { int magic, version, n_seqs, total, n_row_items, n_key_items, max_len, total_k; };
 constexpr int kVarlenMagic = 0x4c564146;      // "FAVL"
 constexpr int kVarlenVersion = 1;
 constexpr int kVarlenBlock = 256;             // rows per row-block item = keys per key-block item (kF1Rows, kBwdRows, kDkKeys)
@@ -90,13 +92,17 @@ inline size_t varlen_bytes(long long n_row, long long n_key)
 }
 
 // What a launch believes of the HOST copy of a plan (nothing of the device copy is read on the host)
-inline int varlen_check(const void* plan_host, const void* plan_dev, size_t plan_bytes, int total_rows, int heads, VarlenHeader* out)
+// one_list: asked by a one-list entry point, which refuses a two-sided plan (it would read K as T_q rows).  The _qk calls take
+// both kinds; a one-sided plan has as many key rows as query rows.
+inline int varlen_check(const void* plan_host, const void* plan_dev, size_t plan_bytes, int total_rows, int total_k, bool one_list,
+                        int heads, VarlenHeader* out)
 {
     if (plan_bytes < sizeof(VarlenHeader) || ((uintptr_t)plan_dev & 3)) return FA2_ERR_INVALID_SHAPE;
     VarlenHeader h;
     memcpy(&h, plan_host, sizeof h);
     if (h.magic != kVarlenMagic || h.version != kVarlenVersion) return FA2_ERR_INVALID_SHAPE;
-    if (h.total != total_rows || h.n_row_items < 1 || h.n_key_items < 1) return FA2_ERR_INVALID_SHAPE;
+    if (h.total != total_rows || h.n_row_items < 1 || h.n_key_items < 1 || h.total_k < 0) return FA2_ERR_INVALID_SHAPE;
+    if (one_list ? h.total_k != 0 : (h.total_k ? h.total_k : h.total) != total_k) return FA2_ERR_INVALID_SHAPE;
     if (plan_bytes < varlen_bytes(h.n_row_items, h.n_key_items)) return FA2_ERR_INVALID_SHAPE;
     if ((long long)std::max(h.n_row_items, h.n_key_items) * heads > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;      // the grid
     *out = h;
@@ -136,13 +142,15 @@ const char* fa2_status_string(int s)
 }
 
 // the bf16 forward of H query heads against H / kv_group K/V heads (fa2_forward: kv_group = 1)
+// (kv_len = 0: seq_len keys.  Another kv_len: the causal mask is aligned bottom-right, key j visible to query i iff
+// j <= i + kv_len - seq_len)
 static int forward_bf16(const void* Q, const void* K, const void* V, void* O, float* L, int B, int H, int kv_group, int seq_len,
-                        int head_dim, float softmax_scale, int causal, void* stream)
+                        int head_dim, float softmax_scale, int causal, void* stream, int kv_len = 0)
 {
     fa2::FwdArgs a{};
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L; a.Oacc = nullptr; a.M = nullptr;
-    a.BH = B * H; a.Nq = seq_len; a.Nk = seq_len; a.d = head_dim; a.scale = softmax_scale;
-    a.causal = causal ? 1 : 0; a.causal_shift = 0; a.resume = 0; a.finalize = 1; a.kv_group = kv_group;
+    a.BH = B * H; a.Nq = seq_len; a.Nk = kv_len ? kv_len : seq_len; a.d = head_dim; a.scale = softmax_scale;
+    a.causal = causal ? 1 : 0; a.causal_shift = causal ? a.Nk - a.Nq : 0; a.resume = 0; a.finalize = 1; a.kv_group = kv_group;
     return hip_status(fa2::launch_fwd1_bf16(a, (hipStream_t)stream));
 }
 
@@ -228,26 +236,111 @@ int fa2_varlen_plan_build(const int* cu_seqlens_host, int n_seqs, void* plan_hos
     return FA2_OK;
 }
 
-int fa2_forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
-                       int H_q, int H_kv, int total_rows, int head_dim, float softmax_scale, int dtype, int causal,
-                       const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
+int fa2_forward_qk(const void* Q, const void* K, const void* V, void* O, float* L,
+                   int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                   int dtype, int causal, void* stream)
+{
+    if (!Q || !K || !V || !O || !L) return FA2_ERR_NULL_POINTER;
+    int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
+    if (!st) st = check_common(B, H_q, kv_len, head_dim, softmax_scale);
+    if (st) return st;
+    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
+    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;      // as the packed calls: head_dim, then dtype
+    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    return forward_bf16(Q, K, V, O, L, B, H_q, H_q / H_kv, q_len, head_dim, softmax_scale, causal, stream, kv_len);
+}
+
+size_t fa2_varlen_plan_bytes_qk(int n_seqs, int total_q, int total_k)
+{
+    if (n_seqs < 1 || total_q < 1 || total_k < 1) return 0;
+    const long long n_row = (long long)total_q / kVarlenBlock + std::min(n_seqs, total_q);      // as fa2_varlen_plan_bytes, per side
+    const long long n_key = (long long)total_k / kVarlenBlock + std::min(n_seqs, total_k);
+    return varlen_bytes(n_row, n_key);
+}
+
+int fa2_varlen_plan_build_qk(const int* cu_seqlens_q_host, const int* cu_seqlens_k_host, int n_seqs, void* plan_host, size_t plan_bytes)
+{
+    const int *cq = cu_seqlens_q_host, *ck = cu_seqlens_k_host;
+    if (!cq || !plan_host) return FA2_ERR_NULL_POINTER;
+    if (n_seqs < 1) return FA2_ERR_INVALID_SHAPE;
+    // no key list, or the query list again: the one-sided plan, byte for byte
+    if (!ck || std::equal(cq, cq + n_seqs + 1, ck)) return fa2_varlen_plan_build(cq, n_seqs, plan_host, plan_bytes);
+    for (const int* cu : {cq, ck}) {
+        if (cu[0] != 0) return FA2_ERR_INVALID_SHAPE;
+        for (int i = 0; i < n_seqs; ++i)
+            if (cu[i + 1] < cu[i]) return FA2_ERR_INVALID_SHAPE;
+        if (cu[n_seqs] < 1 || cu[n_seqs] > kVarlenMaxRows) return FA2_ERR_INVALID_SHAPE;
+    }
+    const auto len_q = [&](int i) { return cq[i + 1] - cq[i]; };
+    const auto len_k = [&](int i) { return ck[i + 1] - ck[i]; };
+    const auto blocks = [](int len) { return (len + kVarlenBlock - 1) / kVarlenBlock; };
+    // sequences by descending work (len_q x len_k), ties by index: the one-sided order when the lengths are equal.  A sequence
+    // with one empty side has no product to form but still has outputs to write (O = 0, L = -inf; dK = dV = 0): it comes last
+    std::vector<int> order(n_seqs);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int a, int b) { return (long long)len_q(a) * len_k(a) > (long long)len_q(b) * len_k(b); });
+    long long n_row = 0, n_key = 0;
+    int max_len = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        n_row += blocks(len_q(i));
+        n_key += blocks(len_k(i));
+        max_len = std::max(max_len, len_q(i));
+    }
+    if (plan_bytes < varlen_bytes(n_row, n_key)) return FA2_ERR_WORKSPACE;
+    const VarlenHeader h{kVarlenMagic, kVarlenVersion, n_seqs, cq[n_seqs], (int)n_row, (int)n_key, max_len, ck[n_seqs]};
+    memcpy(plan_host, &h, sizeof h);
+    char* out = (char*)plan_host + sizeof h;
+    const auto put = [&](int seq, int block) {
+        const fa2::VarlenItem it{cq[seq], ck[seq], len_q(seq), len_k(seq), block};
+        memcpy(out, &it, sizeof it);
+        out += sizeof it;
+    };
+    for (int seq : order)      // row blocks of every sequence with a query (len_k = 0 included), descending
+        for (int b = blocks(len_q(seq)) - 1; b >= 0; --b) put(seq, b);
+    for (int seq : order)      // key blocks of every sequence with a key (len_q = 0 included), ascending
+        for (int b = 0; b < blocks(len_k(seq)); ++b) put(seq, b);
+    return FA2_OK;
+}
+
+// both packed forward entry points (one_list: fa2_forward_varlen, one T for both sides)
+static int forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
+                          int H_q, int H_kv, int total_q, int total_k, bool one_list, int head_dim, float softmax_scale, int dtype,
+                          int causal, const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
 {
     if (!Q || !K || !V || !O || !L || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
-    int st = check_common(1, H_q, total_rows, head_dim, softmax_scale);
+    int st = check_common(1, H_q, total_q, head_dim, softmax_scale);
+    if (!st) st = check_common(1, H_q, total_k, head_dim, softmax_scale);
     if (st) return st;
     if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
     VarlenHeader h;
-    if ((st = varlen_check(plan_host, plan_dev, plan_bytes, total_rows, H_q, &h))) return st;
+    if ((st = varlen_check(plan_host, plan_dev, plan_bytes, total_q, total_k, one_list, H_q, &h))) return st;
     if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;      // whatever the dtype: head_dim comes first
     if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
     fa2::VarlenFwdArgs v{};
     fa2::FwdArgs& a = v.a;
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L;
     a.BH = H_q; a.d = head_dim; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.finalize = 1;
-    a.q_hs = a.k_hs = total_rows; a.kv_group = H_q / H_kv;
+    a.q_hs = total_q; a.k_hs = total_k; a.kv_group = H_q / H_kv;
     v.items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
     v.n_items = h.n_row_items;
     return hip_status(fa2::launch_fwd1_varlen_bf16(v, (hipStream_t)stream));
+}
+
+int fa2_forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
+                       int H_q, int H_kv, int total_rows, int head_dim, float softmax_scale, int dtype, int causal,
+                       const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
+{
+    return forward_varlen(Q, K, V, O, L, H_q, H_kv, total_rows, total_rows, true, head_dim, softmax_scale, dtype, causal, plan_host,
+                          plan_dev, plan_bytes, stream);
+}
+
+int fa2_forward_varlen_qk(const void* Q, const void* K, const void* V, void* O, float* L,
+                          int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                          const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
+{
+    return forward_varlen(Q, K, V, O, L, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
+                          plan_dev, plan_bytes, stream);
 }
 
 size_t fa2_forward_fp8_workspace_bytes(int B, int H, int seq_len, int head_dim)
@@ -335,7 +428,7 @@ static bool bwd_fused_allowed()
     return allowed;
 }
 
-enum class Entry { phases, block, fused, status, plan };      // the public entry point that asks
+enum class Entry { phases, qk, block, fused, status, plan };      // the public entry point that asks
 enum class Path { none, f32, two_kernel, single };
 struct Route {
     int status = FA2_OK;
@@ -350,7 +443,7 @@ struct Route {
 // The one place the backward is routed (the rule: include/fa2_mi355x.h, fa2_backward): validation in the order of the asking
 // entry point, then what to run, its arguments and its workspace.  `t` holds the nine tensors (none for status and plan);
 // `phases` is fa2_backward_fused's mode.  `kv_heads`: 0 = as many K/V heads as query heads (every multi-head entry point); anything
-// else comes from the grouped-query entry points (phases and plan only), is validated here and changes nothing about WHICH
+// else comes from the grouped-query entry points (phases, qk and plan only), is validated here and changes nothing about WHICH
 // implementation runs -- rule (a) depends on seq_len and head_dim alone.
 static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int kv_heads, int q_len, int kv_len, int q_stride, int kv_stride,
                        int q_row0, int d, int dtype, int causal, int shift, float scale, int phases, const void* ws, size_t ws_bytes)
@@ -366,6 +459,21 @@ static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int kv_
     const auto kv_heads_ok = [&] { return kv_heads > 0 && H % kv_heads == 0; };
     const int kv_group = gqa && kv_heads > 0 && H > 0 ? H / kv_heads : 1;
     switch (entry) {
+    case Entry::qk:          // fa2_backward_qk: q_len queries against kv_len keys, grouped or not, bf16
+        if ((r.status = check_common(B, H, q_len, d, scale)) || (r.status = check_common(B, H, kv_len, d, scale))) return r;
+        if (!kv_heads_ok()) return fail(FA2_ERR_INVALID_SHAPE);
+        if (d != 64 && d != 128) return fail(FA2_ERR_UNSUPPORTED_HEAD_DIM);      // as the packed calls: head_dim, then dtype
+        if (dtype != FA2_DTYPE_BF16) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
+        if (q_len != kv_len) {      // a rectangle: the two deterministic kernels, whatever the shape
+            if ((r.status = check_bwd_planes(B, H, q_len))) return r;
+            r.ws = bwd_ws(ws, B, H, q_len, d, dtype);      // D and the two row-constant planes over [B][H][q_len], nothing else
+            r.ws.single = false; r.ws.bytes = r.ws.base_bytes;
+            if (!ws || ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
+            if (phases & 8) return fail(FA2_ERR_UNSUPPORTED);      // the single kernel takes no rectangle here
+            r.path = Path::two_kernel; r.args.phases = phases & 7;
+            break;
+        }
+        [[fallthrough]];     // equal lengths: fa2_backward_gqa's problem -- its rule, its workspace, its launches
     case Entry::phases:      // phases: 1 = D and the row constants, 2 = dQ kernel, 4 = dK/dV kernel, 8 = the single kernel
         if ((r.status = check_common(B, H, q_len, d, scale))) return r;
         if (gqa && !kv_heads_ok()) return fail(FA2_ERR_INVALID_SHAPE);
@@ -546,11 +654,58 @@ int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, i
     return r.status ? r.status : r.path == Path::single ? 1 : 2;
 }
 
+size_t fa2_backward_qk_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, int dtype)
+{
+    if (kv_len <= 0) return 0;
+    if (q_len == kv_len) return fa2_backward_gqa_workspace_bytes(B, H_q, H_kv, q_len, head_dim, dtype);
+    if (B <= 0 || H_q <= 0 || H_kv <= 0 || H_q % H_kv != 0 || q_len <= 0) return 0;
+    return bwd_ws(nullptr, B, H_q, q_len, head_dim, dtype).base_bytes;
+}
+
+int fa2_backward_qk(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                    void* dQ, void* dK, void* dV,
+                    int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                    int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases)
+{
+    return bwd_launch(bwd_route(Entry::qk, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H_q, H_kv ? H_kv : -1, q_len, kv_len, 0, 0, 0, head_dim,
+                                dtype, causal, kv_len - q_len, softmax_scale, phases, workspace, workspace_bytes), stream);
+}
+
 // D [H_q][T] and the two row-constant planes, laid out as the front of every other backward workspace
 size_t fa2_backward_varlen_workspace_bytes(int H_q, int H_kv, int total_rows, int head_dim, int dtype)
 {
     if (H_q <= 0 || H_kv <= 0 || H_q % H_kv != 0 || total_rows <= 0) return 0;
     return bwd_ws(nullptr, 1, H_q, total_rows, head_dim, dtype).base_bytes;
+}
+
+// both packed backward entry points (one_list: fa2_backward_varlen, one T for both sides)
+static int backward_varlen(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                           void* dQ, void* dK, void* dV,
+                           int H_q, int H_kv, int total_q, int total_k, bool one_list, int head_dim, float softmax_scale, int dtype,
+                           int causal, const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                           void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!Q || !K || !V || !O || !L || !dO || !dQ || !dK || !dV || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
+    int st = check_common(1, H_q, total_q, head_dim, softmax_scale);
+    if (!st) st = check_common(1, H_q, total_k, head_dim, softmax_scale);
+    if (st) return st;
+    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
+    if ((st = check_bwd_planes(1, H_q, total_q))) return st;
+    VarlenHeader h;
+    if ((st = varlen_check(plan_host, plan_dev, plan_bytes, total_q, total_k, one_list, H_q, &h))) return st;
+    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
+    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    const BwdWs ws = bwd_ws(workspace, 1, H_q, total_q, head_dim, dtype);
+    if (!workspace || workspace_bytes < ws.base_bytes) return FA2_ERR_WORKSPACE;
+    fa2::VarlenBwdArgs v{};
+    fa2::BwdArgs& a = v.a;
+    a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.L = L; a.dQ = dQ; a.dK = dK; a.dV = dV;
+    a.D = ws.D; a.RC = ws.RC; a.BH = H_q; a.Nq = total_q; a.Nk = total_k; a.d = head_dim;
+    a.q_hs = a.Nq; a.k_hs = a.Nk; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.phases = 7; a.kv_group = H_q / H_kv;
+    const auto* items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
+    v.row_items = items; v.n_row_items = h.n_row_items;
+    v.key_items = items + h.n_row_items; v.n_key_items = h.n_key_items;
+    return hip_status(fa2::launch_bwd_varlen_bf16(v, (hipStream_t)stream));
 }
 
 int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
@@ -559,26 +714,24 @@ int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void*
                         const void* plan_host, const void* plan_dev, size_t plan_bytes,
                         void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!Q || !K || !V || !O || !L || !dO || !dQ || !dK || !dV || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
-    int st = check_common(1, H_q, total_rows, head_dim, softmax_scale);
-    if (st) return st;
-    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
-    if ((st = check_bwd_planes(1, H_q, total_rows))) return st;
-    VarlenHeader h;
-    if ((st = varlen_check(plan_host, plan_dev, plan_bytes, total_rows, H_q, &h))) return st;
-    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
-    const BwdWs ws = bwd_ws(workspace, 1, H_q, total_rows, head_dim, dtype);
-    if (!workspace || workspace_bytes < ws.base_bytes) return FA2_ERR_WORKSPACE;
-    fa2::VarlenBwdArgs v{};
-    fa2::BwdArgs& a = v.a;
-    a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.L = L; a.dQ = dQ; a.dK = dK; a.dV = dV;
-    a.D = ws.D; a.RC = ws.RC; a.BH = H_q; a.Nq = a.Nk = total_rows; a.d = head_dim;
-    a.q_hs = a.k_hs = total_rows; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.phases = 7; a.kv_group = H_q / H_kv;
-    const auto* items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
-    v.row_items = items; v.n_row_items = h.n_row_items;
-    v.key_items = items + h.n_row_items; v.n_key_items = h.n_key_items;
-    return hip_status(fa2::launch_bwd_varlen_bf16(v, (hipStream_t)stream));
+    return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_rows, total_rows, true, head_dim, softmax_scale, dtype, causal, plan_host,
+                           plan_dev, plan_bytes, workspace, workspace_bytes, stream);
+}
+
+// the planes are indexed by query rows: the key side does not enter the size
+size_t fa2_backward_varlen_qk_workspace_bytes(int H_q, int H_kv, int total_q, int total_k, int head_dim, int dtype)
+{
+    return total_k <= 0 ? 0 : fa2_backward_varlen_workspace_bytes(H_q, H_kv, total_q, head_dim, dtype);
+}
+
+int fa2_backward_varlen_qk(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                           void* dQ, void* dK, void* dV,
+                           int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                           const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                           void* workspace, size_t workspace_bytes, void* stream)
+{
+    return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
+                           plan_dev, plan_bytes, workspace, workspace_bytes, stream);
 }
 
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,

@@ -494,6 +494,7 @@ __device__ __forceinline__ void fwd1_varlen_impl(const VarlenFwdArgs& v)
     p.K = (const char*)p.K + (size_t)it.k_row0 * ROWB;
     p.V = (const char*)p.V + (size_t)it.k_row0 * ROWB;
     p.Nq = it.len_q; p.Nk = it.len_k;
+    p.causal_shift = it.len_k - it.len_q;      // the mask is aligned to the sequence's last query and last key
     p.resume = 0; p.finalize = 1;          // (known here: the state branches of the STATE instance fold away)
     const int nrb = (it.len_q + kF1Rows - 1) / kF1Rows;
     fa2_fwd1_impl<D, QBS, CAUSAL, true>(p, head, CAUSAL ? nrb - 1 - it.block : it.block);
@@ -539,7 +540,9 @@ static hipError_t launch_one1(const FwdArgs& a, hipStream_t stream)
 }
 hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream)
 {
-    const bool state = a.resume || !a.finalize;
+    // a causal rectangle (causal_shift != 0: fa2_forward_qk) takes the one-row-block-per-workgroup schedule of the resumable
+    // steps and of the packed launches: the pairs of row blocks balance a square's triangle only
+    const bool state = a.resume || !a.finalize || (a.causal && a.causal_shift != 0);
     if (a.kv_group < 1 || a.BH % a.kv_group != 0) return hipErrorInvalidValue;
     if (a.d == 128) {
         if (state) return a.causal ? launch_one1<128, true, true>(a, stream) : launch_one1<128, false, true>(a, stream);

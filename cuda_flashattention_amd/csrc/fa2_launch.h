@@ -32,16 +32,19 @@ struct FwdArgs {
 
 hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream);     // generated main loop: one wave per SIMD (d = 128), two (d = 64)
 
-// Packed variable-length batches (fa2_forward_varlen / fa2_backward_varlen): tensors are head slabs [H][T][d] in which sequence
-// i owns rows [cu_seqlens[i], cu_seqlens[i + 1]); one launch covers every sequence.  A workgroup's unit of work is one item
+// Packed variable-length batches (fa2_forward_varlen / fa2_backward_varlen and their _qk forms): tensors are head slabs [H][T][d]
+// in which sequence i owns rows [cu_seqlens[i], cu_seqlens[i + 1]) -- of Q's T_q rows by one list and of K's T_k rows by a second
+// one in a two-sided plan; one launch covers every sequence.  A workgroup's unit of work is one item
 // of a table the host built (fa2_varlen_plan_build) and the caller uploaded: a 256-row block of one sequence's queries (forward,
 // dQ kernel) or a 256-key block of its keys (dK/dV kernel).
 struct VarlenItem {
     int q_row0, k_row0;   // the sequence's first row in Q / O / dO / dQ / L and in K / V / dK / dV
-    int len_q, len_k;     // its lengths on the two sides (equal in this version)
+    int len_q, len_k;     // its lengths on the two sides (a row-block item may have len_k = 0, a key-block item len_q = 0); the
+                          // causal mask of the view is shifted by len_k - len_q (the last query sees the last key)
     int block;            // which 256-row (256-key) block of the sequence
 };
-// a: the whole packed problem -- BH = H_q, q_hs = k_hs = T, pointers at row 0 of head 0; Nq, Nk, resume, finalize are per item
+// a: the whole packed problem -- BH = H_q, q_hs = T_q, k_hs = T_k, pointers at row 0 of head 0; Nq, Nk, causal_shift, resume,
+// finalize are per item
 struct VarlenFwdArgs { FwdArgs a; const VarlenItem* items; int n_items; };      // items: DEVICE memory, row-block items
 hipError_t launch_fwd1_varlen_bf16(const VarlenFwdArgs& v, hipStream_t stream);
 // acc (fp32) = (init) or += src (bf16): `rows` runs of `cols` elements, `pitch` elements apart in both.
@@ -80,12 +83,14 @@ struct BwdArgs {
     int phases;       // bit 0: D = rowsum(dO o O), bit 1: dQ kernel, bit 2: dK/dV kernel (7 = all)
     int reserve_cus;  // single-kernel form: CUs its persistent grid leaves free (for a communication kernel on another stream)
     int kv_group;     // grouped-query attention: query heads per K/V head (>= 1, divides BH; 1 = multi-head).  K, V, dK, dV
-                      // then hold BH / kv_group slabs and query head h works against slab h / kv_group; dense square problems only
+                      // then hold BH / kv_group slabs and query head h works against slab h / kv_group.  The two kernels of
+                      // fa2_bwd_bf16.hip take it on any problem (rectangular, packed); the single kernel on dense square ones only
 };
 
 hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream);
-// The two-kernel backward over a packed variable-length batch.  a: the whole packed problem -- BH = H_q, q_hs = k_hs = T, Nq = T for
-// the D kernel (one dense launch over H_q x T rows), q_row0 / Nq / Nk per item in the other two; D / RC dense [H_q][T] planes.
+// The two-kernel backward over a packed variable-length batch.  a: the whole packed problem -- BH = H_q, q_hs = T_q, k_hs = T_k,
+// Nq = T_q for the D kernel (one dense launch over H_q x T_q rows), q_row0 / Nq / Nk / causal_shift per item in the other two;
+// D / RC dense [H_q][T_q] planes.
 struct VarlenBwdArgs {
     BwdArgs a;
     const VarlenItem* row_items; const VarlenItem* key_items;      // DEVICE memory

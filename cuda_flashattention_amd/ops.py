@@ -222,38 +222,150 @@ def attention(Q, K, V, softmax_scale=None, causal=False):
     return _Attention.apply(Q, K, V, softmax_scale, causal)
 
 
+def _qk_shapes(Q, K, V):
+    """(B, H, H_kv, N_q, N_k, d) of a problem with its own query and key lengths, every relation between Q, K and V checked: 4-D
+    bf16 contiguous device tensors, Q [B, H, N_q, d], K and V [B, H_kv, N_k, d] with H_kv dividing H.  Shapes first, then what the
+    C ABI takes on trust -- device, contiguity, dtype."""
+    for n, t in (("Q", Q), ("K", K), ("V", V)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a [B, H, N, d] tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    B, H, Nq, d = Q.shape
+    Bk, Hkv, Nk, dk = K.shape
+    if (Bk, dk) != (B, d) or Hkv < 1 or H % Hkv != 0 or Nq < 1 or Nk < 1:
+        raise ValueError(f"K: shape {tuple(K.shape)} does not match Q {tuple(Q.shape)}: expected [B, H_kv, N_k, d] with B = {B}, "
+                         f"d = {d}, H_kv dividing H = {H} and N_q, N_k >= 1")
+    if tuple(V.shape) != tuple(K.shape):
+        raise ValueError(f"V: shape {tuple(V.shape)} does not match K {tuple(K.shape)}")
+    if Q.dtype != torch.bfloat16:
+        raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16 (different query and key lengths are bf16 in this version)")
+    _bhnd(Q, "Q")
+    _like(K, "K", Q, (B, Hkv, Nk, d), Q.dtype)
+    _like(V, "V", Q, (B, Hkv, Nk, d), Q.dtype)
+    return B, H, Hkv, Nq, Nk, d
+
+
+def flash_attention_2_qk_forward(Q, K, V, softmax_scale=None, causal=False, O=None, L=None, stream=None):
+    """O, L = FA2 forward of N_q queries against N_k keys (fa2_forward_qk): Q [B, H, N_q, d], K and V [B, H_kv, N_k, d] (H_kv
+    dividing H), bf16, d = 64 | 128.  Cross-attention, or (causal) a prompt chunk against a longer contiguous KV cache: the mask
+    is aligned bottom-right, key j visible to query i iff j <= i + N_k - N_q.  A query row that sees no key (causal, N_q > N_k)
+    has O = 0 and L = -inf.  With N_q == N_k this is flash_attention_2_forward, bit for bit."""
+    B, H, Hkv, Nq, Nk, d = _qk_shapes(Q, K, V)
+    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
+    L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
+    st = _capi.lib().fa2_forward_qk(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Nk, d, scale,
+                                    FA2_DTYPE_BF16, 1 if causal else 0, _stream_ptr(stream))
+    check(st, "fa2_forward_qk")
+    return O, L
+
+
+def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=False,
+                                  dQ=None, dK=None, dV=None, workspace=None, stream=None, phases=7):
+    """dQ, dK, dV = FA2 backward of flash_attention_2_qk_forward (fa2_backward_qk): dO like O, dK / dV like K / V.  N_q != N_k
+    runs the two deterministic kernels (phases: 1 = D and the row constants, 2 = dQ, 4 = dK/dV; 8, the single kernel, is
+    refused); N_q == N_k is flash_attention_2_backward.  A row that saw no key gets dQ = 0."""
+    B, H, Hkv, Nq, Nk, d = _qk_shapes(Q, K, V)
+    for n, t in (("O", O), ("dO", dO)):
+        _like(t, n, Q, (B, H, Nq, d), Q.dtype)
+    _rows(L, "L", Q, B, H, Nq)
+    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    dQ = torch.empty_like(Q) if dQ is None else _like(dQ, "dQ", Q, (B, H, Nq, d), Q.dtype)
+    dK = torch.empty_like(K) if dK is None else _like(dK, "dK", Q, (B, Hkv, Nk, d), Q.dtype)
+    dV = torch.empty_like(V) if dV is None else _like(dV, "dV", Q, (B, Hkv, Nk, d), Q.dtype)
+    lib = _capi.lib()
+    if workspace is None:
+        workspace = torch.empty(lib.fa2_backward_qk_workspace_bytes(B, H, Hkv, Nq, Nk, d, FA2_DTYPE_BF16), dtype=torch.uint8, device=Q.device)
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
+        raise ValueError("workspace must be a contiguous device tensor on Q's device")
+    st = lib.fa2_backward_qk(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
+                             dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, H, Hkv, Nq, Nk, d, scale, FA2_DTYPE_BF16,
+                             1 if causal else 0, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                             _stream_ptr(stream), int(phases))
+    check(st, "fa2_backward_qk")
+    return dQ, dK, dV
+
+
+class _AttentionQK(torch.autograd.Function):
+    """flash_attention_2_qk_forward / _backward as one differentiable op (as _Attention)."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, softmax_scale, causal):
+        Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
+        scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
+        O, L = flash_attention_2_qk_forward(Q, K, V, scale, causal=causal)
+        ctx.save_for_backward(Q, K, V, O, L)
+        ctx.scale, ctx.causal = scale, bool(causal)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, O, L = ctx.saved_tensors
+        dQ, dK, dV = flash_attention_2_qk_backward(Q, K, V, O, L, dO.contiguous(), ctx.scale, causal=ctx.causal)
+        return dQ, dK, dV, None, None
+
+
+def attention_qk(Q, K, V, softmax_scale=None, causal=False):
+    """attention() for N_q queries against N_k keys: Q [B, H, N_q, d], K and V [B, H_kv, N_k, d] bf16 device tensors (d = 64 | 128,
+    H_kv dividing H); causal: bottom-right aligned (the last query sees every key).  With gradients, shaped like K and V."""
+    return _AttentionQK.apply(Q, K, V, softmax_scale, causal)
+
+
 class VarlenPlan:
     """The work plan of a packed variable-length batch (fa2_varlen_plan_build): built on the host from cu_seqlens -- a list, a
     numpy array or a CPU integer tensor of n_seqs + 1 non-decreasing offsets starting at 0 -- when the object is made (no GPU
     needed), uploaded to a device the first time a call needs it there and kept for every later call: make one per batch
     layout and reuse it for every layer and step (and make the first call before capturing a graph: the upload is a copy).
-    Sequence i owns rows [cu_seqlens[i], cu_seqlens[i+1]) of every head of the packed [H, T, d] tensors."""
+    Sequence i owns rows [cu_seqlens[i], cu_seqlens[i+1]) of every head of the packed [H, T, d] tensors.
+    cu_seqlens_k: a second list of n_seqs + 1 offsets for the key side (fa2_varlen_plan_build_qk): sequence i then owns rows
+    cu_seqlens[i] : cu_seqlens[i+1] of Q's T_q = total rows and rows cu_seqlens_k[i] : cu_seqlens_k[i+1] of K's and V's
+    T_k = total_k rows, and the packed calls take K, V [H_kv, T_k, d].  None, or a list equal to cu_seqlens: the one-sided plan."""
 
     _HEADER_INTS, _ITEM_INTS = 8, 5
 
-    def __init__(self, cu_seqlens):
+    @staticmethod
+    def _offsets(cu_seqlens, name):
         if isinstance(cu_seqlens, torch.Tensor):
             if cu_seqlens.is_cuda:
-                raise ValueError("cu_seqlens must be host data (a list, a numpy array or a CPU tensor): the plan is built on the host")
+                raise ValueError(f"{name} must be host data (a list, a numpy array or a CPU tensor): the plan is built on the host")
             if cu_seqlens.is_floating_point() or cu_seqlens.is_complex() or cu_seqlens.dtype == torch.bool:
-                raise ValueError(f"cu_seqlens must hold integers, got {cu_seqlens.dtype}")
+                raise ValueError(f"{name} must hold integers, got {cu_seqlens.dtype}")
             cu_seqlens = cu_seqlens.numpy()
         cu = np.asarray(cu_seqlens)
         if cu.ndim != 1 or cu.size < 2 or not np.issubdtype(cu.dtype, np.integer):
-            raise ValueError("cu_seqlens: expected n_seqs + 1 >= 2 integer offsets in one dimension")
+            raise ValueError(f"{name}: expected n_seqs + 1 >= 2 integer offsets in one dimension")
         if int(cu.max()) > 2 ** 31 - 1 or int(cu.min()) < 0:
-            raise ValueError("cu_seqlens: offsets must be non-negative and fit 32 bits")
-        self.cu_seqlens = np.ascontiguousarray(cu, dtype=np.int32)
-        self.cu_seqlens.setflags(write=False)
+            raise ValueError(f"{name}: offsets must be non-negative and fit 32 bits")
+        cu = np.ascontiguousarray(cu, dtype=np.int32)
+        cu.setflags(write=False)
+        return cu
+
+    def __init__(self, cu_seqlens, cu_seqlens_k=None):
+        self.cu_seqlens = self._offsets(cu_seqlens, "cu_seqlens")
         lib = _capi.lib()
         n_seqs, total = self.cu_seqlens.size - 1, int(self.cu_seqlens[-1])
-        blob = np.zeros(max(lib.fa2_varlen_plan_bytes(n_seqs, total), 4 * self._HEADER_INTS), dtype=np.uint8)
-        st = lib.fa2_varlen_plan_build(self.cu_seqlens.ctypes.data, n_seqs, blob.ctypes.data, blob.size)
-        if st:
-            raise ValueError(f"cu_seqlens {self.cu_seqlens.tolist()[:8]}{'...' if n_seqs > 7 else ''}: fa2_varlen_plan_build status {st} "
-                             f"({lib.fa2_status_string(st).decode()}): offsets start at 0, never decrease and end at T >= 1")
+        if cu_seqlens_k is None:
+            self.cu_seqlens_k = self.cu_seqlens
+            blob = np.zeros(max(lib.fa2_varlen_plan_bytes(n_seqs, total), 4 * self._HEADER_INTS), dtype=np.uint8)
+            st = lib.fa2_varlen_plan_build(self.cu_seqlens.ctypes.data, n_seqs, blob.ctypes.data, blob.size)
+            if st:
+                raise ValueError(f"cu_seqlens {self.cu_seqlens.tolist()[:8]}{'...' if n_seqs > 7 else ''}: fa2_varlen_plan_build status {st} "
+                                 f"({lib.fa2_status_string(st).decode()}): offsets start at 0, never decrease and end at T >= 1")
+        else:
+            self.cu_seqlens_k = self._offsets(cu_seqlens_k, "cu_seqlens_k")
+            if self.cu_seqlens_k.size != self.cu_seqlens.size:
+                raise ValueError(f"cu_seqlens_k: {self.cu_seqlens_k.size} offsets beside the {self.cu_seqlens.size} of cu_seqlens "
+                                 "(both lists have n_seqs + 1 entries)")
+            blob = np.zeros(max(lib.fa2_varlen_plan_bytes_qk(n_seqs, total, int(self.cu_seqlens_k[-1])), 4 * self._HEADER_INTS), dtype=np.uint8)
+            st = lib.fa2_varlen_plan_build_qk(self.cu_seqlens.ctypes.data, self.cu_seqlens_k.ctypes.data, n_seqs, blob.ctypes.data, blob.size)
+            if st:
+                raise ValueError(f"cu_seqlens {self.cu_seqlens.tolist()[:8]}{'...' if n_seqs > 7 else ''} / cu_seqlens_k "
+                                 f"{self.cu_seqlens_k.tolist()[:8]}{'...' if n_seqs > 7 else ''}: fa2_varlen_plan_build_qk status {st} "
+                                 f"({lib.fa2_status_string(st).decode()}): each list starts at 0, never decreases and ends at a total >= 1")
         head = blob[:4 * self._HEADER_INTS].view(np.int32)
         self.n_seqs, self.total, n_row, n_key, self.max_len = int(head[2]), int(head[3]), int(head[4]), int(head[5]), int(head[6])
+        self.two_sided = int(head[7]) != 0                 # what the blob says: equal lists give the one-sided plan
+        self.total_k = int(head[7]) if self.two_sided else self.total
+        self.max_len_k = int(np.diff(self.cu_seqlens_k).max())
         lo, mid = 4 * self._HEADER_INTS, 4 * (self._HEADER_INTS + self._ITEM_INTS * n_row)
         self._blob = np.ascontiguousarray(blob[:mid + 4 * self._ITEM_INTS * n_key])      # what the launches validate and the devices hold
         self._blob.setflags(write=False)
@@ -297,7 +409,8 @@ def _htd(x, name, dtype=torch.bfloat16):
 
 
 def _varlen_shapes(Q, K, V, plan):
-    """(H, H_kv, T, d) of a packed problem, every relation between Q, K, V and the plan checked."""
+    """(H, H_kv, T, T_k, d) of a packed problem, every relation between Q, K, V and the plan checked (T_k = T under a one-sided
+    plan)."""
     if not isinstance(plan, VarlenPlan):
         raise ValueError("plan must be a VarlenPlan")
     for n, t in (("Q", Q), ("K", K), ("V", V)):
@@ -310,13 +423,15 @@ def _varlen_shapes(Q, K, V, plan):
     Hkv = K.shape[0]
     if Hkv < 1 or H % Hkv != 0:
         raise ValueError(f"K: {Hkv} key/value heads do not divide {H} query heads")
-    if tuple(K.shape) != (Hkv, T, d) or tuple(V.shape) != (Hkv, T, d):
-        raise ValueError(f"K {tuple(K.shape)} / V {tuple(V.shape)}: expected {(Hkv, T, d)} beside Q {tuple(Q.shape)}")
+    Tk = plan.total_k
+    if tuple(K.shape) != (Hkv, Tk, d) or tuple(V.shape) != (Hkv, Tk, d):
+        raise ValueError(f"K {tuple(K.shape)} / V {tuple(V.shape)}: expected {(Hkv, Tk, d)} beside Q {tuple(Q.shape)}"
+                         + (f" (the plan's cu_seqlens_k end at T_k = {Tk})" if plan.two_sided else ""))
     for n, t in (("Q", Q), ("K", K), ("V", V)):
         _htd(t, n)
         if t.device != Q.device:
             raise ValueError(f"{n} is on {t.device}, expected {Q.device}")
-    return H, Hkv, T, d
+    return H, Hkv, T, Tk, d
 
 
 def _packed(x, name, ref, shape):
@@ -330,15 +445,19 @@ def _packed(x, name, ref, shape):
 def flash_attention_2_varlen_forward(Q, K, V, plan, softmax_scale=None, causal=False, O=None, L=None, stream=None):
     """O, L = FA2 forward over a packed variable-length batch (fa2_forward_varlen): Q [H, T, d], K and V [H_kv, T, d] (H_kv
     dividing H), bf16, d = 64 | 128; sequence i owns rows plan.cu_seqlens[i] : plan.cu_seqlens[i+1] of every head and attends only
-    itself (causal: within itself).  L is fp32 [H, T].  A [T, H, d] tensor must be transposed (and made contiguous) first."""
-    H, Hkv, T, d = _varlen_shapes(Q, K, V, plan)
+    itself (causal: within itself).  L is fp32 [H, T].  A [T, H, d] tensor must be transposed (and made contiguous) first.
+    Under a two-sided plan (VarlenPlan(cu_seqlens, cu_seqlens_k); fa2_forward_varlen_qk) K and V are [H_kv, T_k, d] and sequence i
+    attends its own key rows, causal: bottom-right aligned; a query row that sees no key has O = 0 and L = -inf."""
+    H, Hkv, T, Tk, d = _varlen_shapes(Q, K, V, plan)
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
     O = torch.empty_like(Q) if O is None else _packed(O, "O", Q, (H, T, d))
     L = torch.empty(H, T, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, 1, H, T)
-    st = _capi.lib().fa2_forward_varlen(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), H, Hkv, T, d, scale,
-                                        FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(),
-                                        plan.nbytes, _stream_ptr(stream))
-    check(st, "fa2_forward_varlen")
+    lib, ptrs = _capi.lib(), (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr())
+    tail = (d, scale, FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(), plan.nbytes, _stream_ptr(stream))
+    if plan.two_sided:
+        check(lib.fa2_forward_varlen_qk(*ptrs, H, Hkv, T, Tk, *tail), "fa2_forward_varlen_qk")
+    else:
+        check(lib.fa2_forward_varlen(*ptrs, H, Hkv, T, *tail), "fa2_forward_varlen")
     return O, L
 
 
@@ -346,25 +465,28 @@ def flash_attention_2_varlen_backward(Q, K, V, O, L, dO, plan, softmax_scale=Non
                                       dQ=None, dK=None, dV=None, workspace=None, stream=None):
     """dQ, dK, dV = FA2 backward over a packed variable-length batch (fa2_backward_varlen; the two deterministic kernels): the
     tensors of flash_attention_2_varlen_forward, dO like O, dK / dV like K / V.  workspace: a uint8 device tensor of
-    fa2_backward_varlen_workspace_bytes (allocated per call when omitted -- pass one for graph capture)."""
-    H, Hkv, T, d = _varlen_shapes(Q, K, V, plan)
+    fa2_backward_varlen_workspace_bytes (allocated per call when omitted -- pass one for graph capture).  Under a two-sided plan
+    (fa2_backward_varlen_qk) dK / dV are [H_kv, T_k, d]; a sequence with keys and no queries gets dK = dV = 0."""
+    H, Hkv, T, Tk, d = _varlen_shapes(Q, K, V, plan)
     for n, t in (("O", O), ("dO", dO)):
         _packed(t, n, Q, (H, T, d))
     _rows(L, "L", Q, 1, H, T)
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
     dQ = torch.empty_like(Q) if dQ is None else _packed(dQ, "dQ", Q, (H, T, d))
-    dK = torch.empty_like(K) if dK is None else _packed(dK, "dK", Q, (Hkv, T, d))
-    dV = torch.empty_like(V) if dV is None else _packed(dV, "dV", Q, (Hkv, T, d))
+    dK = torch.empty_like(K) if dK is None else _packed(dK, "dK", Q, (Hkv, Tk, d))
+    dV = torch.empty_like(V) if dV is None else _packed(dV, "dV", Q, (Hkv, Tk, d))
     lib = _capi.lib()
     if workspace is None:
         workspace = torch.empty(lib.fa2_backward_varlen_workspace_bytes(H, Hkv, T, d, FA2_DTYPE_BF16), dtype=torch.uint8, device=Q.device)
     if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
         raise ValueError("workspace must be a contiguous device tensor on Q's device")
-    st = lib.fa2_backward_varlen(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
-                                 dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), H, Hkv, T, d, scale, FA2_DTYPE_BF16, 1 if causal else 0,
-                                 plan.host_ptr(), plan.device(Q.device).data_ptr(), plan.nbytes,
-                                 workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr(stream))
-    check(st, "fa2_backward_varlen")
+    ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr())
+    tail = (d, scale, FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(), plan.nbytes,
+            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr(stream))
+    if plan.two_sided:
+        check(lib.fa2_backward_varlen_qk(*ptrs, H, Hkv, T, Tk, *tail), "fa2_backward_varlen_qk")
+    else:
+        check(lib.fa2_backward_varlen(*ptrs, H, Hkv, T, *tail), "fa2_backward_varlen")
     return dQ, dK, dV
 
 
@@ -389,7 +511,8 @@ class _AttentionVarlen(torch.autograd.Function):
 
 def attention_varlen(Q, K, V, plan, softmax_scale=None, causal=False):
     """attention() over a packed variable-length batch: Q [H, T, d], K and V [H_kv, T, d] bf16 device tensors (d = 64 | 128, H_kv
-    dividing H), plan a VarlenPlan of the batch's cu_seqlens; every sequence attends itself only.  With gradients."""
+    dividing H), plan a VarlenPlan of the batch's cu_seqlens; every sequence attends itself only.  With gradients.  Under a
+    two-sided plan K and V are [H_kv, T_k, d] and so are their gradients."""
     return _AttentionVarlen.apply(Q, K, V, plan, softmax_scale, causal)
 
 

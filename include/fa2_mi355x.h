@@ -217,9 +217,9 @@ int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, i
  * holds [T][H][d] transposes first.  Sequences of length 0 are allowed and cost nothing.
  * THE PLAN.  cu_seqlens is HOST data, like every other size here.  fa2_varlen_plan_build (pure host code, no device needed)
  * validates it and writes a blob of at most fa2_varlen_plan_bytes(n_seqs, T) bytes into plan_host: a header (magic, version,
- * n_seqs, T, the two item counts, the longest length, one reserved word: 8 ints) and two lists of items, each five ints
- * {q_row0, k_row0, len_q, len_k, block} -- both sides are carried although they are equal today, so that different query and key
- * lengths need no new format.  ROW-BLOCK items (256 query rows of one sequence) are the units of the forward and of the dQ
+ * n_seqs, T, the two item counts, the longest length, and a word that is 0 in this one-list plan and the key side's row count
+ * in a two-sided one, see fa2_varlen_plan_build_qk below: 8 ints) and two lists of items, each five ints
+ * {q_row0, k_row0, len_q, len_k, block} -- both sides are carried; they are equal in a one-list plan.  ROW-BLOCK items (256 query rows of one sequence) are the units of the forward and of the dQ
  * kernel, KEY-BLOCK items (256 keys) those of the dK/dV kernel.  ORDER, deterministic and the same with or without the causal
  * mask: sequences by descending length, ties by index; within a sequence row blocks descend and key blocks ascend (the heaviest
  * first under a causal mask, indifferent without one); a sequence's blocks are adjacent, so its K / V stay in one XCD's L2.
@@ -237,13 +237,13 @@ int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, i
  * A sequence never reads another's rows: every buffer resource ends where the sequence ends.  DETERMINISTIC: no atomics, every
  * sum in a fixed order.  Nothing synchronises and nothing is allocated: the launch calls may be captured in a graph.
  * STATUS CODES, in this order: NULL pointers (the plan's included) -> FA2_ERR_NULL_POINTER; H_q, T, scale, H_kv not dividing
- * H_q, total_rows different from the plan's T, a blob without the magic, plan_bytes smaller than the blob ->
- * FA2_ERR_INVALID_SHAPE; head_dim -> FA2_ERR_UNSUPPORTED_HEAD_DIM; fp32 and fp8 -> FA2_ERR_UNSUPPORTED_DTYPE; workspace ->
+ * H_q, total_rows different from the plan's T, a blob without the magic, plan_bytes smaller than the blob, a two-sided plan
+ * (these two calls would read K as T_q rows: it belongs to the _qk calls) -> FA2_ERR_INVALID_SHAPE; head_dim -> FA2_ERR_UNSUPPORTED_HEAD_DIM; fp32 and fp8 -> FA2_ERR_UNSUPPORTED_DTYPE; workspace ->
  * FA2_ERR_WORKSPACE.  fa2_varlen_plan_build: NULL -> FA2_ERR_NULL_POINTER; n_seqs < 1, cu_seqlens[0] != 0, a decreasing entry,
  * T < 1 or T above 4194303 rows (the 2 GiB-per-plane rule of every call, at the widest row) -> FA2_ERR_INVALID_SHAPE; plan_bytes
  * too small for this cu_seqlens -> FA2_ERR_WORKSPACE.  fa2_varlen_plan_bytes returns 0 for n_seqs < 1 or total_rows < 1.
- * NOT COVERED in this version: different query and key lengths per sequence (the item format already carries them), the
- * single-kernel backward on packed batches, fp32 and fp8, the ring, a paged KV cache. */
+ * NOT COVERED in this version: the single-kernel backward on packed batches, fp32 and fp8, the ring, a paged KV cache.
+ * (Different query and key lengths per sequence: the _qk calls below.) */
 size_t fa2_varlen_plan_bytes(int n_seqs, int total_rows);
 int fa2_varlen_plan_build(const int* cu_seqlens_host, int n_seqs, void* plan_host, size_t plan_bytes);
 int fa2_forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
@@ -255,6 +255,65 @@ int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void*
                         int H_q, int H_kv, int total_rows, int head_dim, float softmax_scale, int dtype, int causal,
                         const void* plan_host, const void* plan_dev, size_t plan_bytes,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Different query and key lengths ("qk"): cross-attention, a prompt chunk against a longer contiguous KV cache (chunked
+ * prefill), and ragged batches of either.  bf16, head_dim 64 or 128, H_q % H_kv == 0 (multi-head, GQA, MQA), causal or not,
+ * DETERMINISTIC (no atomics).
+ * DENSE LAYOUT: Q, O, dO, dQ [B][H_q][q_len][d]; K, V, dK, dV [B][H_kv][kv_len][d]; L [B][H_q][q_len]; q_len >= 1, kv_len >= 1.
+ * PACKED LAYOUT: Q, O, dO, dQ [H_q][T_q][d]; K, V, dK, dV [H_kv][T_k][d]; L [H_q][T_q].  Sequence i owns query rows
+ * [cu_q[i], cu_q[i+1]) and key rows [cu_k[i], cu_k[i+1]); T_q >= 1 and T_k >= 1; any single sequence may have len_q == 0,
+ * len_k == 0, or both.
+ * CAUSAL MASK, BOTTOM-RIGHT ALIGNED: key j is visible to query i of the same sequence iff j <= i + (len_k - len_q).  The last
+ * query sees every key; with len_q == len_k this is the mask of every other call; the shift len_k - len_q may be negative.
+ * A QUERY ROW THAT SEES NO KEY (causal with len_q > len_k, or len_k == 0) has O = 0 and L = -inf (the log-sum-exp of nothing); in
+ * the backward its dQ = 0 and it contributes nothing to dK or dV.  A sequence with len_q == 0 < len_k gets dK = dV = 0 written
+ * for its keys.  Every output element of every row in [0, T) is written by every call, and for finite inputs no NaN and no Inf
+ * appears in O, dQ, dK or dV (the backward gives such a row finite row constants under which P vanishes, as the single kernel
+ * does for rows past the end).
+ * DENSE CALLS.  q_len == kv_len enqueues exactly what fa2_forward_gqa / fa2_backward_gqa enqueue -- the same routing rule, the same
+ * workspace size, bit-identical results.  q_len != kv_len: the forward runs one 256-row block per workgroup when causal (the
+ * two-block pairing balances a square's triangle only); the backward ALWAYS runs the two deterministic kernels (`phases` as
+ * fa2_backward_gqa; bit 3, the single kernel, -> FA2_ERR_UNSUPPORTED), a dK/dV workgroup walking the query tiles of its group's
+ * heads as in fa2_backward_gqa, and fa2_backward_qk_workspace_bytes is D plus the two row-constant planes over [B][H_q][q_len].
+ * THE TWO-SIDED PLAN.  fa2_varlen_plan_build_qk takes two lists of n_seqs + 1 offsets.  With cu_seqlens_k_host NULL or
+ * element-wise equal to the query list it writes BYTE FOR BYTE what fa2_varlen_plan_build writes (a one-list plan).  Otherwise:
+ * the same magic, version and item format; the header's last word holds T_k (it is 0 in a one-list plan), its "longest length"
+ * the longest len_q.  ORDER: sequences by descending len_q x len_k (64-bit), ties by index -- the one-list order when the lengths
+ * are equal; row-block items for every sequence with len_q > 0 (len_k == 0 included), blocks descending; key-block items for
+ * every sequence with len_k > 0 (len_q == 0 included), blocks ascending.  The two item counts may differ.
+ * fa2_varlen_plan_bytes_qk(n_seqs, T_q, T_k) bounds the blob (0 for n_seqs < 1, T_q < 1 or T_k < 1).  Validation, per list:
+ * offsets start at 0, never decrease, end at a total >= 1 and within the row limit of fa2_varlen_plan_build ->
+ * FA2_ERR_INVALID_SHAPE otherwise; NULL query list or plan -> FA2_ERR_NULL_POINTER; plan_bytes too small -> FA2_ERR_WORKSPACE.
+ * PACKED CALLS.  fa2_forward_varlen_qk / fa2_backward_varlen_qk take both kinds of plan; with a one-list plan they require
+ * total_k == total_q and are fa2_forward_varlen / fa2_backward_varlen.  Kernels, grids and the bit-identity of a sequence with the
+ * dense call on that sequence alone (here: fa2_forward_qk, and fa2_backward_qk with phases 1, then 6, for sequences with both
+ * lengths >= 1) are those of the packed calls above; the workspace is D and the two row-constant planes over [H_q][T_q].
+ * STATUS CODES of every call with tensors, in this order: NULL pointers -> FA2_ERR_NULL_POINTER; B, H_q, a length or total, scale,
+ * H_kv not dividing H_q, totals different from the plan's, a blob without the magic or longer than plan_bytes ->
+ * FA2_ERR_INVALID_SHAPE; head_dim -> FA2_ERR_UNSUPPORTED_HEAD_DIM; fp32 and fp8 -> FA2_ERR_UNSUPPORTED_DTYPE; workspace ->
+ * FA2_ERR_WORKSPACE; then (dense rectangle, phases bit 3) FA2_ERR_UNSUPPORTED.
+ * NOT COVERED: the single-kernel backward on rectangles, fp32 and fp8, the ring, a paged or non-contiguous KV cache, sliding
+ * windows, a split-KV decode kernel (q_len = 1 works but gets one workgroup per head). */
+int fa2_forward_qk(const void* Q, const void* K, const void* V, void* O, float* L,
+                   int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                   int dtype, int causal, void* stream);
+size_t fa2_backward_qk_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, int dtype);
+int fa2_backward_qk(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                    void* dQ, void* dK, void* dV,
+                    int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                    int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases);
+size_t fa2_varlen_plan_bytes_qk(int n_seqs, int total_q, int total_k);
+int fa2_varlen_plan_build_qk(const int* cu_seqlens_q_host, const int* cu_seqlens_k_host, int n_seqs, void* plan_host,
+                             size_t plan_bytes);
+int fa2_forward_varlen_qk(const void* Q, const void* K, const void* V, void* O, float* L,
+                          int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                          const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream);
+size_t fa2_backward_varlen_qk_workspace_bytes(int H_q, int H_kv, int total_q, int total_k, int head_dim, int dtype);
+int fa2_backward_varlen_qk(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
+                           void* dQ, void* dK, void* dV,
+                           int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                           const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output
