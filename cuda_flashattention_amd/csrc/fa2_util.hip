@@ -149,25 +149,40 @@ hipError_t launch_accumulate_bf16(float* acc, const void* src, size_t rows, size
 // Per XCC two 64-bit counters into out[2 x] , out[2 x + 1] (x = HW_REG_XCC_ID, 16 possible values): s_memtime (ticks of the
 // shader clock) and s_memrealtime (the constant 100 MHz reference).  Two calls bracket a stretch of stream work;
 // d(memtime) / d(memrealtime) x 100 MHz PER XCC is the mean shader clock the chip held over it (MI355X_MICROARCH.md, DVFS
-// give-back item 6) -- what bench.py's `sustained` object reports.  Per XCC because s_memtime is an XCC's own counter: a
+// give-back item 6) -- what bench.py's `sustained` object reports.  Per XCC because each XCC holds its own clock: a
 // one-workgroup kernel lands on whichever XCC the dispatcher's rotation points at, and two such samples taken on different
 // XCCs differ by the counters' offset, not by elapsed clocks (round 3's rehearsal read "225 MHz" that way as soon as a
-// second process shared the GPU and moved the rotation).  64 workgroups reach every XCC of the device; the workgroups of
-// one XCC write the same slot with 16-byte stores a few hundred clocks apart: any of them will do.
+// second process shared the GPU and moved the rotation).
+// Nor is s_memtime ONE counter per XCC: every CU reads a counter of its own, all at the XCC's rate but up to ~2e8 ticks apart
+// (measured: 32 CUs of one XCC stamped within 0.1 us of each other spread over 1.2e8 - 1.9e8 ticks, the same spread in every
+// sample; differences taken on one CU agree to the last digit on all 32, differences across CUs read anything from -900 to
+// +3100 "MHz" over 0.2 s).  A slot that whichever workgroup of the XCC came last overwrites is therefore a sample of a
+// random CU.  Each slot takes the MAXIMUM over the XCC's workgroups instead (the caller zeroes the buffer): with every CU
+// stamped in both samples that is the same CU's counter both times -- the one furthest ahead -- or, where two CUs are
+// closer than the few thousand ticks between stamps, one within that of it.  8 single-wave workgroups per CU, each held
+// for ~4 us after its stamp so that the dispatcher has to spread them, reach every CU (measured: 32 of 32 per XCC in every
+// sample).  The 100 MHz reference is one counter for the device; its maximum is the last stamp, < 1 us from any other.
+constexpr int kClockStampsPerCU = 8;
+
 __global__ void __launch_bounds__(64) read_clocks_kernel(unsigned long long* out)
 {
     int xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
     if (threadIdx.x == 0) {
-        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-        const u64x2 v = {__builtin_amdgcn_s_memtime(), __builtin_amdgcn_s_memrealtime()};
-        *reinterpret_cast<u64x2*>(out + 2 * xcc) = v;
+        const unsigned long long t = __builtin_amdgcn_s_memtime(), rt = __builtin_amdgcn_s_memrealtime();
+        atomicMax(out + 2 * xcc, t);
+        atomicMax(out + 2 * xcc + 1, rt);
     }
+    __builtin_amdgcn_s_sleep(127);
 }
 
 hipError_t launch_read_clocks(unsigned long long* out, hipStream_t stream)
 {
-    hipLaunchKernelGGL(read_clocks_kernel, dim3(64), dim3(64), 0, stream, out);
+    int dev = 0, cus = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(read_clocks_kernel, dim3((unsigned)(kClockStampsPerCU * (cus > 0 ? cus : 256))), dim3(64), 0, stream, out);
     return hipGetLastError();
 }
 

@@ -526,8 +526,8 @@ def read_clocks(stream=None):
 
 def mean_shader_clock_mhz(before, after):
     """Mean shader clock between two read_clocks samples (the caller has synchronised): per XCC present in both,
-    d(ticks) / d(reference ticks) x 100 MHz; the mean over those XCCs.  s_memtime is an XCC's own counter, so a difference
-    is only ever taken within one XCC."""
+    d(ticks) / d(reference ticks) x 100 MHz; the mean over those XCCs.  s_memtime counts per CU at its XCC's clock (a sample
+    holds, per XCC, the counter furthest ahead), so a difference is only ever taken within one XCC."""
     a, b = before.cpu().tolist(), after.cpu().tolist()
     vals = [(y[0] - x[0]) / (y[1] - x[1]) * 100.0 for x, y in zip(a, b) if x[1] and y[1] and y[1] > x[1]]
     if not vals:

@@ -403,8 +403,10 @@ int fa2_accumulate_bf16_2d(float* acc, const void* src, size_t rows, size_t cols
 
 /* Measurement aid: a small kernel on `stream` writes, for every XCC x of the device it reaches (x = HW_REG_XCC_ID < 16), two
  * 64-bit device counters to out32[2 x], out32[2 x + 1] (DEVICE memory, 32 x 8 = 256 bytes, 16-byte aligned, zeroed by the
- * caller: an XCC the device does not have keeps zeros): shader-clock ticks (s_memtime: an XCC's own counter, so only
- * differences taken on the SAME XCC mean anything) and ticks of the constant 100 MHz reference (s_memrealtime).  Bracket a
+ * caller: an XCC the device does not have keeps zeros, and each slot takes the MAXIMUM over the XCC's workgroups): shader-clock
+ * ticks (s_memtime: every CU has a counter of its own, offset from its neighbours'; the maximum over all CUs of an XCC is the
+ * same CU's in every sample, so only differences taken on the SAME XCC mean anything) and ticks of the constant 100 MHz
+ * reference (s_memrealtime).  Bracket a
  * stretch of work with two calls into two buffers: per XCC, d(ticks) / d(reference ticks) x 100 MHz is the mean shader clock
  * it held over the stretch (cuda_flashattention_amd.ops.mean_shader_clock_mhz averages the XCCs present in both). */
 int fa2_read_clocks(unsigned long long* out32, void* stream);

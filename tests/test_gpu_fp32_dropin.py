@@ -201,7 +201,7 @@ def test_fa1_baseline_matches_oracle_medium():
 
 
 def test_read_clocks_brackets_a_stretch_of_work():
-    """fa2_read_clocks: per XCC two 64-bit device counters (shader-clock ticks -- the XCC's own counter -- and 100 MHz
+    """fa2_read_clocks: per XCC two 64-bit device counters (shader-clock ticks -- of the CU whose counter is furthest ahead -- and 100 MHz
     reference ticks); two calls around some work give a plausible mean shader clock on every XCC (what bench.py's
     `sustained` object reports).  The XCCs need not agree exactly: each holds its own clock (measured on a lightly loaded
     stretch: 1106 - 1174 MHz across the eight) -- one more reason never to difference counters of two XCCs."""
@@ -223,6 +223,28 @@ def test_read_clocks_brackets_a_stretch_of_work():
     assert max(per) - min(per) < 0.25 * max(per), per       # eight clock domains, one power budget
     assert abs(fa.ops.mean_shader_clock_mhz(a, b) - sum(per) / 8) < 1e-6
     assert lib.fa2_read_clocks(None, s) == -1
+
+
+def test_read_clocks_samples_one_counter_per_xcc_every_time():
+    """Every CU has a shader-clock counter of its own, up to ~2e8 ticks from its neighbours' on the same XCC (measured), so a
+    sample that took whichever CU's workgroup wrote last reads anything from negative to several GHz over a short stretch:
+    2e8 ticks are 10 GHz over 20 ms.  Six samples around five stretches of ~20 ms: every XCC, every stretch, between 100 MHz
+    and the 2600 MHz that the test above allows a chip whose clock tops out at 2400."""
+    import cuda_flashattention_amd as fa
+    x = torch.rand(4096, 4096, device="cuda")
+    samples = [fa.ops.read_clocks()]
+    for _ in range(5):
+        for _ in range(20):
+            x = x @ x * 1e-3
+        samples.append(fa.ops.read_clocks())
+    torch.cuda.synchronize()
+    c = [t.cpu().tolist() for t in samples]
+    for a, b in zip(c[:-1], c[1:]):
+        present = [i for i in range(16) if a[i][1] and b[i][1]]
+        assert len(present) == 8, present
+        per = [(b[i][0] - a[i][0]) / (b[i][1] - a[i][1]) * 100.0 for i in present]
+        print("per XCC, MHz:", [round(m, 1) for m in per])
+        assert all(100.0 < m < 2600.0 for m in per), per
 
 
 def test_bare_mfma_probe_reports_a_plausible_ceiling():

@@ -2,8 +2,8 @@
 K, V, dK, dV [B, H_kv, N_k, d]) and packed (fa2_forward_varlen_qk / fa2_backward_varlen_qk under a two-sided VarlenPlan: Q
 [H_q, T_q, d], K, V [H_kv, T_k, d]).  Causal mask bottom-right aligned: key j visible to query i iff j <= i + (len_k - len_q).
 
-REFERENCE.  The oracle computes square problems only, so this file carries a float64 NumPy reference for rectangular attention,
-forward and backward (ref_attention), with the mask and the empty-row rules of include/fa2_mi355x.h: a query row that sees no
+REFERENCE.  The oracle computes square problems only, so tests/regimes.py carries a float64 NumPy reference for rectangular
+attention, forward and backward (ref_attention, imported here), with the mask and the empty-row rules of include/fa2_mi355x.h: a query row that sees no
 key has O = 0, L = -inf, dQ = 0 and adds nothing to dK / dV.  tests/test_qk_plan.py pins it to the oracle on square shapes.  It
 runs on the bf16-rounded inputs, K / V repeated to H_q heads on the host, dK / dV summed over each group.
 
@@ -25,6 +25,8 @@ import numpy as np
 import pytest
 import torch
 
+from regimes import _group_sum, ref_attention
+
 pytestmark = pytest.mark.gpu
 
 BF16_REL = 5e-3
@@ -42,41 +44,6 @@ DENSE_CASES = tuple(itertools.product(PAIRS, (64, 128), (False, True)))
 PACKED_CASES = tuple(itertools.product(PAIRS, (64, 128), (False, True), ("A", "B")))
 SENTINEL16, SENTINEL32 = 0x5A5A, 0x5A5A5A5A               # bf16 1.5e16 / fp32 1.5e16: nothing these inputs produce (test_gpu_varlen.py)
 NAMES = ("O", "L", "dQ", "dK", "dV")
-
-
-# ------------------------------------------------------------------------------------------------ the float64 reference
-def ref_attention(q, k, v, g, scale, causal, want_abs=False):
-    """float64 O, L, dQ, dK, dV of softmax(scale q k^T [bottom-right causal]) v and its backward under dO = g.  q, g [..., Nq, d];
-    k, v [..., Nk, d] (same leading dimensions); Nq or Nk may be 0.  A row without a visible key: O = 0, L = -inf, dQ = 0.
-    want_abs: also the magnitudes of the terms that dQ and dK sum (the same formulas on absolute values)."""
-    q, k, v, g = (np.asarray(t, dtype=np.float64) for t in (q, k, v, g))
-    nq, nk = q.shape[-2], k.shape[-2]
-    s = scale * (q @ np.swapaxes(k, -1, -2))
-    if causal:
-        i, j = np.arange(nq)[:, None], np.arange(nk)[None, :]
-        s = np.where(j <= i + (nk - nq), s, -np.inf)
-    m = s.max(axis=-1, initial=-np.inf)
-    seen = np.isfinite(m)                                            # rows with a visible key
-    p = np.exp(s - np.where(seen, m, 0.0)[..., None])                # exp(-inf) = 0 on masked keys and on rows without any
-    l = p.sum(axis=-1)
-    with np.errstate(divide="ignore"):
-        L = np.where(seen, m + np.log(np.where(seen, l, 1.0)), -np.inf)
-    P = p / np.where(seen, l, 1.0)[..., None]
-    O = P @ v
-    D = (g * O).sum(axis=-1)
-    dP = g @ np.swapaxes(v, -1, -2)
-    dS = P * (dP - D[..., None])
-    dQ, dK, dV = scale * (dS @ k), scale * (np.swapaxes(dS, -1, -2) @ q), np.swapaxes(P, -1, -2) @ g
-    if not want_abs:
-        return O, L, dQ, dK, dV
-    aS = P * (np.abs(g) @ np.swapaxes(np.abs(v), -1, -2) + (np.abs(g) * np.abs(O)).sum(axis=-1)[..., None])
-    return (O, L, dQ, dK, dV), (scale * (aS @ np.abs(k)), scale * (np.swapaxes(aS, -1, -2) @ np.abs(q)))
-
-
-def _group_sum(x, hkv):
-    """[..., H_q, N, d] -> [..., H_kv, N, d]: the gradients of a K/V head are the sums over its group's query heads."""
-    *lead, hq, n, d = x.shape
-    return x.reshape(*lead, hkv, hq // hkv, n, d).sum(axis=-3)
 
 
 def _rel(a, b):

@@ -1,6 +1,7 @@
 """CPU: the two-sided plan of a packed batch with its own query and key lengths (fa2_varlen_plan_build_qk, VarlenPlan(cu_seqlens,
 cu_seqlens_k)), the argument checking of every _qk entry point and of their Python wrappers, and the float64 NumPy reference of
-tests/test_gpu_qk.py pinned to the oracle on square shapes.  No GPU: the plan is host code, and the launch calls are only driven
+tests/regimes.py (what tests/test_gpu_qk.py and tests/test_gpu_regimes.py judge the kernels by) pinned to the oracle on square
+shapes.  No GPU: the plan is host code, and the launch calls are only driven
 into the returns that come before any device call (never-dereferenced pointers, the `one = c_void_p(16)` idiom of
 test_capi_symbols.py)."""
 import ctypes
@@ -9,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_qk import ref_attention
+from regimes import ref_attention
 
 PAIRS = ((300, 1), (1, 300), (0, 77), (257, 64), (77, 0), (0, 0), (600, 1100), (256, 512), (512, 256), (255, 255), (64, 257))
 HEADER_BYTES, ITEM_INTS = 32, 5
@@ -258,7 +259,7 @@ def test_python_wrappers_refuse_what_the_abi_would_take_on_trust():
 
 @pytest.mark.parametrize("causal", [False, True])
 def test_the_numpy_reference_equals_the_oracle_on_square_shapes(causal):
-    """ref_attention of tests/test_gpu_qk.py against oracle.attention_forward / attention_backward at [1, 3, 300, 64] and a second,
+    """ref_attention of tests/regimes.py against oracle.attention_forward / attention_backward at [1, 3, 300, 64] and a second,
     smaller shape: rel-L2 <= 1e-6 on O, dQ, dK, dV and |dL| <= 1e-5 -- about 40 times the fp32 rounding of the oracle's outputs
     measured at the first shape (2.5e-8 and 2.4e-7), to cover other seeds and shapes."""
     import oracle
