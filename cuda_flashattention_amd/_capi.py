@@ -57,6 +57,12 @@ SIGNATURES = {
     "fa2_forward_varlen_qk": (_i, [_vp] * 5 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
     "fa2_backward_varlen_qk_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "fa2_backward_varlen_qk": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "fa2_forward_sink": (_i, [_vp] * 6 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    "fa2_backward_sink_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "fa2_backward_sink": (_i, [_vp] * 11 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp, _i]),
+    "fa2_forward_varlen_sink": (_i, [_vp] * 6 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
+    "fa2_backward_varlen_sink_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "fa2_backward_varlen_sink": (_i, [_vp] * 11 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "fa2_backward_fused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fa2_backward_fused": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "fa2_backward_block": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),

@@ -9,6 +9,7 @@
 // order-dependent.  Here every gradient element is owned by exactly one wave:
 //
 //   kernel 0  fa2_bwd_delta      D[q] = sum_c dO[q][c] O[q][c]                (HBM-bound)
+//   kernel 0b fa2_bwd_dsink      (attention sinks only) dsink[h] = - sum_q exp(sink[h] - L[q]) D[q], one workgroup per head
 //   kernel 1  fa2_bwd_dq         row-parallel (the forward's mapping): a workgroup owns 256
 //                                query rows, streams K/V tiles, keeps dQ^T in accumulators
 //   kernel 2  fa2_bwd_dkdv       column-parallel: a workgroup owns 256 keys (a wave 32 of
@@ -79,6 +80,47 @@ __global__ void __launch_bounds__(256) fa2_bwd_delta_kernel(const __bf16* __rest
         RC[prow] = l == -INFINITY ? kNoKeyRC : -l * inv_scale;
         RC[rc_plane + prow] = -acc;
     }
+}
+
+// --------------------------------------------------------------------------- kernel 0b: the attention sinks' gradient
+// A sink is a (score s_h, value 0) column of every row of query head h (include/fa2_mi355x.h, fa2_backward_sink): dP_sink = 0,
+// so dS_sink = -P_sink D and dsink[h] = - sum over the batch and the rows of exp(s_h - L) D -- a reduction over the D plane
+// kernel 0 has just written, with the sink-inclusive L the forward stored.  One workgroup per query head: thread t adds the
+// rows t, t + 256, ... of the head's `batch` x `nq` rows in ascending order, then the 256 partial sums meet in a fixed tree
+// (fp32, no atomics: the same bits on every run).  Rows: L as the tensors lie (heads q_hs rows apart, pointer at row q_row0),
+// D in the dense plane.  s_h = -inf: no sink, dsink = 0.  A row without a key has L = s_h and D = 0 and adds nothing.
+__global__ void __launch_bounds__(256) fa2_bwd_dsink_kernel(const float* __restrict__ Dv, const float* __restrict__ L,
+                                                            const float* __restrict__ sink, float* __restrict__ dsink,
+                                                            int batch, int heads, int nq, int q_hs, int q_row0)
+{
+    __shared__ float part[256];
+    const int h = blockIdx.x, tid = threadIdx.x;
+    const float s = sink[h];
+    float acc = 0.0f;
+    if (s != -INFINITY) {
+        for (int b = 0; b < batch; ++b) {
+            const size_t row0 = ((size_t)b * heads + h) * (size_t)q_hs;
+#pragma unroll 8
+            for (int i = tid; i < nq; i += 256)      // (s - L first: the difference of two nearby values is exact to an ulp of itself)
+                acc -= __builtin_amdgcn_exp2f((s - L[row0 + i]) * kLog2e) * Dv[row0 + q_row0 + i];
+        }
+    }
+    part[tid] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int off = 128; off >= 1; off >>= 1) {
+        if (tid < off) part[tid] += part[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) dsink[h] = part[0];
+}
+
+static hipError_t launch_dsink(const SinkGrad& sg, const BwdArgs& a, int nq, hipStream_t stream)
+{
+    if (!sg.sink || !sg.dsink || sg.heads < 1 || a.BH % sg.heads != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fa2_bwd_dsink_kernel, dim3((unsigned)sg.heads), dim3(256), 0, stream, (const float*)a.D, a.L, sg.sink, sg.dsink,
+                       a.BH / sg.heads, sg.heads, nq, a.q_hs, a.q_row0);
+    return hipGetLastError();
 }
 
 // --------------------------------------------------------------------------- kernel 1: dQ
@@ -601,7 +643,7 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(60))) f
 
 // --------------------------------------------------------------------------- launch
 template <int D, bool CAUSAL>
-static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream)
+static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream, const SinkGrad* sg)
 {
     const size_t rows = (size_t)a.BH * a.Nq;
     hipError_t e = hipSuccess;
@@ -611,6 +653,7 @@ static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream)
                            (size_t)a.BH * a.q_hs, 1.0f / a.scale);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
+        if (sg && (e = launch_dsink(*sg, a, a.Nq, stream)) != hipSuccess) return e;
     }
     const int nb = (a.Nq + kBwdRows - 1) / kBwdRows;
     constexpr int lds_dq = 3 * 2 * kDqKV * D * 2;      // ring of three (K tile | V tile)
@@ -628,7 +671,7 @@ static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream)
 
 // Packed batches: D over the whole [H_q][T] tensors in one dense launch (no table), then the two table-driven kernels.
 template <int D, bool CAUSAL>
-static hipError_t launch_bwd_varlen_one(const VarlenBwdArgs& v, hipStream_t stream)
+static hipError_t launch_bwd_varlen_one(const VarlenBwdArgs& v, hipStream_t stream, const SinkGrad* sg)
 {
     const BwdArgs& a = v.a;
     const size_t rows = (size_t)a.BH * a.q_hs;
@@ -636,6 +679,7 @@ static hipError_t launch_bwd_varlen_one(const VarlenBwdArgs& v, hipStream_t stre
                        (const __bf16*)a.dO, (const __bf16*)a.O, a.L, a.D, a.RC, rows, a.q_hs, a.q_hs, 0, rows, 1.0f / a.scale);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (sg && (e = launch_dsink(*sg, a, a.q_hs, stream)) != hipSuccess) return e;      // the planes are [H_q][T_q], q_row0 = 0
     constexpr int lds_dq = 3 * 2 * kDqKV * D * 2;
     constexpr int lds_dk = kDkKeys * D * 2 + 2 * (2 * 2 * kDkQ * D * 2 + 512);
     e = launch_lds<fa2_bwd_dq_varlen_kernel<D, CAUSAL>>(dim3((unsigned)(v.n_row_items * a.BH)), dim3(256), lds_dq, stream, v);
@@ -644,21 +688,21 @@ static hipError_t launch_bwd_varlen_one(const VarlenBwdArgs& v, hipStream_t stre
                                                             stream, v);
 }
 
-hipError_t launch_bwd_varlen_bf16(const VarlenBwdArgs& v, hipStream_t stream)
+hipError_t launch_bwd_varlen_bf16(const VarlenBwdArgs& v, hipStream_t stream, const SinkGrad* sg)
 {
     const BwdArgs& a = v.a;
     if (a.kv_group < 1 || a.BH % a.kv_group != 0 || v.n_row_items < 1 || v.n_key_items < 1 || !v.row_items || !v.key_items)
         return hipErrorInvalidValue;
-    if (a.d == 128) return a.causal ? launch_bwd_varlen_one<128, true>(v, stream) : launch_bwd_varlen_one<128, false>(v, stream);
-    if (a.d == 64) return a.causal ? launch_bwd_varlen_one<64, true>(v, stream) : launch_bwd_varlen_one<64, false>(v, stream);
+    if (a.d == 128) return a.causal ? launch_bwd_varlen_one<128, true>(v, stream, sg) : launch_bwd_varlen_one<128, false>(v, stream, sg);
+    if (a.d == 64) return a.causal ? launch_bwd_varlen_one<64, true>(v, stream, sg) : launch_bwd_varlen_one<64, false>(v, stream, sg);
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream)
+hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream, const SinkGrad* sg)
 {
     if (a.kv_group < 1 || a.BH % a.kv_group != 0) return hipErrorInvalidValue;
-    if (a.d == 128) return a.causal ? launch_bwd_one<128, true>(a, stream) : launch_bwd_one<128, false>(a, stream);
-    if (a.d == 64) return a.causal ? launch_bwd_one<64, true>(a, stream) : launch_bwd_one<64, false>(a, stream);
+    if (a.d == 128) return a.causal ? launch_bwd_one<128, true>(a, stream, sg) : launch_bwd_one<128, false>(a, stream, sg);
+    if (a.d == 64) return a.causal ? launch_bwd_one<64, true>(a, stream, sg) : launch_bwd_one<64, false>(a, stream, sg);
     return hipErrorInvalidValue;
 }
 

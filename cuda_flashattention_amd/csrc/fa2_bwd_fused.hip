@@ -800,7 +800,8 @@ static hipError_t launch_chained_square(bool causal, bool ragged, dim3 grid, int
                   : launch_lds<fa2_bwd_fused_kernel<true, false, false, false, HD>>(grid, dim3(256), lds, stream, fa);
 }
 
-hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int mode, hipStream_t stream, float* rcpad, void* kvpart)
+hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int mode, hipStream_t stream, float* rcpad, void* kvpart,
+                                 const SinkGrad* sg)
 {
     const int npad = (a.Nk + 255) / 256 * 256;
     const bool ragged = npad != a.Nk;            // chained form only: needs `rcpad` (2 BH npad floats)
@@ -819,7 +820,7 @@ hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int m
     if (a.phases & 1) {
         BwdArgs d = a;
         d.phases = 1;
-        e = launch_bwd_bf16(d, stream);                   // D = rowsum(dO o O) and the row constants (kernel 0)
+        e = launch_bwd_bf16(d, stream, sg);               // D = rowsum(dO o O) and the row constants (kernel 0), the sinks' gradient
         if (e != hipSuccess) return e;
     }
     if (!(a.phases & 8)) return hipSuccess;

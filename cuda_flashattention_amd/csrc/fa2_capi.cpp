@@ -145,12 +145,13 @@ const char* fa2_status_string(int s)
 // (kv_len = 0: seq_len keys.  Another kv_len: the causal mask is aligned bottom-right, key j visible to query i iff
 // j <= i + kv_len - seq_len)
 static int forward_bf16(const void* Q, const void* K, const void* V, void* O, float* L, int B, int H, int kv_group, int seq_len,
-                        int head_dim, float softmax_scale, int causal, void* stream, int kv_len = 0)
+                        int head_dim, float softmax_scale, int causal, void* stream, int kv_len = 0, const float* sink = nullptr)
 {
     fa2::FwdArgs a{};
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L; a.Oacc = nullptr; a.M = nullptr;
     a.BH = B * H; a.Nq = seq_len; a.Nk = kv_len ? kv_len : seq_len; a.d = head_dim; a.scale = softmax_scale;
     a.causal = causal ? 1 : 0; a.causal_shift = causal ? a.Nk - a.Nq : 0; a.resume = 0; a.finalize = 1; a.kv_group = kv_group;
+    a.sink = sink; a.sink_heads = H;
     return hip_status(fa2::launch_fwd1_bf16(a, (hipStream_t)stream));
 }
 
@@ -250,6 +251,21 @@ int fa2_forward_qk(const void* Q, const void* K, const void* V, void* O, float* 
     return forward_bf16(Q, K, V, O, L, B, H_q, H_q / H_kv, q_len, head_dim, softmax_scale, causal, stream, kv_len);
 }
 
+// ---- attention sinks: the _qk problems with one learned logit per query head in every row's softmax (include/fa2_mi355x.h)
+int fa2_forward_sink(const void* Q, const void* K, const void* V, const float* sink, void* O, float* L,
+                     int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                     int dtype, int causal, void* stream)
+{
+    if (!Q || !K || !V || !sink || !O || !L) return FA2_ERR_NULL_POINTER;
+    int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
+    if (!st) st = check_common(B, H_q, kv_len, head_dim, softmax_scale);
+    if (st) return st;
+    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
+    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
+    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    return forward_bf16(Q, K, V, O, L, B, H_q, H_q / H_kv, q_len, head_dim, softmax_scale, causal, stream, kv_len, sink);
+}
+
 size_t fa2_varlen_plan_bytes_qk(int n_seqs, int total_q, int total_k)
 {
     if (n_seqs < 1 || total_q < 1 || total_k < 1) return 0;
@@ -306,7 +322,8 @@ int fa2_varlen_plan_build_qk(const int* cu_seqlens_q_host, const int* cu_seqlens
 // both packed forward entry points (one_list: fa2_forward_varlen, one T for both sides)
 static int forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
                           int H_q, int H_kv, int total_q, int total_k, bool one_list, int head_dim, float softmax_scale, int dtype,
-                          int causal, const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
+                          int causal, const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream,
+                          const float* sink = nullptr)
 {
     if (!Q || !K || !V || !O || !L || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
     int st = check_common(1, H_q, total_q, head_dim, softmax_scale);
@@ -322,6 +339,7 @@ static int forward_varlen(const void* Q, const void* K, const void* V, void* O, 
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L;
     a.BH = H_q; a.d = head_dim; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.finalize = 1;
     a.q_hs = total_q; a.k_hs = total_k; a.kv_group = H_q / H_kv;
+    a.sink = sink; a.sink_heads = H_q;
     v.items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
     v.n_items = h.n_row_items;
     return hip_status(fa2::launch_fwd1_varlen_bf16(v, (hipStream_t)stream));
@@ -341,6 +359,15 @@ int fa2_forward_varlen_qk(const void* Q, const void* K, const void* V, void* O, 
 {
     return forward_varlen(Q, K, V, O, L, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
                           plan_dev, plan_bytes, stream);
+}
+
+int fa2_forward_varlen_sink(const void* Q, const void* K, const void* V, const float* sink, void* O, float* L,
+                            int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                            const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
+{
+    if (!sink) return FA2_ERR_NULL_POINTER;
+    return forward_varlen(Q, K, V, O, L, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
+                          plan_dev, plan_bytes, stream, sink);
 }
 
 size_t fa2_forward_fp8_workspace_bytes(int B, int H, int seq_len, int head_dim)
@@ -557,7 +584,8 @@ static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int kv_
     return r;
 }
 
-static int bwd_launch(const Route& r, void* stream)
+// sg: the attention sinks and their gradient (fa2_backward_sink), computed with phase bit 0 on either bf16 path
+static int bwd_launch(const Route& r, void* stream, const fa2::SinkGrad* sg = nullptr)
 {
     const hipStream_t s = (hipStream_t)stream;
     const fa2::BwdArgs& a = r.args;
@@ -566,8 +594,8 @@ static int bwd_launch(const Route& r, void* stream)
         const hipError_t e = fa2::bwd_fused_clear_error(r.ws.ctl, s);
         if (e != hipSuccess) return hip_status(e);
     }
-    if (r.path == Path::single) return hip_status(fa2::launch_bwd_fused_bf16(a, r.ws.acc, r.ws.ctl, r.mode, s, r.ws.rcpad, r.ws.kvpart));
-    if (r.path == Path::two_kernel) return hip_status(fa2::launch_bwd_bf16(a, s));
+    if (r.path == Path::single) return hip_status(fa2::launch_bwd_fused_bf16(a, r.ws.acc, r.ws.ctl, r.mode, s, r.ws.rcpad, r.ws.kvpart, sg));
+    if (r.path == Path::two_kernel) return hip_status(fa2::launch_bwd_bf16(a, s, sg));
     const fa2::F32Args f{(const float*)a.Q, (const float*)a.K, (const float*)a.V, (float*)a.O, (float*)a.L, (const float*)a.dO,
                          (float*)a.dQ, (float*)a.dK, (float*)a.dV, a.D, a.BH, a.Nq, a.d, a.scale, a.causal, a.phases};
     return hip_status(fa2::launch_bwd_f32(f, s));
@@ -671,6 +699,22 @@ int fa2_backward_qk(const void* Q, const void* K, const void* V, const void* O, 
                                 dtype, causal, kv_len - q_len, softmax_scale, phases, workspace, workspace_bytes), stream);
 }
 
+size_t fa2_backward_sink_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, int dtype)
+{
+    return fa2_backward_qk_workspace_bytes(B, H_q, H_kv, q_len, kv_len, head_dim, dtype);
+}
+
+int fa2_backward_sink(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L, const void* dO,
+                      void* dQ, void* dK, void* dV, float* dsink,
+                      int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                      int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases)
+{
+    if (!sink || !dsink) return FA2_ERR_NULL_POINTER;
+    const fa2::SinkGrad sg{sink, dsink, H_q};
+    return bwd_launch(bwd_route(Entry::qk, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H_q, H_kv ? H_kv : -1, q_len, kv_len, 0, 0, 0, head_dim,
+                                dtype, causal, kv_len - q_len, softmax_scale, phases, workspace, workspace_bytes), stream, &sg);
+}
+
 // D [H_q][T] and the two row-constant planes, laid out as the front of every other backward workspace
 size_t fa2_backward_varlen_workspace_bytes(int H_q, int H_kv, int total_rows, int head_dim, int dtype)
 {
@@ -683,7 +727,7 @@ static int backward_varlen(const void* Q, const void* K, const void* V, const vo
                            void* dQ, void* dK, void* dV,
                            int H_q, int H_kv, int total_q, int total_k, bool one_list, int head_dim, float softmax_scale, int dtype,
                            int causal, const void* plan_host, const void* plan_dev, size_t plan_bytes,
-                           void* workspace, size_t workspace_bytes, void* stream)
+                           void* workspace, size_t workspace_bytes, void* stream, const fa2::SinkGrad* sg = nullptr)
 {
     if (!Q || !K || !V || !O || !L || !dO || !dQ || !dK || !dV || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
     int st = check_common(1, H_q, total_q, head_dim, softmax_scale);
@@ -705,7 +749,7 @@ static int backward_varlen(const void* Q, const void* K, const void* V, const vo
     const auto* items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
     v.row_items = items; v.n_row_items = h.n_row_items;
     v.key_items = items + h.n_row_items; v.n_key_items = h.n_key_items;
-    return hip_status(fa2::launch_bwd_varlen_bf16(v, (hipStream_t)stream));
+    return hip_status(fa2::launch_bwd_varlen_bf16(v, (hipStream_t)stream, sg));
 }
 
 int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
@@ -732,6 +776,23 @@ int fa2_backward_varlen_qk(const void* Q, const void* K, const void* V, const vo
 {
     return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
                            plan_dev, plan_bytes, workspace, workspace_bytes, stream);
+}
+
+size_t fa2_backward_varlen_sink_workspace_bytes(int H_q, int H_kv, int total_q, int total_k, int head_dim, int dtype)
+{
+    return fa2_backward_varlen_qk_workspace_bytes(H_q, H_kv, total_q, total_k, head_dim, dtype);
+}
+
+int fa2_backward_varlen_sink(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L,
+                             const void* dO, void* dQ, void* dK, void* dV, float* dsink,
+                             int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                             const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!sink || !dsink) return FA2_ERR_NULL_POINTER;
+    const fa2::SinkGrad sg{sink, dsink, H_q};
+    return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
+                           plan_dev, plan_bytes, workspace, workspace_bytes, stream, &sg);
 }
 
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,

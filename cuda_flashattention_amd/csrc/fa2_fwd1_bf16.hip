@@ -148,6 +148,9 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p, const int head, 
     // together on one XCD (K / V through its L2), as before.
     constexpr bool PAIRED = CAUSAL && !STATE;
     const int nrb = (p.Nq + kF1Rows - 1) / kF1Rows;
+    // the head's attention sink (the epilogue below): wave-uniform, one scalar load per head, in flight behind the first staging
+    float snk = -INFINITY;
+    if (p.sink) snk = p.sink[head % p.sink_heads];
 #pragma nounroll
     for (int half = 0; half < (PAIRED ? 2 : 1); ++half) {
     int rb = CAUSAL ? nrb - 1 - wi : wi;              // (not paired) heaviest row blocks first
@@ -431,12 +434,25 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p, const int head, 
     // ---- epilogue
     mfma_acc_settle();
     const bool fin = !STATE || p.finalize;
+    // The attention sink of the head (include/fa2_mi355x.h, fa2_forward_sink): a (score s, value 0) column that joins every
+    // row's softmax.  It never meets the main loop: with Lrow = m_run + ln l the row's log-sum-exp over its keys, the row ends
+    // with L' = logaddexp(Lrow, s) and O scaled by f = exp(Lrow - L') = sigmoid(Lrow - s).  Everything is formed from
+    // Lrow - s, never from s - m_run: m_run is a lagging reference after the rounds without maxima and -inf on a row
+    // without a key (there Lrow = -inf: L' = s, f = 0 beside inv = 0, no NaN).  s = -inf: no sink, nothing below runs.
+    // (snk: read at the top of the kernel, so that the load's latency is not paid once per row block here)
+    const bool sunk = fin && snk != -INFINITY;
     static_for<QBS>([&](auto QB) {
         constexpr int qb = decltype(QB)::value;
         const float l_tot = half_sum(vget<ST + 2 * qb>() + vget<ST + 2 * qb + 1>());
         const size_t qoff = (size_t)head * qhs + qrow[qb];
         const float pa = pend[qb];                 // an O rescale still pending from the last update (1 otherwise)
-        const float inv = (fin ? (l_tot > 0.0f ? 1.0f / l_tot : 0.0f) : 1.0f) * pa;
+        float inv = (fin ? (l_tot > 0.0f ? 1.0f / l_tot : 0.0f) : 1.0f) * pa;
+        float lse = m_run[qb] + __builtin_logf(l_tot);
+        if (sunk) {
+            const float lp = fmaxf(lse, snk) + __builtin_logf(1.0f + __builtin_amdgcn_exp2f(-fabsf(lse - snk) * kLog2e));
+            inv *= __builtin_amdgcn_exp2f((lse - lp) * kLog2e);
+            lse = lp;
+        }
         static_for<2 * DT>([&](auto G) {
             constexpr int dt = decltype(G)::value / 2, gp = decltype(G)::value % 2;
             constexpr int R = A_O + (qb * DT + dt) * 16 + 8 * gp;
@@ -452,7 +468,7 @@ __device__ __forceinline__ void fa2_fwd1_impl(const FwdArgs& p, const int head, 
         });
         if (qrow[qb] < Nq && h == 0) {
             if (fin) {
-                p.L[qoff] = m_run[qb] + __builtin_logf(l_tot);
+                p.L[qoff] = lse;
             } else {
                 p.L[qoff] = l_tot;
                 p.M[qoff] = m_run[qb];
@@ -544,6 +560,7 @@ hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream)
     // steps and of the packed launches: the pairs of row blocks balance a square's triangle only
     const bool state = a.resume || !a.finalize || (a.causal && a.causal_shift != 0);
     if (a.kv_group < 1 || a.BH % a.kv_group != 0) return hipErrorInvalidValue;
+    if (a.sink && (a.sink_heads < 1 || a.BH % a.sink_heads != 0 || !a.finalize)) return hipErrorInvalidValue;      // sinks: finalising launches only
     if (a.d == 128) {
         if (state) return a.causal ? launch_one1<128, true, true>(a, stream) : launch_one1<128, false, true>(a, stream);
         return a.causal ? launch_one1<128, true, false>(a, stream) : launch_one1<128, false, false>(a, stream);
@@ -568,6 +585,7 @@ static hipError_t launch_varlen1(const VarlenFwdArgs& v, hipStream_t stream)
 hipError_t launch_fwd1_varlen_bf16(const VarlenFwdArgs& v, hipStream_t stream)
 {
     if (v.a.kv_group < 1 || v.a.BH % v.a.kv_group != 0 || v.n_items < 1 || !v.items) return hipErrorInvalidValue;
+    if (v.a.sink && v.a.sink_heads != v.a.BH) return hipErrorInvalidValue;
     if (v.a.d == 128) return v.a.causal ? launch_varlen1<128, true>(v, stream) : launch_varlen1<128, false>(v, stream);
     if (v.a.d == 64) return v.a.causal ? launch_varlen1<64, true>(v, stream) : launch_varlen1<64, false>(v, stream);
     return hipErrorInvalidValue;

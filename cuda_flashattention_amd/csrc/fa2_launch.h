@@ -28,6 +28,8 @@ struct FwdArgs {
     int q_hs, k_hs;   // rows between consecutive heads of Q/O/Oacc/L/M and of K/V (0: Nq, Nk -- dense slabs).
                       // Larger strides address a row range of every head (the zig-zag chunks of the causal ring).
     int kv_group;     // query heads per K/V head (>= 1, divides the head count; 1 = multi-head attention)
+    const float* sink;   // [sink_heads] fp32 attention sinks (fa2_forward_sink) or nullptr; read by finalising launches only
+    int sink_heads;      // H_q: BH flattens the batch, head h of it reads sink[h % sink_heads]
 };
 
 hipError_t launch_fwd1_bf16(const FwdArgs& a, hipStream_t stream);     // generated main loop: one wave per SIMD (d = 128), two (d = 64)
@@ -87,7 +89,11 @@ struct BwdArgs {
                       // fa2_bwd_bf16.hip take it on any problem (rectangular, packed); the single kernel on dense square ones only
 };
 
-hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream);
+// The gradient of the attention sinks (fa2_backward_sink): dsink[h] = - sum over the batch and the rows of exp(sink[h] - L) D,
+// one more kernel behind kernel 0 (phase bit 0) over the D plane it wrote.  Handed BESIDE BwdArgs: no other kernel sees it.
+struct SinkGrad { const float* sink; float* dsink; int heads; };      // heads = H_q (BH = batch x heads)
+
+hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream, const SinkGrad* sg = nullptr);
 // The two-kernel backward over a packed variable-length batch.  a: the whole packed problem -- BH = H_q, q_hs = T_q, k_hs = T_k,
 // Nq = T_q for the D kernel (one dense launch over H_q x T_q rows), q_row0 / Nq / Nk / causal_shift per item in the other two;
 // D / RC dense [H_q][T_q] planes.
@@ -96,7 +102,7 @@ struct VarlenBwdArgs {
     const VarlenItem* row_items; const VarlenItem* key_items;      // DEVICE memory
     int n_row_items, n_key_items;
 };
-hipError_t launch_bwd_varlen_bf16(const VarlenBwdArgs& v, hipStream_t stream);
+hipError_t launch_bwd_varlen_bf16(const VarlenBwdArgs& v, hipStream_t stream, const SinkGrad* sg = nullptr);
 // Single-kernel five-product backward (fa2_bwd_fused.hip): d = 128 or 64, a dense square problem or (d = 128, mode 1) an unmasked
 // rectangular block; causal with mode 1 only.  Which problems come here: the routing rule at fa2_backward (include/fa2_mi355x.h),
 // applied by fa2_capi.cpp alone (device check included).
@@ -109,7 +115,7 @@ size_t bwd_fused_ctl_bytes(int BH, int N);
 // every K/V head, in ascending query-head order in fp32, into dK / dV.
 size_t bwd_fused_kvpart_bytes(int BH, int N, int d);
 hipError_t launch_bwd_fused_bf16(const BwdArgs& a, float* dQacc, int* ctl, int mode, hipStream_t stream, float* rcpad = nullptr,
-                                 void* kvpart = nullptr);
+                                 void* kvpart = nullptr, const SinkGrad* sg = nullptr);
 // Whether the current device has the layout the ordered hand-off (mode 1) was validated on; *why = a static sentence.
 bool bwd_fused_device_ok(const char** why);
 // Synchronises `stream` and reads the error word a chained launch leaves in its control block (non-zero: a bounded wait

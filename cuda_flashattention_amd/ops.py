@@ -84,6 +84,39 @@ def _rows(x, name, ref, B, H, N):
     return x
 
 
+def _sink_arg(sink, Q, heads_dim, name="sink"):
+    """An attention-sink tensor (or its gradient) beside Q ([B, H, N, d]: heads_dim 1; packed [H, T, d]: heads_dim 0), checked like
+    every other tensor the C ABI takes on trust: a contiguous fp32 device tensor of H_q elements on Q's device, and Q in bf16.
+    (A Q that is no tensor of that rank is the shape check's to refuse.)"""
+    if not isinstance(sink, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if not isinstance(Q, torch.Tensor) or Q.dim() != (4 if heads_dim else 3):
+        return sink
+    if Q.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: attention sinks are bf16 in this version, Q is {Q.dtype}")
+    H = Q.shape[heads_dim]
+    if sink.dtype != torch.float32:
+        raise ValueError(f"{name}: dtype {sink.dtype}, expected torch.float32 (the autograd ops also take a bf16 parameter)")
+    if sink.dim() != 1 or sink.numel() != H:
+        raise ValueError(f"{name}: shape {tuple(sink.shape)}, expected ({H},): one logit per query head")
+    if not sink.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (got stride {tuple(sink.stride())}; call .contiguous())")
+    if not sink.is_cuda:
+        raise ValueError(f"{name} must be a device tensor")
+    if sink.device != Q.device:
+        raise ValueError(f"{name} is on {sink.device}, expected {Q.device}")
+    return sink
+
+
+def _sink_param(sink):
+    """What the autograd ops call with: the fp32 copy of a bf16 or fp32 sink parameter (None stays None)."""
+    if sink is None:
+        return None
+    if not isinstance(sink, torch.Tensor) or sink.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"sink: a bf16 or fp32 tensor of H_q logits expected, got {sink.dtype if isinstance(sink, torch.Tensor) else type(sink)}")
+    return sink.detach().float().contiguous()
+
+
 def forward_fp8_workspace(B, H, N, d, device="cuda"):
     """Scratch for the fp8 forward (V transposed + key-norm maxima): allocate once, pass as workspace=."""
     return torch.empty(_capi.lib().fa2_forward_fp8_workspace_bytes(B, H, N, d), dtype=torch.uint8, device=device)
@@ -215,10 +248,14 @@ class _Attention(torch.autograd.Function):
         return dQ, dK, dV, None, None
 
 
-def attention(Q, K, V, softmax_scale=None, causal=False):
+def attention(Q, K, V, softmax_scale=None, causal=False, sink=None):
     """softmax(scale Q K^T [causal]) V for [B, H, N, d] bf16 (d = 64 | 128) or fp32 (non-causal) device tensors, with gradients.
     bf16 K and V may have fewer heads ([B, H_kv, N, d], H_kv dividing H: grouped-query attention); their gradients have their shape.
+    sink: attention sinks, a bf16 or fp32 tensor (a parameter) of H logits that join every row's softmax (attention_qk; bf16
+    [B, H, N, d] tensors only), with its gradient.
     A convenience for callers that live in torch autograd; tests and bench.py call the two halves directly."""
+    if sink is not None:
+        return attention_qk(Q, K, V, softmax_scale, causal, sink=sink)
     return _Attention.apply(Q, K, V, softmax_scale, causal)
 
 
@@ -244,15 +281,25 @@ def _qk_shapes(Q, K, V):
     return B, H, Hkv, Nq, Nk, d
 
 
-def flash_attention_2_qk_forward(Q, K, V, softmax_scale=None, causal=False, O=None, L=None, stream=None):
+def flash_attention_2_qk_forward(Q, K, V, softmax_scale=None, causal=False, O=None, L=None, stream=None, sink=None):
     """O, L = FA2 forward of N_q queries against N_k keys (fa2_forward_qk): Q [B, H, N_q, d], K and V [B, H_kv, N_k, d] (H_kv
     dividing H), bf16, d = 64 | 128.  Cross-attention, or (causal) a prompt chunk against a longer contiguous KV cache: the mask
     is aligned bottom-right, key j visible to query i iff j <= i + N_k - N_q.  A query row that sees no key (causal, N_q > N_k)
-    has O = 0 and L = -inf.  With N_q == N_k this is flash_attention_2_forward, bit for bit."""
+    has O = 0 and L = -inf.  With N_q == N_k this is flash_attention_2_forward, bit for bit.
+    sink (fa2_forward_sink): fp32 [H] device tensor of attention sinks, one logit per query head in natural units that joins every
+    row's softmax and carries no value: L = log(exp(sink) + sum exp S), O = sum exp(S - L) v; -inf = no sink for that head; a
+    row without a key then has L = sink."""
+    if sink is not None:
+        _sink_arg(sink, Q, 1)
     B, H, Hkv, Nq, Nk, d = _qk_shapes(Q, K, V)
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
     O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
     L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
+    if sink is not None:
+        st = _capi.lib().fa2_forward_sink(Q.data_ptr(), K.data_ptr(), V.data_ptr(), sink.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, Hkv,
+                                          Nq, Nk, d, scale, FA2_DTYPE_BF16, 1 if causal else 0, _stream_ptr(stream))
+        check(st, "fa2_forward_sink")
+        return O, L
     st = _capi.lib().fa2_forward_qk(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Nk, d, scale,
                                     FA2_DTYPE_BF16, 1 if causal else 0, _stream_ptr(stream))
     check(st, "fa2_forward_qk")
@@ -260,10 +307,18 @@ def flash_attention_2_qk_forward(Q, K, V, softmax_scale=None, causal=False, O=No
 
 
 def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=False,
-                                  dQ=None, dK=None, dV=None, workspace=None, stream=None, phases=7):
+                                  dQ=None, dK=None, dV=None, workspace=None, stream=None, phases=7, sink=None, dsink=None):
     """dQ, dK, dV = FA2 backward of flash_attention_2_qk_forward (fa2_backward_qk): dO like O, dK / dV like K / V.  N_q != N_k
     runs the two deterministic kernels (phases: 1 = D and the row constants, 2 = dQ, 4 = dK/dV; 8, the single kernel, is
-    refused); N_q == N_k is flash_attention_2_backward.  A row that saw no key gets dQ = 0."""
+    refused); N_q == N_k is flash_attention_2_backward.  A row that saw no key gets dQ = 0.
+    sink (fa2_backward_sink): the forward's sinks, with its O and L; returns (dQ, dK, dV, dsink), dsink fp32 [H] (written with
+    phase bit 0)."""
+    if sink is not None:
+        _sink_arg(sink, Q, 1)
+        if dsink is not None:
+            _sink_arg(dsink, Q, 1, "dsink")
+    elif dsink is not None:
+        raise ValueError("dsink belongs to a call with sink=")
     B, H, Hkv, Nq, Nk, d = _qk_shapes(Q, K, V)
     for n, t in (("O", O), ("dO", dO)):
         _like(t, n, Q, (B, H, Nq, d), Q.dtype)
@@ -277,6 +332,14 @@ def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=
         workspace = torch.empty(lib.fa2_backward_qk_workspace_bytes(B, H, Hkv, Nq, Nk, d, FA2_DTYPE_BF16), dtype=torch.uint8, device=Q.device)
     if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
         raise ValueError("workspace must be a contiguous device tensor on Q's device")
+    if sink is not None:
+        dsink = torch.empty(H, dtype=torch.float32, device=Q.device) if dsink is None else dsink
+        st = lib.fa2_backward_sink(Q.data_ptr(), K.data_ptr(), V.data_ptr(), sink.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
+                                   dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), dsink.data_ptr(), B, H, Hkv, Nq, Nk, d, scale,
+                                   FA2_DTYPE_BF16, 1 if causal else 0, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                   _stream_ptr(stream), int(phases))
+        check(st, "fa2_backward_sink")
+        return dQ, dK, dV, dsink
     st = lib.fa2_backward_qk(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
                              dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, H, Hkv, Nq, Nk, d, scale, FA2_DTYPE_BF16,
                              1 if causal else 0, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
@@ -289,25 +352,31 @@ class _AttentionQK(torch.autograd.Function):
     """flash_attention_2_qk_forward / _backward as one differentiable op (as _Attention)."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, softmax_scale, causal):
+    def forward(ctx, Q, K, V, softmax_scale, causal, sink=None):
         Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
         scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
-        O, L = flash_attention_2_qk_forward(Q, K, V, scale, causal=causal)
-        ctx.save_for_backward(Q, K, V, O, L)
-        ctx.scale, ctx.causal = scale, bool(causal)
+        s32 = _sink_param(sink)                      # the kernels read fp32 sinks; the parameter may be bf16
+        O, L = flash_attention_2_qk_forward(Q, K, V, scale, causal=causal, sink=s32)
+        ctx.save_for_backward(Q, K, V, O, L, s32)
+        ctx.scale, ctx.causal, ctx.sink_dtype = scale, bool(causal), None if sink is None else sink.dtype
         return O
 
     @staticmethod
     def backward(ctx, dO):
-        Q, K, V, O, L = ctx.saved_tensors
-        dQ, dK, dV = flash_attention_2_qk_backward(Q, K, V, O, L, dO.contiguous(), ctx.scale, causal=ctx.causal)
-        return dQ, dK, dV, None, None
+        Q, K, V, O, L, s32 = ctx.saved_tensors
+        if s32 is None:
+            dQ, dK, dV = flash_attention_2_qk_backward(Q, K, V, O, L, dO.contiguous(), ctx.scale, causal=ctx.causal)
+            return dQ, dK, dV, None, None, None
+        dQ, dK, dV, dsink = flash_attention_2_qk_backward(Q, K, V, O, L, dO.contiguous(), ctx.scale, causal=ctx.causal, sink=s32)
+        return dQ, dK, dV, None, None, dsink.to(ctx.sink_dtype)
 
 
-def attention_qk(Q, K, V, softmax_scale=None, causal=False):
+def attention_qk(Q, K, V, softmax_scale=None, causal=False, sink=None):
     """attention() for N_q queries against N_k keys: Q [B, H, N_q, d], K and V [B, H_kv, N_k, d] bf16 device tensors (d = 64 | 128,
-    H_kv dividing H); causal: bottom-right aligned (the last query sees every key).  With gradients, shaped like K and V."""
-    return _AttentionQK.apply(Q, K, V, softmax_scale, causal)
+    H_kv dividing H); causal: bottom-right aligned (the last query sees every key).  With gradients, shaped like K and V.
+    sink: attention sinks, a bf16 or fp32 tensor (a parameter) of H logits (flash_attention_2_qk_forward); its gradient comes
+    back in its dtype."""
+    return _AttentionQK.apply(Q, K, V, softmax_scale, causal, sink)
 
 
 class VarlenPlan:
@@ -442,19 +511,24 @@ def _packed(x, name, ref, shape):
     return x
 
 
-def flash_attention_2_varlen_forward(Q, K, V, plan, softmax_scale=None, causal=False, O=None, L=None, stream=None):
+def flash_attention_2_varlen_forward(Q, K, V, plan, softmax_scale=None, causal=False, O=None, L=None, stream=None, sink=None):
     """O, L = FA2 forward over a packed variable-length batch (fa2_forward_varlen): Q [H, T, d], K and V [H_kv, T, d] (H_kv
     dividing H), bf16, d = 64 | 128; sequence i owns rows plan.cu_seqlens[i] : plan.cu_seqlens[i+1] of every head and attends only
     itself (causal: within itself).  L is fp32 [H, T].  A [T, H, d] tensor must be transposed (and made contiguous) first.
     Under a two-sided plan (VarlenPlan(cu_seqlens, cu_seqlens_k); fa2_forward_varlen_qk) K and V are [H_kv, T_k, d] and sequence i
-    attends its own key rows, causal: bottom-right aligned; a query row that sees no key has O = 0 and L = -inf."""
+    attends its own key rows, causal: bottom-right aligned; a query row that sees no key has O = 0 and L = -inf.
+    sink (fa2_forward_varlen_sink, either kind of plan): fp32 [H] attention sinks, as in flash_attention_2_qk_forward."""
+    if sink is not None:
+        _sink_arg(sink, Q, 0)
     H, Hkv, T, Tk, d = _varlen_shapes(Q, K, V, plan)
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
     O = torch.empty_like(Q) if O is None else _packed(O, "O", Q, (H, T, d))
     L = torch.empty(H, T, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, 1, H, T)
     lib, ptrs = _capi.lib(), (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr())
     tail = (d, scale, FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(), plan.nbytes, _stream_ptr(stream))
-    if plan.two_sided:
+    if sink is not None:
+        check(lib.fa2_forward_varlen_sink(*ptrs[:3], sink.data_ptr(), *ptrs[3:], H, Hkv, T, Tk, *tail), "fa2_forward_varlen_sink")
+    elif plan.two_sided:
         check(lib.fa2_forward_varlen_qk(*ptrs, H, Hkv, T, Tk, *tail), "fa2_forward_varlen_qk")
     else:
         check(lib.fa2_forward_varlen(*ptrs, H, Hkv, T, *tail), "fa2_forward_varlen")
@@ -462,11 +536,18 @@ def flash_attention_2_varlen_forward(Q, K, V, plan, softmax_scale=None, causal=F
 
 
 def flash_attention_2_varlen_backward(Q, K, V, O, L, dO, plan, softmax_scale=None, causal=False,
-                                      dQ=None, dK=None, dV=None, workspace=None, stream=None):
+                                      dQ=None, dK=None, dV=None, workspace=None, stream=None, sink=None, dsink=None):
     """dQ, dK, dV = FA2 backward over a packed variable-length batch (fa2_backward_varlen; the two deterministic kernels): the
     tensors of flash_attention_2_varlen_forward, dO like O, dK / dV like K / V.  workspace: a uint8 device tensor of
     fa2_backward_varlen_workspace_bytes (allocated per call when omitted -- pass one for graph capture).  Under a two-sided plan
-    (fa2_backward_varlen_qk) dK / dV are [H_kv, T_k, d]; a sequence with keys and no queries gets dK = dV = 0."""
+    (fa2_backward_varlen_qk) dK / dV are [H_kv, T_k, d]; a sequence with keys and no queries gets dK = dV = 0.
+    sink (fa2_backward_varlen_sink): the forward's sinks, with its O and L; returns (dQ, dK, dV, dsink), dsink fp32 [H]."""
+    if sink is not None:
+        _sink_arg(sink, Q, 0)
+        if dsink is not None:
+            _sink_arg(dsink, Q, 0, "dsink")
+    elif dsink is not None:
+        raise ValueError("dsink belongs to a call with sink=")
     H, Hkv, T, Tk, d = _varlen_shapes(Q, K, V, plan)
     for n, t in (("O", O), ("dO", dO)):
         _packed(t, n, Q, (H, T, d))
@@ -483,6 +564,11 @@ def flash_attention_2_varlen_backward(Q, K, V, O, L, dO, plan, softmax_scale=Non
     ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr())
     tail = (d, scale, FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(), plan.nbytes,
             workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr(stream))
+    if sink is not None:
+        dsink = torch.empty(H, dtype=torch.float32, device=Q.device) if dsink is None else dsink
+        check(lib.fa2_backward_varlen_sink(*ptrs[:3], sink.data_ptr(), *ptrs[3:], dsink.data_ptr(), H, Hkv, T, Tk, *tail),
+              "fa2_backward_varlen_sink")
+        return dQ, dK, dV, dsink
     if plan.two_sided:
         check(lib.fa2_backward_varlen_qk(*ptrs, H, Hkv, T, Tk, *tail), "fa2_backward_varlen_qk")
     else:
@@ -494,26 +580,31 @@ class _AttentionVarlen(torch.autograd.Function):
     """flash_attention_2_varlen_forward / _backward as one differentiable op (as _Attention)."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, plan, softmax_scale, causal):
+    def forward(ctx, Q, K, V, plan, softmax_scale, causal, sink=None):
         Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
         scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
-        O, L = flash_attention_2_varlen_forward(Q, K, V, plan, scale, causal=causal)
-        ctx.save_for_backward(Q, K, V, O, L)
-        ctx.plan, ctx.scale, ctx.causal = plan, scale, bool(causal)
+        s32 = _sink_param(sink)
+        O, L = flash_attention_2_varlen_forward(Q, K, V, plan, scale, causal=causal, sink=s32)
+        ctx.save_for_backward(Q, K, V, O, L, s32)
+        ctx.plan, ctx.scale, ctx.causal, ctx.sink_dtype = plan, scale, bool(causal), None if sink is None else sink.dtype
         return O
 
     @staticmethod
     def backward(ctx, dO):
-        Q, K, V, O, L = ctx.saved_tensors
-        dQ, dK, dV = flash_attention_2_varlen_backward(Q, K, V, O, L, dO.contiguous(), ctx.plan, ctx.scale, causal=ctx.causal)
-        return dQ, dK, dV, None, None, None
+        Q, K, V, O, L, s32 = ctx.saved_tensors
+        if s32 is None:
+            dQ, dK, dV = flash_attention_2_varlen_backward(Q, K, V, O, L, dO.contiguous(), ctx.plan, ctx.scale, causal=ctx.causal)
+            return dQ, dK, dV, None, None, None, None
+        dQ, dK, dV, dsink = flash_attention_2_varlen_backward(Q, K, V, O, L, dO.contiguous(), ctx.plan, ctx.scale, causal=ctx.causal,
+                                                              sink=s32)
+        return dQ, dK, dV, None, None, None, dsink.to(ctx.sink_dtype)
 
 
-def attention_varlen(Q, K, V, plan, softmax_scale=None, causal=False):
+def attention_varlen(Q, K, V, plan, softmax_scale=None, causal=False, sink=None):
     """attention() over a packed variable-length batch: Q [H, T, d], K and V [H_kv, T, d] bf16 device tensors (d = 64 | 128, H_kv
     dividing H), plan a VarlenPlan of the batch's cu_seqlens; every sequence attends itself only.  With gradients.  Under a
-    two-sided plan K and V are [H_kv, T_k, d] and so are their gradients."""
-    return _AttentionVarlen.apply(Q, K, V, plan, softmax_scale, causal)
+    two-sided plan K and V are [H_kv, T_k, d] and so are their gradients.  sink: attention sinks, as in attention_qk."""
+    return _AttentionVarlen.apply(Q, K, V, plan, softmax_scale, causal, sink)
 
 
 def read_clocks(stream=None):

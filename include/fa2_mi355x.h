@@ -315,6 +315,51 @@ int fa2_backward_varlen_qk(const void* Q, const void* K, const void* V, const vo
                            const void* plan_host, const void* plan_dev, size_t plan_bytes,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Attention sinks: one learned logit per query head that joins every row's softmax and carries no value (GPT-OSS, the
+ * StreamingLLM line).  bf16, head_dim 64 or 128, every problem of the _qk calls above (square, rectangular, grouped, dense and
+ * packed); the signatures are theirs with `sink` after V and `dsink` after dV.
+ * DEFINITION.  sink is fp32 [H_q] in DEVICE memory, in natural units: it is NOT multiplied by softmax_scale.  For every (batch,
+ * query head h, row i), with S_ij = softmax_scale q_i . k_j over the keys j visible to row i and s_h = sink[h]:
+ *     L_i = log(exp(s_h) + sum_j exp S_ij),    P_ij = exp(S_ij - L_i),    O_i = sum_j P_ij v_j
+ * -- the row's probabilities sum to 1 - exp(s_h - L_i), the rest stays with the sink.  L is the sink-INCLUSIVE log-sum-exp.
+ * sink[h] = -inf means "no sink for this head": O, L, dQ, dK, dV of that head are bit for bit those of the calls without a
+ * sink, and dsink[h] = 0.  A ROW THAT SEES NO KEY (causal with q_len > kv_len, a packed sequence without keys) has O = 0, dQ = 0
+ * and L = s_h (-inf only if s_h = -inf); it adds nothing to dsink.  +inf and NaN in sink are the caller's error; the values live
+ * in device memory and are not checked.
+ * FORWARD: the kernels of fa2_forward_qk / fa2_forward_varlen_qk; the sink never meets their main loop.  A finished row has
+ * Lrow = its log-sum-exp over the keys; the epilogue stores L' = max(Lrow, s) + log1p(exp(-|Lrow - s|)) and scales O by
+ * exp(Lrow - L') = sigmoid(Lrow - s).
+ * BACKWARD: the kernels of fa2_backward_qk / fa2_backward_varlen_qk, unchanged -- handed the sink-inclusive L and the sink-scaled
+ * O they form P = exp(S - L) and D = rowsum(dO o O) (the sink's value is 0: dP_sink = 0) and with them the right dQ, dK, dV.
+ * Routing, `phases`, the workspace (fa2_backward_sink_workspace_bytes = fa2_backward_qk_workspace_bytes, the packed one
+ * likewise) and fa2_backward_status are those of fa2_backward_qk, the single kernel included where it takes the shape.
+ * dsink[h] = - sum over the batch and the rows of exp(s_h - L_row) D_row (fp32 [H_q], DEVICE memory) is written by one more
+ * kernel that runs with PHASE BIT 0, behind the D kernel, over the D plane in the workspace: a call without bit 0 leaves dsink
+ * as it is.  DETERMINISTIC: one workgroup per query head, a fixed summation order, no floating-point atomics.  Nothing is
+ * allocated and nothing synchronises: the calls may be captured in a graph.
+ * STATUS CODES: a NULL sink or dsink (like every other NULL tensor) -> FA2_ERR_NULL_POINTER; then those of the _qk calls in
+ * their order, fp32 and fp8 -> FA2_ERR_UNSUPPORTED_DTYPE.  fa2_forward_varlen_sink / fa2_backward_varlen_sink take both kinds of
+ * plan; a one-list plan requires total_k == total_q.
+ * NOT COVERED: the resumable forward steps and fa2_forward_state_finalize (no sink argument: a ring schedule finalises without
+ * one), the ring, fp8 and fp32 (cuda_flashattention_amd.ops raises ValueError for a sink beside tensors that are not bf16). */
+int fa2_forward_sink(const void* Q, const void* K, const void* V, const float* sink, void* O, float* L,
+                     int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                     int dtype, int causal, void* stream);
+size_t fa2_backward_sink_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, int dtype);
+int fa2_backward_sink(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L, const void* dO,
+                      void* dQ, void* dK, void* dV, float* dsink,
+                      int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                      int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases);
+int fa2_forward_varlen_sink(const void* Q, const void* K, const void* V, const float* sink, void* O, float* L,
+                            int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                            const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream);
+size_t fa2_backward_varlen_sink_workspace_bytes(int H_q, int H_kv, int total_q, int total_k, int head_dim, int dtype);
+int fa2_backward_varlen_sink(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L,
+                             const void* dO, void* dQ, void* dK, void* dV, float* dsink,
+                             int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                             const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output
  * pass (FA2_ERR_UNSUPPORTED for shapes or devices it does not take, and in combination with bits 1 or 2).  7 = fa2_backward (which picks the implementation);
