@@ -63,6 +63,10 @@ SIGNATURES = {
     "fa2_forward_varlen_sink": (_i, [_vp] * 6 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
     "fa2_backward_varlen_sink_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "fa2_backward_varlen_sink": (_i, [_vp] * 11 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "fa2_backward_lse": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp, _i]),
+    "fa2_backward_varlen_lse": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "fa2_merge_states": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _i, _i, _vp]),
+    "fa2_merge_states_backward": (_i, [_vp] * 8 + [_i, _sz, _i, _i, _vp]),
     "fa2_backward_fused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fa2_backward_fused": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "fa2_backward_block": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),

@@ -49,10 +49,14 @@ namespace fa2 {
 constexpr float kNoKeyRC = -1.0e30f;       // RC[0] of a row without a visible key
 constexpr float kNoKeyLq = 1.0e30f;        // and what the dQ kernel subtracts from its scores in place of L log2 e
 
+// A gradient of L (fa2_backward_lse): dL/dS_ij = P_ij, so dS = P o (dP - D + dL) -- the row constant becomes D' = D - dL and
+// every consumer of D and RC[1] (the dQ and dK/dV kernels, the single kernel, the sinks' gradient: dL/dsink = exp(sink - L))
+// is right as it stands.  dL is addressed like L; nullptr: a uniform branch, the stores of a call without it.  A row with
+// L = -inf has no P to carry a gradient: its dL is dropped by a select, so that a NaN or an Inf there reaches nothing.
 template <int D>
 __global__ void __launch_bounds__(256) fa2_bwd_delta_kernel(const __bf16* __restrict__ dO,
                                                             const __bf16* __restrict__ O,
-                                                            const float* __restrict__ L,
+                                                            const float* __restrict__ L, const float* __restrict__ dL,
                                                             float* __restrict__ Dv, float* __restrict__ RC,
                                                             size_t rows, int nq, int q_hs, int q_row0, size_t rc_plane,
                                                             float inv_scale)
@@ -75,8 +79,12 @@ __global__ void __launch_bounds__(256) fa2_bwd_delta_kernel(const __bf16* __rest
 #pragma unroll
     for (int off = 8; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 16);
     if (r < rows && sub == 0) {
-        Dv[prow] = acc;
         const float l = L[row];
+        if (dL) {
+            const float g = dL[row];
+            acc -= l == -INFINITY ? 0.0f : g;
+        }
+        Dv[prow] = acc;
         RC[prow] = l == -INFINITY ? kNoKeyRC : -l * inv_scale;
         RC[rc_plane + prow] = -acc;
     }
@@ -649,11 +657,11 @@ static hipError_t launch_bwd_one(const BwdArgs& a, hipStream_t stream, const Sin
     hipError_t e = hipSuccess;
     if (a.phases & 1) {
         hipLaunchKernelGGL((fa2_bwd_delta_kernel<D>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0,
-                           stream, (const __bf16*)a.dO, (const __bf16*)a.O, a.L, a.D, a.RC, rows, a.Nq, a.q_hs, a.q_row0,
-                           (size_t)a.BH * a.q_hs, 1.0f / a.scale);
+                           stream, (const __bf16*)a.dO, (const __bf16*)a.O, a.L, sg ? sg->dL : nullptr, a.D, a.RC, rows, a.Nq, a.q_hs,
+                           a.q_row0, (size_t)a.BH * a.q_hs, 1.0f / a.scale);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        if (sg && (e = launch_dsink(*sg, a, a.Nq, stream)) != hipSuccess) return e;
+        if (sg && sg->sink && (e = launch_dsink(*sg, a, a.Nq, stream)) != hipSuccess) return e;
     }
     const int nb = (a.Nq + kBwdRows - 1) / kBwdRows;
     constexpr int lds_dq = 3 * 2 * kDqKV * D * 2;      // ring of three (K tile | V tile)
@@ -676,10 +684,11 @@ static hipError_t launch_bwd_varlen_one(const VarlenBwdArgs& v, hipStream_t stre
     const BwdArgs& a = v.a;
     const size_t rows = (size_t)a.BH * a.q_hs;
     hipLaunchKernelGGL((fa2_bwd_delta_kernel<D>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, stream,
-                       (const __bf16*)a.dO, (const __bf16*)a.O, a.L, a.D, a.RC, rows, a.q_hs, a.q_hs, 0, rows, 1.0f / a.scale);
+                       (const __bf16*)a.dO, (const __bf16*)a.O, a.L, sg ? sg->dL : nullptr, a.D, a.RC, rows, a.q_hs, a.q_hs, 0, rows,
+                       1.0f / a.scale);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (sg && (e = launch_dsink(*sg, a, a.q_hs, stream)) != hipSuccess) return e;      // the planes are [H_q][T_q], q_row0 = 0
+    if (sg && sg->sink && (e = launch_dsink(*sg, a, a.q_hs, stream)) != hipSuccess) return e;      // the planes are [H_q][T_q], q_row0 = 0
     constexpr int lds_dq = 3 * 2 * kDqKV * D * 2;
     constexpr int lds_dk = kDkKeys * D * 2 + 2 * (2 * 2 * kDkQ * D * 2 + 512);
     e = launch_lds<fa2_bwd_dq_varlen_kernel<D, CAUSAL>>(dim3((unsigned)(v.n_row_items * a.BH)), dim3(256), lds_dq, stream, v);

@@ -715,6 +715,19 @@ int fa2_backward_sink(const void* Q, const void* K, const void* V, const float* 
                                 dtype, causal, kv_len - q_len, softmax_scale, phases, workspace, workspace_bytes), stream, &sg);
 }
 
+// fa2_backward_qk / fa2_backward_sink with a gradient for L (kernel 0 alone reads it, with phase bit 0)
+int fa2_backward_lse(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L, const void* dO,
+                     const float* dL, void* dQ, void* dK, void* dV, float* dsink,
+                     int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                     int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases)
+{
+    if (!sink != !dsink) return FA2_ERR_NULL_POINTER;
+    const fa2::SinkGrad sg{sink, dsink, H_q, dL};
+    return bwd_launch(bwd_route(Entry::qk, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H_q, H_kv ? H_kv : -1, q_len, kv_len, 0, 0, 0, head_dim,
+                                dtype, causal, kv_len - q_len, softmax_scale, phases, workspace, workspace_bytes), stream,
+                      sink || dL ? &sg : nullptr);
+}
+
 // D [H_q][T] and the two row-constant planes, laid out as the front of every other backward workspace
 size_t fa2_backward_varlen_workspace_bytes(int H_q, int H_kv, int total_rows, int head_dim, int dtype)
 {
@@ -793,6 +806,60 @@ int fa2_backward_varlen_sink(const void* Q, const void* K, const void* V, const 
     const fa2::SinkGrad sg{sink, dsink, H_q};
     return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
                            plan_dev, plan_bytes, workspace, workspace_bytes, stream, &sg);
+}
+
+int fa2_backward_varlen_lse(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L,
+                            const void* dO, const float* dL, void* dQ, void* dK, void* dV, float* dsink,
+                            int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                            const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                            void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!sink != !dsink) return FA2_ERR_NULL_POINTER;
+    const fa2::SinkGrad sg{sink, dsink, H_q, dL};
+    return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
+                           plan_dev, plan_bytes, workspace, workspace_bytes, stream, sink || dL ? &sg : nullptr);
+}
+
+// ---- merging partial results (include/fa2_mi355x.h): argument checks, then the part pointers by value into the kernels
+static int merge_check(const void* const* O_parts, const float* const* L_parts, int n_parts, size_t rows, int head_dim, int dtype)
+{
+    if (!O_parts || !L_parts) return FA2_ERR_NULL_POINTER;
+    if (n_parts < 1 || n_parts > fa2::kMergeMaxParts || rows == 0) return FA2_ERR_INVALID_SHAPE;
+    for (int i = 0; i < n_parts; ++i)
+        if (!O_parts[i] || !L_parts[i]) return FA2_ERR_NULL_POINTER;
+    if (rows > (size_t)0x7fffffff * 8) return FA2_ERR_INVALID_SHAPE;      // the grid: one workgroup per 16 or 32 rows
+    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
+    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    return FA2_OK;
+}
+
+int fa2_merge_states(const void* const* O_parts, const float* const* L_parts, int n_parts, void* O, float* L, size_t rows,
+                     int head_dim, int dtype, void* stream)
+{
+    if (!O || !L) return FA2_ERR_NULL_POINTER;
+    const int st = merge_check(O_parts, L_parts, n_parts, rows, head_dim, dtype);
+    if (st) return st;
+    fa2::MergeArgs a{};
+    for (int i = 0; i < n_parts; ++i) { a.O[i] = O_parts[i]; a.L[i] = L_parts[i]; }
+    a.n = n_parts; a.Oout = O; a.Lout = L; a.rows = rows;
+    return hip_status(fa2::launch_merge_fwd(a, head_dim, (hipStream_t)stream));
+}
+
+int fa2_merge_states_backward(const void* const* O_parts, const float* const* L_parts, const void* O, const float* L, const void* dO,
+                              const float* dL, void* const* dO_parts, float* const* dL_parts, int n_parts, size_t rows, int head_dim,
+                              int dtype, void* stream)
+{
+    if (!O || !L || !dO || !dO_parts || !dL_parts) return FA2_ERR_NULL_POINTER;
+    const int st = merge_check(O_parts, L_parts, n_parts, rows, head_dim, dtype);
+    if (st) return st;
+    fa2::MergeBwdArgs b{};
+    for (int i = 0; i < n_parts; ++i) {
+        if (!dO_parts[i] || !dL_parts[i]) return FA2_ERR_NULL_POINTER;
+        b.m.O[i] = O_parts[i]; b.m.L[i] = L_parts[i]; b.dO_parts[i] = dO_parts[i]; b.dL_parts[i] = dL_parts[i];
+    }
+    b.m.n = n_parts; b.m.Oout = const_cast<void*>(O); b.m.Lout = const_cast<float*>(L); b.m.rows = rows;
+    b.dO = dO; b.dL = dL;
+    return hip_status(fa2::launch_merge_bwd(b, head_dim, (hipStream_t)stream));
 }
 
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,

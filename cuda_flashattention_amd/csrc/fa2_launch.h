@@ -54,6 +54,23 @@ hipError_t launch_accumulate_bf16(float* acc, const void* src, size_t rows, size
 // Ring epilogue: O = bf16(Oacc / l), L = m + ln l for `rows` consecutive rows (l arrives in L).
 hipError_t launch_finalize_state(const float* Oacc, const float* M, float* L, void* O, size_t rows, int d, hipStream_t stream);
 
+// Merging partial attention results (fa2_merge.hip; fa2_merge_states): n parts (O_i bf16 [rows][d], L_i fp32 [rows]) over disjoint
+// key sets -> the attention over their union.  The part pointers travel BY VALUE in the kernel's argument block.
+constexpr int kMergeMaxParts = 8;
+struct MergeArgs {
+    const void* O[kMergeMaxParts]; const float* L[kMergeMaxParts];      // entries [n, 8) are never read
+    int n;
+    void* Oout; float* Lout;      // the merged O and L: written by the forward, read by the backward
+    size_t rows;
+};
+struct MergeBwdArgs {
+    MergeArgs m;
+    const void* dO; const float* dL;      // dL may be nullptr (= 0)
+    void* dO_parts[kMergeMaxParts]; float* dL_parts[kMergeMaxParts];
+};
+hipError_t launch_merge_fwd(const MergeArgs& a, int d, hipStream_t stream);        // d = 64 | 128
+hipError_t launch_merge_bwd(const MergeBwdArgs& b, int d, hipStream_t stream);
+
 // fp8 (OCP e4m3) forward, d = 128: Q, K, V fp8 [BH][N][128]; O bf16; Vt: [BH][128][Npad] fp8 scratch the
 // launcher fills with V transposed (Npad = N rounded up to 64); kn: [BH][Npad / 64] fp32 scratch it fills with the largest
 // |k| of every 64 keys (fa2_fwd_fp8.hip: where the softmax needs no lane maxima).
@@ -91,7 +108,9 @@ struct BwdArgs {
 
 // The gradient of the attention sinks (fa2_backward_sink): dsink[h] = - sum over the batch and the rows of exp(sink[h] - L) D,
 // one more kernel behind kernel 0 (phase bit 0) over the D plane it wrote.  Handed BESIDE BwdArgs: no other kernel sees it.
-struct SinkGrad { const float* sink; float* dsink; int heads; };      // heads = H_q (BH = batch x heads)
+// dL (fa2_backward_lse): the gradient of L, addressed like BwdArgs::L, or nullptr; kernel 0 alone reads it (D' = D - dL, so the
+// sinks' gradient above is taken over D').  sink and dsink are nullptr together in a call that only brings dL.
+struct SinkGrad { const float* sink; float* dsink; int heads; const float* dL = nullptr; };      // heads = H_q (BH = batch x heads)
 
 hipError_t launch_bwd_bf16(const BwdArgs& a, hipStream_t stream, const SinkGrad* sg = nullptr);
 // The two-kernel backward over a packed variable-length batch.  a: the whole packed problem -- BH = H_q, q_hs = T_q, k_hs = T_k,

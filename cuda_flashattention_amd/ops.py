@@ -6,6 +6,7 @@ include/fa2_mi355x.h for file:line).  These wrappers keep the same names and arg
 meaning, take torch tensors only as *device memory* (pointer + shape), and call the C ABI
 through ctypes.  torch is plumbing here: allocation, streams, nothing numerical.
 """
+import ctypes
 import math
 
 import numpy as np
@@ -248,14 +249,15 @@ class _Attention(torch.autograd.Function):
         return dQ, dK, dV, None, None
 
 
-def attention(Q, K, V, softmax_scale=None, causal=False, sink=None):
+def attention(Q, K, V, softmax_scale=None, causal=False, sink=None, return_lse=False):
     """softmax(scale Q K^T [causal]) V for [B, H, N, d] bf16 (d = 64 | 128) or fp32 (non-causal) device tensors, with gradients.
     bf16 K and V may have fewer heads ([B, H_kv, N, d], H_kv dividing H: grouped-query attention); their gradients have their shape.
     sink: attention sinks, a bf16 or fp32 tensor (a parameter) of H logits that join every row's softmax (attention_qk; bf16
     [B, H, N, d] tensors only), with its gradient.
+    return_lse: return (O, L) with the differentiable log-sum-exp L (attention_qk; bf16 [B, H, N, d] tensors only).
     A convenience for callers that live in torch autograd; tests and bench.py call the two halves directly."""
-    if sink is not None:
-        return attention_qk(Q, K, V, softmax_scale, causal, sink=sink)
+    if sink is not None or return_lse:
+        return attention_qk(Q, K, V, softmax_scale, causal, sink=sink, return_lse=return_lse)
     return _Attention.apply(Q, K, V, softmax_scale, causal)
 
 
@@ -307,12 +309,14 @@ def flash_attention_2_qk_forward(Q, K, V, softmax_scale=None, causal=False, O=No
 
 
 def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=False,
-                                  dQ=None, dK=None, dV=None, workspace=None, stream=None, phases=7, sink=None, dsink=None):
+                                  dQ=None, dK=None, dV=None, workspace=None, stream=None, phases=7, sink=None, dsink=None, dL=None):
     """dQ, dK, dV = FA2 backward of flash_attention_2_qk_forward (fa2_backward_qk): dO like O, dK / dV like K / V.  N_q != N_k
     runs the two deterministic kernels (phases: 1 = D and the row constants, 2 = dQ, 4 = dK/dV; 8, the single kernel, is
     refused); N_q == N_k is flash_attention_2_backward.  A row that saw no key gets dQ = 0.
     sink (fa2_backward_sink): the forward's sinks, with its O and L; returns (dQ, dK, dV, dsink), dsink fp32 [H] (written with
-    phase bit 0)."""
+    phase bit 0).
+    dL (fa2_backward_lse): the gradient of L, fp32 shaped like L -- dS = P o (dP - D + dL), through the row constant D' = D - dL
+    that phase bit 0 writes; a row with L = -inf ignores it.  With or without sink=."""
     if sink is not None:
         _sink_arg(sink, Q, 1)
         if dsink is not None:
@@ -323,6 +327,8 @@ def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=
     for n, t in (("O", O), ("dO", dO)):
         _like(t, n, Q, (B, H, Nq, d), Q.dtype)
     _rows(L, "L", Q, B, H, Nq)
+    if dL is not None:
+        _rows(dL, "dL", Q, B, H, Nq)
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
     dQ = torch.empty_like(Q) if dQ is None else _like(dQ, "dQ", Q, (B, H, Nq, d), Q.dtype)
     dK = torch.empty_like(K) if dK is None else _like(dK, "dK", Q, (B, Hkv, Nk, d), Q.dtype)
@@ -332,6 +338,16 @@ def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=
         workspace = torch.empty(lib.fa2_backward_qk_workspace_bytes(B, H, Hkv, Nq, Nk, d, FA2_DTYPE_BF16), dtype=torch.uint8, device=Q.device)
     if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
         raise ValueError("workspace must be a contiguous device tensor on Q's device")
+    if dL is not None:
+        if sink is not None and dsink is None:
+            dsink = torch.empty(H, dtype=torch.float32, device=Q.device)
+        st = lib.fa2_backward_lse(Q.data_ptr(), K.data_ptr(), V.data_ptr(), None if sink is None else sink.data_ptr(), O.data_ptr(),
+                                  L.data_ptr(), dO.data_ptr(), dL.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(),
+                                  None if sink is None else dsink.data_ptr(), B, H, Hkv, Nq, Nk, d, scale, FA2_DTYPE_BF16,
+                                  1 if causal else 0, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                  _stream_ptr(stream), int(phases))
+        check(st, "fa2_backward_lse")
+        return (dQ, dK, dV) if sink is None else (dQ, dK, dV, dsink)
     if sink is not None:
         dsink = torch.empty(H, dtype=torch.float32, device=Q.device) if dsink is None else dsink
         st = lib.fa2_backward_sink(Q.data_ptr(), K.data_ptr(), V.data_ptr(), sink.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
@@ -348,35 +364,46 @@ def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=
     return dQ, dK, dV
 
 
+def _grad_pair(O, dO, dL):
+    """What a backward is handed for the outputs (O, L) of an op that does not materialise absent gradients, as the raw halves
+    take it: dO contiguous (zeros when only L was used), dL contiguous fp32 or None."""
+    dO = torch.zeros_like(O) if dO is None else dO.contiguous()
+    return dO, None if dL is None else dL.float().contiguous()
+
+
 class _AttentionQK(torch.autograd.Function):
     """flash_attention_2_qk_forward / _backward as one differentiable op (as _Attention)."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, softmax_scale, causal, sink=None):
+    def forward(ctx, Q, K, V, softmax_scale, causal, sink=None, return_lse=False):
         Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
         scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
         s32 = _sink_param(sink)                      # the kernels read fp32 sinks; the parameter may be bf16
         O, L = flash_attention_2_qk_forward(Q, K, V, scale, causal=causal, sink=s32)
         ctx.save_for_backward(Q, K, V, O, L, s32)
         ctx.scale, ctx.causal, ctx.sink_dtype = scale, bool(causal), None if sink is None else sink.dtype
-        return O
+        ctx.set_materialize_grads(False)             # an output nobody used arrives as None: no dL, the call of before
+        return (O, L) if return_lse else O
 
     @staticmethod
-    def backward(ctx, dO):
+    def backward(ctx, dO, dL=None):
         Q, K, V, O, L, s32 = ctx.saved_tensors
+        dO, dL = _grad_pair(O, dO, dL)
         if s32 is None:
-            dQ, dK, dV = flash_attention_2_qk_backward(Q, K, V, O, L, dO.contiguous(), ctx.scale, causal=ctx.causal)
-            return dQ, dK, dV, None, None, None
-        dQ, dK, dV, dsink = flash_attention_2_qk_backward(Q, K, V, O, L, dO.contiguous(), ctx.scale, causal=ctx.causal, sink=s32)
-        return dQ, dK, dV, None, None, dsink.to(ctx.sink_dtype)
+            dQ, dK, dV = flash_attention_2_qk_backward(Q, K, V, O, L, dO, ctx.scale, causal=ctx.causal, dL=dL)
+            return dQ, dK, dV, None, None, None, None
+        dQ, dK, dV, dsink = flash_attention_2_qk_backward(Q, K, V, O, L, dO, ctx.scale, causal=ctx.causal, sink=s32, dL=dL)
+        return dQ, dK, dV, None, None, dsink.to(ctx.sink_dtype), None
 
 
-def attention_qk(Q, K, V, softmax_scale=None, causal=False, sink=None):
+def attention_qk(Q, K, V, softmax_scale=None, causal=False, sink=None, return_lse=False):
     """attention() for N_q queries against N_k keys: Q [B, H, N_q, d], K and V [B, H_kv, N_k, d] bf16 device tensors (d = 64 | 128,
     H_kv dividing H); causal: bottom-right aligned (the last query sees every key).  With gradients, shaped like K and V.
     sink: attention sinks, a bf16 or fp32 tensor (a parameter) of H logits (flash_attention_2_qk_forward); its gradient comes
-    back in its dtype."""
-    return _AttentionQK.apply(Q, K, V, softmax_scale, causal, sink)
+    back in its dtype.
+    return_lse: return (O, L), L the fp32 [B, H, N_q] log-sum-exp of every row (-inf on a row without a key or sink), both
+    differentiable (merge_attention_states, a z-loss)."""
+    return _AttentionQK.apply(Q, K, V, softmax_scale, causal, sink, bool(return_lse))
 
 
 class VarlenPlan:
@@ -536,12 +563,13 @@ def flash_attention_2_varlen_forward(Q, K, V, plan, softmax_scale=None, causal=F
 
 
 def flash_attention_2_varlen_backward(Q, K, V, O, L, dO, plan, softmax_scale=None, causal=False,
-                                      dQ=None, dK=None, dV=None, workspace=None, stream=None, sink=None, dsink=None):
+                                      dQ=None, dK=None, dV=None, workspace=None, stream=None, sink=None, dsink=None, dL=None):
     """dQ, dK, dV = FA2 backward over a packed variable-length batch (fa2_backward_varlen; the two deterministic kernels): the
     tensors of flash_attention_2_varlen_forward, dO like O, dK / dV like K / V.  workspace: a uint8 device tensor of
     fa2_backward_varlen_workspace_bytes (allocated per call when omitted -- pass one for graph capture).  Under a two-sided plan
     (fa2_backward_varlen_qk) dK / dV are [H_kv, T_k, d]; a sequence with keys and no queries gets dK = dV = 0.
-    sink (fa2_backward_varlen_sink): the forward's sinks, with its O and L; returns (dQ, dK, dV, dsink), dsink fp32 [H]."""
+    sink (fa2_backward_varlen_sink): the forward's sinks, with its O and L; returns (dQ, dK, dV, dsink), dsink fp32 [H].
+    dL (fa2_backward_varlen_lse): the gradient of L, fp32 [H, T], as in flash_attention_2_qk_backward."""
     if sink is not None:
         _sink_arg(sink, Q, 0)
         if dsink is not None:
@@ -552,6 +580,8 @@ def flash_attention_2_varlen_backward(Q, K, V, O, L, dO, plan, softmax_scale=Non
     for n, t in (("O", O), ("dO", dO)):
         _packed(t, n, Q, (H, T, d))
     _rows(L, "L", Q, 1, H, T)
+    if dL is not None:
+        _rows(dL, "dL", Q, 1, H, T)
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
     dQ = torch.empty_like(Q) if dQ is None else _packed(dQ, "dQ", Q, (H, T, d))
     dK = torch.empty_like(K) if dK is None else _packed(dK, "dK", Q, (Hkv, Tk, d))
@@ -564,6 +594,12 @@ def flash_attention_2_varlen_backward(Q, K, V, O, L, dO, plan, softmax_scale=Non
     ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr())
     tail = (d, scale, FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(), plan.nbytes,
             workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr(stream))
+    if dL is not None:
+        if sink is not None and dsink is None:
+            dsink = torch.empty(H, dtype=torch.float32, device=Q.device)
+        check(lib.fa2_backward_varlen_lse(*ptrs[:3], None if sink is None else sink.data_ptr(), *ptrs[3:6], dL.data_ptr(), *ptrs[6:],
+                                          None if sink is None else dsink.data_ptr(), H, Hkv, T, Tk, *tail), "fa2_backward_varlen_lse")
+        return (dQ, dK, dV) if sink is None else (dQ, dK, dV, dsink)
     if sink is not None:
         dsink = torch.empty(H, dtype=torch.float32, device=Q.device) if dsink is None else dsink
         check(lib.fa2_backward_varlen_sink(*ptrs[:3], sink.data_ptr(), *ptrs[3:], dsink.data_ptr(), H, Hkv, T, Tk, *tail),
@@ -580,31 +616,169 @@ class _AttentionVarlen(torch.autograd.Function):
     """flash_attention_2_varlen_forward / _backward as one differentiable op (as _Attention)."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, plan, softmax_scale, causal, sink=None):
+    def forward(ctx, Q, K, V, plan, softmax_scale, causal, sink=None, return_lse=False):
         Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
         scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
         s32 = _sink_param(sink)
         O, L = flash_attention_2_varlen_forward(Q, K, V, plan, scale, causal=causal, sink=s32)
         ctx.save_for_backward(Q, K, V, O, L, s32)
         ctx.plan, ctx.scale, ctx.causal, ctx.sink_dtype = plan, scale, bool(causal), None if sink is None else sink.dtype
-        return O
+        ctx.set_materialize_grads(False)
+        return (O, L) if return_lse else O
 
     @staticmethod
-    def backward(ctx, dO):
+    def backward(ctx, dO, dL=None):
         Q, K, V, O, L, s32 = ctx.saved_tensors
+        dO, dL = _grad_pair(O, dO, dL)
         if s32 is None:
-            dQ, dK, dV = flash_attention_2_varlen_backward(Q, K, V, O, L, dO.contiguous(), ctx.plan, ctx.scale, causal=ctx.causal)
-            return dQ, dK, dV, None, None, None, None
-        dQ, dK, dV, dsink = flash_attention_2_varlen_backward(Q, K, V, O, L, dO.contiguous(), ctx.plan, ctx.scale, causal=ctx.causal,
-                                                              sink=s32)
-        return dQ, dK, dV, None, None, None, dsink.to(ctx.sink_dtype)
+            dQ, dK, dV = flash_attention_2_varlen_backward(Q, K, V, O, L, dO, ctx.plan, ctx.scale, causal=ctx.causal, dL=dL)
+            return dQ, dK, dV, None, None, None, None, None
+        dQ, dK, dV, dsink = flash_attention_2_varlen_backward(Q, K, V, O, L, dO, ctx.plan, ctx.scale, causal=ctx.causal, sink=s32, dL=dL)
+        return dQ, dK, dV, None, None, None, dsink.to(ctx.sink_dtype), None
 
 
-def attention_varlen(Q, K, V, plan, softmax_scale=None, causal=False, sink=None):
+def attention_varlen(Q, K, V, plan, softmax_scale=None, causal=False, sink=None, return_lse=False):
     """attention() over a packed variable-length batch: Q [H, T, d], K and V [H_kv, T, d] bf16 device tensors (d = 64 | 128, H_kv
     dividing H), plan a VarlenPlan of the batch's cu_seqlens; every sequence attends itself only.  With gradients.  Under a
-    two-sided plan K and V are [H_kv, T_k, d] and so are their gradients.  sink: attention sinks, as in attention_qk."""
-    return _AttentionVarlen.apply(Q, K, V, plan, softmax_scale, causal, sink)
+    two-sided plan K and V are [H_kv, T_k, d] and so are their gradients.  sink: attention sinks, as in attention_qk.
+    return_lse: return (O, L), L fp32 [H, T], both differentiable."""
+    return _AttentionVarlen.apply(Q, K, V, plan, softmax_scale, causal, sink, bool(return_lse))
+
+
+MERGE_MAX_PARTS = 8
+
+
+def _merge_parts(Os, Ls):
+    """The parts of a merge, checked like every tensor the C ABI takes on trust: 1..8 bf16 contiguous device tensors [..., d] of one
+    shape on one device, and as many fp32 tensors of that shape without its last dimension.  Returns (n, rows, d)."""
+    if not isinstance(Os, (list, tuple)) or not isinstance(Ls, (list, tuple)):
+        raise ValueError("Os and Ls must be lists (or tuples) of tensors")
+    n = len(Os)
+    if not 1 <= n <= MERGE_MAX_PARTS or len(Ls) != n:
+        raise ValueError(f"expected 1..{MERGE_MAX_PARTS} parts and as many Ls as Os, got {n} Os and {len(Ls)} Ls")
+    ref = Os[0]
+    if not isinstance(ref, torch.Tensor) or ref.dim() < 2 or ref.shape[-1] < 1:
+        raise ValueError("Os[0] must be a tensor [..., d]")
+    for i in range(n):
+        _merge_like(Os[i], f"Os[{i}]", ref, tuple(ref.shape), torch.bfloat16)
+        _merge_like(Ls[i], f"Ls[{i}]", ref, tuple(ref.shape[:-1]), torch.float32)
+    return n, ref.numel() // ref.shape[-1], ref.shape[-1]
+
+
+def _merge_like(x, name, ref, shape, dtype):
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if not x.is_cuda:
+        raise ValueError(f"{name} must be a device tensor")
+    if tuple(x.shape) != shape:
+        raise ValueError(f"{name}: shape {tuple(x.shape)} does not match {shape}")
+    if x.dtype != dtype:
+        raise ValueError(f"{name}: dtype {x.dtype}, expected {dtype}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (got strides {tuple(x.stride())}; call .contiguous())")
+    if x.device != ref.device:
+        raise ValueError(f"{name} is on {x.device}, expected {ref.device}")
+    return x
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def merge_states_forward(Os, Ls, O=None, L=None, stream=None):
+    """O, L = the attention over the union of the key sets of n <= 8 partial results (fa2_merge_states): Os bf16 [..., d] (d = 64 |
+    128) and Ls fp32 [...], the (O_i, L_i) of forwards of the SAME queries over disjoint keys ([B, H, N, d] or packed [H, T, d]).
+    L = logsumexp_i L_i, O = sum_i exp(L_i - L) O_i (fp32 arithmetic, bf16 result).  A part with L_i = -inf on a row is left out
+    of the row; every part -inf: O = 0, L = -inf; one part: its own bits."""
+    n, rows, d = _merge_parts(Os, Ls)
+    ref = Os[0]
+    O = torch.empty_like(ref) if O is None else _merge_like(O, "O", ref, tuple(ref.shape), torch.bfloat16)
+    L = torch.empty_like(Ls[0]) if L is None else _merge_like(L, "L", ref, tuple(ref.shape[:-1]), torch.float32)
+    st = _capi.lib().fa2_merge_states(_ptr_array(Os), _ptr_array(Ls), n, O.data_ptr(), L.data_ptr(), rows, d, FA2_DTYPE_BF16, _stream_ptr(stream))
+    check(st, "fa2_merge_states")
+    return O, L
+
+
+def merge_states_backward(Os, Ls, O, L, dO, dL=None, dOs=None, dLs=None, stream=None):
+    """dOs, dLs = the gradients of the parts of merge_states_forward (fa2_merge_states_backward) from its results O, L and their
+    gradients dO (bf16, like O) and dL (fp32, like L, or None = 0): dO_i = exp(L_i - L) dO, dL_i = exp(L_i - L) (dL + rowsum(dO o
+    (O_i - O))), both 0 where L_i = -inf.  dOs / dLs: lists of tensors to write into (allocated when omitted)."""
+    n, rows, d = _merge_parts(Os, Ls)
+    ref = Os[0]
+    oshape, lshape = tuple(ref.shape), tuple(ref.shape[:-1])
+    _merge_like(O, "O", ref, oshape, torch.bfloat16)
+    _merge_like(L, "L", ref, lshape, torch.float32)
+    _merge_like(dO, "dO", ref, oshape, torch.bfloat16)
+    if dL is not None:
+        _merge_like(dL, "dL", ref, lshape, torch.float32)
+    if dOs is None:
+        dOs = [torch.empty_like(ref) for _ in range(n)]
+    if dLs is None:
+        dLs = [torch.empty_like(L) for _ in range(n)]
+    if not isinstance(dOs, (list, tuple)) or not isinstance(dLs, (list, tuple)) or len(dOs) != n or len(dLs) != n:
+        raise ValueError(f"dOs and dLs must be lists of {n} tensors")
+    for i in range(n):
+        _merge_like(dOs[i], f"dOs[{i}]", ref, oshape, torch.bfloat16)
+        _merge_like(dLs[i], f"dLs[{i}]", ref, lshape, torch.float32)
+    st = _capi.lib().fa2_merge_states_backward(_ptr_array(Os), _ptr_array(Ls), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
+                                               None if dL is None else dL.data_ptr(), _ptr_array(dOs), _ptr_array(dLs), n, rows, d,
+                                               FA2_DTYPE_BF16, _stream_ptr(stream))
+    check(st, "fa2_merge_states_backward")
+    return list(dOs), list(dLs)
+
+
+class _MergeStates(torch.autograd.Function):
+    """merge_states_forward / _backward as one differentiable op over (O_0 .. O_n-1, L_0 .. L_n-1)."""
+
+    @staticmethod
+    def forward(ctx, n, *parts):
+        Os, Ls = [t.contiguous() for t in parts[:n]], [t.contiguous() for t in parts[n:]]
+        O, L = merge_states_forward(Os, Ls)
+        ctx.save_for_backward(O, L, *Os, *Ls)
+        ctx.n = n
+        ctx.set_materialize_grads(False)
+        return O, L
+
+    @staticmethod
+    def backward(ctx, dO, dL=None):
+        O, L, *parts = ctx.saved_tensors
+        dO, dL = _grad_pair(O, dO, dL)
+        dOs, dLs = merge_states_backward(parts[:ctx.n], parts[ctx.n:], O, L, dO, dL)
+        return (None, *dOs, *dLs)
+
+
+def merge_attention_states(Os, Ls):
+    """O, L = merge_states_forward(Os, Ls) with gradients: (O_i, L_i) from attention_qk(..., return_lse=True) (or attention,
+    attention_varlen) of the same queries over disjoint key sets become the attention over the union of the keys, and the
+    gradients of O and of L flow back into every part's O_i and L_i."""
+    Os, Ls = list(Os), list(Ls)
+    if not 1 <= len(Os) <= MERGE_MAX_PARTS or len(Ls) != len(Os):
+        raise ValueError(f"expected 1..{MERGE_MAX_PARTS} parts and as many Ls as Os, got {len(Os)} Os and {len(Ls)} Ls")
+    return _MergeStates.apply(len(Os), *Os, *Ls)
+
+
+def attention_segments(Q, segments, softmax_scale=None, causal=False, sink=None, return_lse=False):
+    """attention_qk of Q [B, H, N_q, d] over the concatenation, along the key axis, of segments = [(K_0, V_0), ...] (at most 8, each
+    [B, H_kv, N_s, d]) WITHOUT copying K or V: a prompt chunk against a prefix cache that lives in another allocation, a shared
+    prefix.  One attention_qk(..., return_lse=True) per segment, then merge_attention_states; with gradients for Q and every
+    segment.  causal: bottom-right aligned over the whole key axis, applied in the last segment only -- which therefore must hold
+    at least N_q keys, so that every earlier segment lies wholly in every query's past.  sink joins the softmax once, in the last
+    segment.  return_lse: (O, L)."""
+    if not isinstance(segments, (list, tuple)) or not 1 <= len(segments) <= MERGE_MAX_PARTS:
+        raise ValueError(f"segments: expected a list of 1..{MERGE_MAX_PARTS} (K, V) pairs")
+    for seg in segments:
+        if not isinstance(seg, (list, tuple)) or len(seg) != 2:
+            raise ValueError("segments: every entry is a (K, V) pair")
+    last = len(segments) - 1
+    if causal and isinstance(Q, torch.Tensor) and Q.dim() == 4 and isinstance(segments[last][0], torch.Tensor) and segments[last][0].dim() == 4 \
+            and segments[last][0].shape[2] < Q.shape[2]:
+        raise ValueError(f"causal attention over segments applies the mask in the last segment only: it must hold at least N_q = "
+                         f"{Q.shape[2]} keys, so that every earlier segment lies wholly in every query's past (got "
+                         f"{segments[last][0].shape[2]}; per-segment shifts are not supported)")
+    outs = [attention_qk(Q, K, V, softmax_scale, causal and i == last, sink=sink if i == last else None, return_lse=True)
+            for i, (K, V) in enumerate(segments)]
+    O, L = outs[0] if last == 0 else merge_attention_states([o for o, _ in outs], [l for _, l in outs])
+    return (O, L) if return_lse else O
 
 
 def read_clocks(stream=None):

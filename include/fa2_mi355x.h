@@ -360,6 +360,42 @@ int fa2_backward_varlen_sink(const void* Q, const void* K, const void* V, const 
                              const void* plan_host, const void* plan_dev, size_t plan_bytes,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- A gradient for L, and merging partial results.  Every bf16 forward returns the row log-sum-exp L beside O; these calls
+ * make it a differentiable output and combine (O, L) pairs computed over DIFFERENT KEY SETS into the attention over their union
+ * (context-parallel and ring attention written in autograd, a prompt chunk against a prefix cache held in another allocation,
+ * cascade / shared-prefix inference, z-loss).
+ * fa2_backward_lse / fa2_backward_varlen_lse are fa2_backward_sink / fa2_backward_varlen_sink with `dL` behind dO: fp32, DEVICE
+ * memory, shaped and addressed like L, the gradient of the loss with respect to L.  dL/dS_ij = P_ij, so dS = P o (dP - D + dL): the
+ * D kernel stores D' = rowsum(dO o O) - dL and every other kernel runs unchanged; dsink = - sum exp(s_h - L) D' (dL/ds_h =
+ * exp(s_h - L)).  dL takes effect with PHASE BIT 0, like dsink.  A row with L = -inf (no visible key, no sink) ignores its dL,
+ * whatever it holds.  dL may be NULL (= 0); sink and dsink are NULL together (no sink) or non-NULL together, FA2_ERR_NULL_POINTER
+ * otherwise.  With sink == NULL and dL == NULL the calls are fa2_backward_qk / fa2_backward_varlen_qk bit for bit; routing,
+ * `phases`, status codes and the workspace (fa2_backward_qk_workspace_bytes / fa2_backward_varlen_qk_workspace_bytes) are theirs.
+ * fa2_merge_states: n_parts (1..8) parts O_i (bf16 [rows][head_dim]) and L_i (fp32 [rows]), `rows` the flattened leading
+ * dimensions ([B][H][N] or a packed [H][T]), head_dim 64 or 128:
+ *     L = log sum_i exp L_i,    O = bf16(sum_i exp(L_i - L) O_i)         (fp32, ascending i: the same bits on every run)
+ * O_parts / L_parts (and dO_parts / dL_parts) are HOST arrays of n_parts DEVICE pointers, read during the call.  A part with
+ * L_i = -inf on a row is left out of that row (its O_i row may hold anything); all parts -inf: O = 0, L = -inf; one part: its bits.
+ * fa2_merge_states_backward: from the parts, the merged O and L, dO (bf16) and dL (fp32 or NULL), with w_i = exp(L_i - L):
+ *     dO_i = bf16(w_i dO),    dL_i = w_i (dL + rowsum(dO o (O_i - O)))   (0 and 0 where L_i = -inf)
+ * -- feed them to fa2_backward_lse of the call that produced part i.  O and dO_i may not alias.  Nothing is allocated, nothing
+ * synchronises.  STATUS CODES: a NULL array, tensor or array entry -> FA2_ERR_NULL_POINTER; n_parts outside 1..8 or rows == 0 ->
+ * FA2_ERR_INVALID_SHAPE; then FA2_ERR_UNSUPPORTED_HEAD_DIM, FA2_ERR_UNSUPPORTED_DTYPE (bf16 only). */
+int fa2_backward_lse(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L, const void* dO,
+                     const float* dL, void* dQ, void* dK, void* dV, float* dsink,
+                     int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                     int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases);
+int fa2_backward_varlen_lse(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L,
+                            const void* dO, const float* dL, void* dQ, void* dK, void* dV, float* dsink,
+                            int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
+                            const void* plan_host, const void* plan_dev, size_t plan_bytes,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int fa2_merge_states(const void* const* O_parts, const float* const* L_parts, int n_parts, void* O, float* L, size_t rows,
+                     int head_dim, int dtype, void* stream);
+int fa2_merge_states_backward(const void* const* O_parts, const float* const* L_parts, const void* O, const float* L, const void* dO,
+                              const float* dL, void* const* dO_parts, float* const* dL_parts, int n_parts, size_t rows, int head_dim,
+                              int dtype, void* stream);
+
 /* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output
  * pass (FA2_ERR_UNSUPPORTED for shapes or devices it does not take, and in combination with bits 1 or 2).  7 = fa2_backward (which picks the implementation);
