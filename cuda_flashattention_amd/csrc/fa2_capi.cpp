@@ -862,6 +862,49 @@ int fa2_merge_states_backward(const void* const* O_parts, const float* const* L_
     return hip_status(fa2::launch_merge_bwd(b, head_dim, (hipStream_t)stream));
 }
 
+// ---- split-KV decode over a KV cache (include/fa2_mi355x.h; fa2_decode.hip).  Nothing here reads a sequence length.
+int fa2_decode_num_splits(int B, int H_kv, int kv_capacity, int head_dim)
+{
+    (void)head_dim;      // part of the signature: the rule may come to depend on the row size
+    if (B <= 0 || H_kv <= 0 || kv_capacity <= 0) return 1;
+    return fa2::decode_num_splits(B, H_kv, kv_capacity);
+}
+
+size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, int n_splits)
+{
+    if (B <= 0 || H_q <= 0 || H_kv <= 0 || q_len <= 0 || kv_capacity <= 0 || head_dim <= 0) return 0;
+    if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return 0;
+    if (n_splits == 0) n_splits = fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
+    if (n_splits == 1) return 0;
+    return align256((size_t)n_splits * B * H_q * q_len * ((size_t)head_dim + 1) * sizeof(float));
+}
+
+int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
+                       void* O, float* L, int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
+                       int dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!Q || !K_cache || !V_cache || !O || !L) return FA2_ERR_NULL_POINTER;
+    int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
+    if (st) return st;
+    if (H_kv <= 0 || H_q % H_kv != 0 || kv_capacity <= 0) return FA2_ERR_INVALID_SHAPE;
+    if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
+    if ((long long)kv_capacity * head_dim * 2 > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;      // one (b, head) slab, one buffer resource
+    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
+    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    if (n_splits == 0) n_splits = fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
+    if ((long long)B * H_kv * n_splits > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;             // the grid
+    const size_t need = fa2_decode_workspace_bytes(B, H_q, H_kv, q_len, kv_capacity, head_dim, n_splits);
+    if (n_splits > 1 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return FA2_ERR_WORKSPACE;
+    if ((long long)(H_q / H_kv) * q_len > fa2::kDecodeMaxRows) return FA2_ERR_UNSUPPORTED;
+    fa2::DecodeArgs a{};
+    a.Q = Q; a.K = K_cache; a.V = V_cache; a.seqlens = seqlens_k; a.sink = sink; a.O = O; a.L = L;
+    a.wsO = (float*)workspace;
+    a.wsL = n_splits > 1 ? (float*)workspace + (size_t)n_splits * B * H_q * q_len * head_dim : nullptr;
+    a.B = B; a.Hq = H_q; a.Hkv = H_kv; a.Nq = q_len; a.Ncap = kv_capacity; a.n_splits = n_splits;
+    a.scale = softmax_scale; a.causal = causal ? 1 : 0;
+    return hip_status(fa2::launch_decode(a, head_dim, (hipStream_t)stream));
+}
+
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,
                         void* stream)
 {

@@ -1,0 +1,341 @@
+// fa2_decode.hip -- split-KV decode attention over a KV cache with per-sequence lengths (fa2_forward_decode,
+// include/fa2_mi355x.h): a few new query tokens per sequence (N_q) against [B][H_kv][N_cap][d] caches of which sequence b uses
+// the first len_b = clamp(seqlens_k[b], 0, N_cap) rows.
+//
+// WORK SPLIT.  One workgroup = one (sequence, K/V head, key split).  The M = G N_q query rows of the head's group (G = H_q / H_kv;
+// they are one contiguous [M][d] slab of Q, O and L) are the 32 COLUMNS of an MFMA tile, so the K/V head is streamed once for
+// the whole group.  Split s covers keys [s chunk, min((s + 1) chunk, len_b)), chunk = roundup(ceil(len_b / n_splits), kDecodeKB),
+// computed here from len_b: the host never sees a length.  Inside the split the four waves take the 32-key tiles round-robin
+// (wave w: tiles w, w + 4, ...), each with an online softmax of its own; they meet once, through LDS, at the end.
+// DATA PATH per 32-key tile of a wave:
+//   S^T = K Q^T   A = K: lane (key r, half h) holds 16 contiguous bytes of its key row per k-step, loaded straight from global
+//                 memory into VGPRs (every K byte is used once: no LDS round trip); B = Q^T, loaded once, rows >= M zero;
+//   softmax       a score's query row is the LANE, its 16 keys the registers: maximum and sum are in-lane plus one
+//                 permlane32_swap; masked probabilities are SELECTED to 0; the row sum adds the fp32 P;
+//   O^T += V^T P^T  P^T is the accumulator itself (bf16-rounded) as the B operand; V^T comes from V rows loaded in whole lines
+//                 into VGPRs, written into the wave's own swizzled LDS image (lds_off) and read back with ds_read_b64_tr_b16.
+//                 A wave's LDS operations execute in order, so its private image needs no barrier.
+// K and V are read through buffer resources that end at the split's last key: rows past it (whatever a cache holds beyond
+// its length, NaNs included) come back as zeros and never meet an MFMA as data.  The next tile's K and V loads are issued before
+// the current tile's arithmetic.
+// RESULT.  n_splits == 1: O (bf16, the sink applied) and L.  Otherwise an fp32 partial per (split, row): the normalised O_s [d]
+// and L_s (-inf for a split without a visible key), which fa2_decode_combine_kernel -- a second plain launch on the same
+// stream -- folds in ascending s: L = logsumexp_s L_s, O = sum_s exp(L_s - L) O_s, then the sink, then ONE rounding to bf16.
+// No workgroup talks to another inside a launch: no atomics, no flags, no waiting; every sum has a fixed order.
+#include "fa2_common.h"
+#include "fa2_launch.h"
+
+#include <algorithm>
+
+namespace fa2 {
+
+namespace {
+
+constexpr float kDecLn2 = 0.6931471805599453f;
+constexpr int kDecWaves = kDecodeKB / kDecodeTile;      // 4: one tile per wave and round
+typedef __attribute__((address_space(3))) bf16x4 dec_lds_bf16x4;
+constexpr int kCombineBatch = 8;      // partials of a row in flight in the combine
+
+// L <- log(exp L + exp s), returns exp(L_old - L_new), what O scales by (fa2_forward_sink's rule).  s = -inf: no sink, nothing
+// changes, bit for bit.  L = -inf (a row without a key): L = s and O = 0.
+__device__ __forceinline__ float decode_sink(float s, float& L)
+{
+    const bool none = s == -INFINITY, keyless = L == -INFINITY;
+    const float hi = fmaxf(L, s);
+    const float e = __builtin_amdgcn_exp2f(-fabsf(L - s) * kLog2e);             // (NaN where both are -inf: selected away)
+    const float Ln = hi + __builtin_amdgcn_logf(1.0f + e) * kDecLn2;
+    const float w = __builtin_amdgcn_exp2f((L - Ln) * kLog2e);
+    const float Lold = L;
+    L = none ? Lold : (keyless ? s : Ln);
+    return none ? 1.0f : (keyless ? 0.0f : w);
+}
+
+__device__ __forceinline__ bf16x4 to_bf16x4(const f32x4& v, float w)
+{
+    bf16x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = (__bf16)(v[e] * w);
+    return r;
+}
+
+}  // namespace
+
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_split_kernel(DecodeArgs a)
+{
+    constexpr int ROWB = 2 * D;               // bytes per cache row
+    constexpr int KS = D / 16;                // k-steps of S^T = K Q^T
+    constexpr int CPR = D / 8;                // 16-byte chunks per row
+    constexpr int RPI = 64 / CPR;             // V rows one wave-wide load covers
+    constexpr int NV = kDecodeTile / RPI;     // V loads per tile
+    constexpr int DB = D / 32;                // 32-column tiles of O^T
+    constexpr int VIMG = kDecodeTile * ROWB;  // a wave's V image
+    constexpr int OP = D + 4;                 // floats per row of a wave's O image (the pad spreads 32 rows over the banks)
+    constexpr int C4 = D / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // kDecWaves x max(VIMG, 32 OP 4) | m, l: kDecWaves x 32 x 2 floats
+    float* const s_ml = reinterpret_cast<float*>(smem + kDecWaves * 32 * OP * 4);
+
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int G = a.Hq / a.Hkv, M = G * a.Nq;
+    const int bid = blockIdx.x;
+    const int split = bid % a.n_splits, hkv = (bid / a.n_splits) % a.Hkv, b = bid / (a.n_splits * a.Hkv);
+
+    // the clamp is the contract: nothing below sees the stored value
+    int len = a.Ncap;
+    if (a.seqlens) len = min(max(__builtin_amdgcn_readfirstlane(a.seqlens[b]), 0), a.Ncap);
+    const int per = (len + a.n_splits - 1) / a.n_splits;
+    const int chunk = (per + kDecodeKB - 1) / kDecodeKB * kDecodeKB;
+    const int begin = split * chunk;                      // <= len + n_splits kDecodeKB: no overflow
+    const int end = min(begin + chunk, len);
+
+    const size_t R = (size_t)a.B * a.Hq * a.Nq;           // rows of O, L and of one split's partials
+    const size_t row0 = ((size_t)b * a.Hq + (size_t)hkv * G) * a.Nq;      // the group's first row
+
+    // what a finished row piece becomes: a partial, or the result
+    const auto emit = [&](int row, int c4, const f32x4& o, float Lrow) {
+        const size_t gr = row0 + row;
+        if (a.n_splits > 1) {
+            *reinterpret_cast<f32x4*>(a.wsO + ((size_t)split * R + gr) * D + 4 * c4) = o;
+            if (c4 == 0) a.wsL[(size_t)split * R + gr] = Lrow;
+        } else {
+            float w = 1.0f;
+            if (a.sink) w = decode_sink(a.sink[hkv * G + row / a.Nq], Lrow);
+            *reinterpret_cast<bf16x4*>((__bf16*)a.O + gr * D + 4 * c4) = to_bf16x4(o, w);
+            if (c4 == 0) a.L[gr] = Lrow;
+        }
+    };
+
+    if (begin >= end) {                                   // an empty split (a short sequence's later splits, len = 0): no key
+        for (int idx = tid; idx < M * C4; idx += 256) emit(idx / C4, idx % C4, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, -INFINITY);
+        return;
+    }
+
+    // Q^T fragments: lane (row r, half h) holds Q[r][16 t + 8 h ..+8] for k-step t
+    bf16x8 q[KS];
+    {
+        const __bf16* Qg = (const __bf16*)a.Q + (row0 + (r < M ? r : 0)) * D + 8 * h;
+#pragma unroll
+        for (int t = 0; t < KS; ++t) {
+            q[t] = *reinterpret_cast<const bf16x8*>(Qg + 16 * t);
+            if (r >= M) q[t] = bf16x8{};
+        }
+    }
+    // keys [0, kmax) are visible to this lane's row (bottom-right causal: j <= i + len - N_q), none to a padding row
+    int kmax = end;
+    if (a.causal) kmax = min(end, r % a.Nq + len - a.Nq + 1);
+    if (r >= M) kmax = 0;
+
+    const size_t slab = ((size_t)b * a.Hkv + hkv) * (size_t)a.Ncap * D;
+    const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.K + slab), 0, end * ROWB, 0x00020000);
+    const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.V + slab), 0, end * ROWB, 0x00020000);
+    const uint32_t koff = (uint32_t)r * ROWB + 16 * h;                       // + 32 t per k-step
+    const uint32_t voff = (uint32_t)(lane / CPR) * ROWB + 16 * (lane % CPR);   // + RPI rows per load
+    u32x4 kf[KS], vf[NV];
+    const auto load_tile = [&](int base) {      // rows past `end` read as zeros (and cost no traffic)
+        const uint32_t b0 = (uint32_t)base * ROWB;
+#pragma unroll
+        for (int t = 0; t < KS; ++t) kf[t] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, b0 + koff + 32 * t, 0, 0);
+#pragma unroll
+        for (int n = 0; n < NV; ++n) vf[n] = __builtin_amdgcn_raw_buffer_load_b128(v_rsrc, b0 + voff + n * RPI * ROWB, 0, 0);
+    };
+
+    char* const vimg = smem + wave * VIMG;
+    // ds_read_b64_tr_b16: lane 4 qq + p of a 16-lane group supplies row qq, columns 4 p ..+4 of a 4 x 16 block; the group's lanes
+    // get the block's columns.  Group g serves half g >> 1 and columns 16 (g & 1) ..+16 of a 32-column tile of V.
+    const int gi = lane & 15, qq = gi >> 2, pp = gi & 3, c0 = 16 * ((lane >> 4) & 1);
+
+    float m = -INFINITY, l = 0.0f;              // running maximum (log2 units) and this lane half's part of the running sum
+    f32x16 o[DB];
+#pragma unroll
+    for (int c = 0; c < DB; ++c)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[c][e] = 0.0f;
+    const float sc = a.scale * kLog2e;
+
+    int kb = begin + kDecodeTile * wave;
+    load_tile(kb);
+    for (; kb < end; kb += kDecodeKB) {
+#pragma unroll
+        for (int n = 0; n < NV; ++n)
+            *reinterpret_cast<u32x4*>(vimg + lds_off<D>(n * RPI + lane / CPR, lane % CPR)) = vf[n];
+        f32x16 s;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[e] = 0.0f;
+#pragma unroll
+        for (int t = 0; t < KS; ++t)
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[t]), q[t], s, 0, 0, 0);
+        load_tile(kb + kDecodeKB);
+
+        float mx = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            s[e] *= sc;
+            mx = kb + acc_row(e, h) < kmax ? fmaxf(mx, s[e]) : mx;
+        }
+        mx = half_max(mx);
+        const float m_new = fmaxf(m, mx);
+        const float m0 = m_new == -INFINITY ? 0.0f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m - m0);      // m = -inf: 0, and there is nothing to scale yet
+        m = m_new;
+        float ps = 0.0f;
+        bf16x8 p[2];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float pe = kb + acc_row(e, h) < kmax ? __builtin_amdgcn_exp2f(s[e] - m0) : 0.0f;
+            ps += pe;
+            p[e >> 3][e & 7] = (__bf16)pe;
+        }
+        l = l * alpha + ps;
+#pragma unroll
+        for (int c = 0; c < DB; ++c)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[c][e] *= alpha;
+        // element j of half h of k-step ks is key 16 ks + 8 (j >> 2) + 4 h + (j & 3): two transposed reads of four keys each
+#pragma unroll
+        for (int c = 0; c < DB; ++c) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                bf16x8 vt;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int row = 16 * ks + 8 * u + 4 * h + qq, col = 32 * c + c0 + 4 * pp;
+                    const bf16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                        (dec_lds_bf16x4*)(vimg + lds_off<D>(row, col >> 3) + 8 * (pp & 1)));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) vt[4 * u + e] = x[e];
+                }
+                o[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt, p[ks], o[c], 0, 0, 0);
+            }
+        }
+    }
+
+    // the four waves' states meet: common maximum, then O and l at that maximum, summed in wave order
+    l = half_sum(l);
+    if (h == 0) { s_ml[(wave * 32 + r) * 2] = m; s_ml[(wave * 32 + r) * 2 + 1] = l; }
+    __syncthreads();      // every wave is done with its V image: the O images below overlap them
+    {
+        float ms = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < kDecWaves; ++w) ms = fmaxf(ms, s_ml[(w * 32 + r) * 2]);
+        const float f = __builtin_amdgcn_exp2f(m - (ms == -INFINITY ? 0.0f : ms));
+        float* const oimg = reinterpret_cast<float*>(smem) + (wave * 32 + r) * OP + 4 * h;
+#pragma unroll
+        for (int c = 0; c < DB; ++c)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {      // registers 4 g4 ..+4: columns 32 c + 8 g4 + 4 h ..+4 of O's row r
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = o[c][4 * g4 + e] * f;
+                *reinterpret_cast<f32x4*>(oimg + 32 * c + 8 * g4) = v;
+            }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < M * C4; idx += 256) {
+        const int row = idx / C4, c4 = idx % C4;
+        float ms = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < kDecWaves; ++w) ms = fmaxf(ms, s_ml[(w * 32 + row) * 2]);
+        const float ms0 = ms == -INFINITY ? 0.0f : ms;
+        float lt = 0.0f;
+        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int w = 0; w < kDecWaves; ++w) {
+            lt += s_ml[(w * 32 + row) * 2 + 1] * __builtin_amdgcn_exp2f(s_ml[(w * 32 + row) * 2] - ms0);
+            acc += *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem) + (w * 32 + row) * OP + 4 * c4);
+        }
+        const bool has = lt > 0.0f;             // a select: a row without a visible key in this split
+        const float inv = 1.0f / lt;
+        f32x4 out;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[e] = has ? acc[e] * inv : 0.0f;
+        emit(row, c4, out, has ? (ms + __builtin_amdgcn_logf(lt)) * kDecLn2 : -INFINITY);      // (v_log_f32 is log2)
+    }
+}
+
+// rows x d / 4 lanes, a lane owns four columns of one row: partials in, ascending s, fp32; the sink; one rounding
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_combine_kernel(DecodeArgs a)
+{
+    constexpr int C4 = D / 4;
+    const size_t R = (size_t)a.B * a.Hq * a.Nq;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t row = t / C4;
+    const int c4 = (int)(t % C4);
+    if (row >= R) return;
+    // The partials of a row are loaded kCombineBatch at a time, all loads of a batch ahead of their use: the loop is a chain of
+    // memory latencies, one per batch, and summing split after split behind its own load made it four times as long (the
+    // summation order stays ascending s).  Indices past the last split are clamped and their terms selected away.
+    const int last = a.n_splits - 1;
+    float m = -INFINITY;
+    for (int s0 = 0; s0 < a.n_splits; s0 += 2 * kCombineBatch) {
+        float ls[2 * kCombineBatch];
+#pragma unroll
+        for (int i = 0; i < 2 * kCombineBatch; ++i) ls[i] = a.wsL[(size_t)min(s0 + i, last) * R + row];
+#pragma unroll
+        for (int i = 0; i < 2 * kCombineBatch; ++i) m = fmaxf(m, ls[i]);
+    }
+    const float m0 = m == -INFINITY ? 0.0f : m;
+    float sum = 0.0f;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s0 = 0; s0 < a.n_splits; s0 += kCombineBatch) {
+        float ls[kCombineBatch];
+        f32x4 os[kCombineBatch];
+#pragma unroll
+        for (int i = 0; i < kCombineBatch; ++i) {
+            const size_t at = (size_t)min(s0 + i, last) * R + row;
+            ls[i] = a.wsL[at];
+            os[i] = *reinterpret_cast<const f32x4*>(a.wsO + at * D + 4 * c4);
+        }
+#pragma unroll
+        for (int i = 0; i < kCombineBatch; ++i) {
+            const bool has = s0 + i <= last && ls[i] != -INFINITY;      // a select: an empty split's O_s is left out
+            const float w = __builtin_amdgcn_exp2f((ls[i] - m0) * kLog2e);
+            sum += has ? w : 0.0f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = has ? acc[e] + w * os[i][e] : acc[e];
+        }
+    }
+    const bool none = m == -INFINITY;
+    float Lrow = none ? -INFINITY : m + __builtin_amdgcn_logf(sum) * kDecLn2;
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = none ? 0.0f : acc[e] * inv;
+    float w = 1.0f;
+    if (a.sink) w = decode_sink(a.sink[(row / a.Nq) % a.Hq], Lrow);
+    *reinterpret_cast<bf16x4*>((__bf16*)a.O + row * D + 4 * c4) = to_bf16x4(acc, w);
+    if (c4 == 0) a.L[row] = Lrow;
+}
+
+int decode_num_splits(int B, int H_kv, int kv_capacity)
+{
+    const long long groups = (long long)B * H_kv;
+    const long long fill = (kDecodeCUs + groups - 1) / groups;               // smallest s with B H_kv s >= the CU count
+    const long long room = std::max(1, kv_capacity / kDecodeMinSplitKeys);   // a split of a full cache keeps that many keys
+    return (int)std::min<long long>(std::min(fill, room), kDecodeMaxSplits);
+}
+
+template <int D>
+static hipError_t decode_launch(const DecodeArgs& a, hipStream_t stream)
+{
+    constexpr int lds = kDecWaves * 32 * (D + 4) * 4 + kDecWaves * 32 * 2 * 4;
+    static_assert(kDecWaves * kDecodeTile * 2 * D <= kDecWaves * 32 * (D + 4) * 4, "the V images fit under the O images");
+    const unsigned grid = (unsigned)a.B * a.Hkv * a.n_splits;
+    hipError_t e = launch_lds<fa2_decode_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
+    if (e != hipSuccess || a.n_splits == 1) return e;
+    const size_t threads = (size_t)a.B * a.Hq * a.Nq * (D / 4);
+    hipLaunchKernelGGL(fa2_decode_combine_kernel<D>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream)
+{
+    if (a.n_splits < 1 || a.n_splits > kDecodeMaxSplits || a.Hq % a.Hkv || a.Hq / a.Hkv * a.Nq > kDecodeMaxRows)
+        return hipErrorInvalidValue;
+    if ((long long)a.B * a.Hkv * a.n_splits > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (d == 128) return decode_launch<128>(a, stream);
+    if (d == 64) return decode_launch<64>(a, stream);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace fa2

@@ -71,6 +71,25 @@ struct MergeBwdArgs {
 hipError_t launch_merge_fwd(const MergeArgs& a, int d, hipStream_t stream);        // d = 64 | 128
 hipError_t launch_merge_bwd(const MergeBwdArgs& b, int d, hipStream_t stream);
 
+// Split-KV decode over a KV cache (fa2_decode.hip; fa2_forward_decode): Q, O [B][Hq][Nq][d] bf16, K, V [B][Hkv][Ncap][d] bf16,
+// L [B][Hq][Nq]; seqlens (DEVICE, int [B]) and sink (DEVICE, fp32 [Hq]) may be nullptr.  n_splits >= 2: every split writes its
+// normalised fp32 partial to wsO [n_splits][B Hq Nq][d] and its LSE to wsL [n_splits][B Hq Nq], and a combine launch follows.
+constexpr int kDecodeTile = 32;            // keys of one MFMA tile: one wave's step
+constexpr int kDecodeKB = 128;             // the key block: one round of the four waves; a split's first key is a multiple of it
+constexpr int kDecodeMaxRows = 32;         // G Nq: the query rows of a K/V head fill the 32 columns of one tile
+constexpr int kDecodeMaxSplits = 256;
+constexpr int kDecodeCUs = 256;            // compute units of an MI355X: what the default split count fills
+constexpr int kDecodeMinSplitKeys = 256;   // the default gives a split of a full cache at least this many keys
+struct DecodeArgs {
+    const void* Q; const void* K; const void* V; const int* seqlens; const float* sink;
+    void* O; float* L; float* wsO; float* wsL;
+    int B, Hq, Hkv, Nq, Ncap, n_splits;
+    float scale;
+    int causal;
+};
+int decode_num_splits(int B, int H_kv, int kv_capacity);      // pure host arithmetic: fa2_decode_num_splits
+hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream);      // d = 64 | 128; 1 <= G Nq <= 32
+
 // fp8 (OCP e4m3) forward, d = 128: Q, K, V fp8 [BH][N][128]; O bf16; Vt: [BH][128][Npad] fp8 scratch the
 // launcher fills with V transposed (Npad = N rounded up to 64); kn: [BH][Npad / 64] fp32 scratch it fills with the largest
 // |k| of every 64 keys (fa2_fwd_fp8.hip: where the softmax needs no lane maxima).

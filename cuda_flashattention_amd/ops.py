@@ -308,6 +308,112 @@ def flash_attention_2_qk_forward(Q, K, V, softmax_scale=None, causal=False, O=No
     return O, L
 
 
+DECODE_MAX_ROWS = 32      # (H_q / H_kv) N_q: the query rows of one K/V head fill one 32-row MFMA tile (fa2_forward_decode)
+DECODE_MAX_SPLITS = 256
+
+
+def _decode_shapes(Q, K_cache, V_cache):
+    """(B, H, H_kv, N_q, N_cap, d) of a decode problem: Q [B, H, N_q, d] against caches [B, H_kv, N_cap, d], bf16, H_kv dividing
+    H.  Shapes and dtypes first, then device and contiguity, as _qk_shapes."""
+    for n, t in (("Q", Q), ("K_cache", K_cache), ("V_cache", V_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a [B, H, N, d] tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    B, H, Nq, d = Q.shape
+    Bk, Hkv, Ncap, dk = K_cache.shape
+    if (Bk, dk) != (B, d) or Hkv < 1 or H % Hkv != 0 or Nq < 1 or Ncap < 1:
+        raise ValueError(f"K_cache: shape {tuple(K_cache.shape)} does not match Q {tuple(Q.shape)}: expected [B, H_kv, N_cap, d] with "
+                         f"B = {B}, d = {d}, H_kv dividing H = {H} and N_q, N_cap >= 1")
+    if tuple(V_cache.shape) != tuple(K_cache.shape):
+        raise ValueError(f"V_cache: shape {tuple(V_cache.shape)} does not match K_cache {tuple(K_cache.shape)}")
+    if Q.dtype != torch.bfloat16:
+        raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16 (decode is bf16 in this version)")
+    for n, t in (("K_cache", K_cache), ("V_cache", V_cache)):
+        if t.dtype != Q.dtype:
+            raise ValueError(f"{n}: dtype {t.dtype}, expected {Q.dtype}")
+    if d not in (64, 128):
+        raise ValueError(f"Q: head_dim {d}, expected 64 or 128")
+    if (H // Hkv) * Nq > DECODE_MAX_ROWS:
+        raise ValueError(f"Q: {H // Hkv} query heads per K/V head x {Nq} query tokens = {(H // Hkv) * Nq} rows, decode takes at most "
+                         f"{DECODE_MAX_ROWS}: that is a prefill chunk, use flash_attention_2_qk_forward")
+    return B, H, Hkv, Nq, Ncap, d
+
+
+def _seqlens_arg(seqlens_k, Q, B):
+    """seqlens_k beside Q: the kernels read it ON THE DEVICE at the time they run (that is what lets one captured graph serve
+    every step), so a host list or a CPU tensor cannot stand in for it."""
+    if not isinstance(seqlens_k, torch.Tensor):
+        raise ValueError(f"seqlens_k must be an int32 device tensor of {B} lengths, got {type(seqlens_k).__name__}: the kernels read "
+                         "the lengths on the device when they run, the host never does; use torch.tensor(..., dtype=torch.int32, device=Q.device)")
+    if seqlens_k.dtype != torch.int32:
+        raise ValueError(f"seqlens_k: dtype {seqlens_k.dtype}, expected torch.int32")
+    if seqlens_k.dim() != 1 or seqlens_k.numel() != B:
+        raise ValueError(f"seqlens_k: shape {tuple(seqlens_k.shape)}, expected ({B},): one length per sequence")
+    if not seqlens_k.is_contiguous():
+        raise ValueError(f"seqlens_k must be contiguous (got stride {tuple(seqlens_k.stride())}; call .contiguous())")
+    if not seqlens_k.is_cuda:
+        raise ValueError("seqlens_k is a CPU tensor: the kernels read the lengths on the device when they run (the host never "
+                         "reads them), so it must live on Q's device")
+    if seqlens_k.device != Q.device:
+        raise ValueError(f"seqlens_k is on {seqlens_k.device}, expected {Q.device}")
+    return seqlens_k
+
+
+def decode_num_splits(B, H_kv, kv_capacity, head_dim):
+    """The split count n_splits=0 stands for (fa2_decode_num_splits): host arithmetic on the capacity, never on a length."""
+    return _capi.lib().fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim)
+
+
+def decode_workspace(B, H, H_kv, N_q, kv_capacity, d, n_splits=0, device="cuda"):
+    """Scratch for flash_attention_2_decode (the splits' fp32 partials): allocate once, pass as workspace= (graph capture)."""
+    return torch.empty(_capi.lib().fa2_decode_workspace_bytes(B, H, H_kv, N_q, kv_capacity, d, n_splits), dtype=torch.uint8, device=device)
+
+
+def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=None, causal=True, sink=None, n_splits=0,
+                             O=None, L=None, workspace=None, stream=None):
+    """O, L = attention of a few new tokens per sequence against a preallocated KV cache (fa2_forward_decode): Q [B, H, N_q, d],
+    K_cache and V_cache [B, H_kv, N_cap, d] (H_kv dividing H, (H / H_kv) N_q <= 32), bf16, d = 64 | 128.  INFERENCE ONLY: there is
+    no autograd and no backward.
+    seqlens_k: int32 [B] DEVICE tensor; sequence b attends keys [0, min(max(seqlens_k[b], 0), N_cap)) of its cache rows (None: all
+    N_cap).  The host never reads it.  The N_q queries are the sequence's last N_q tokens, already in the cache; causal=True masks
+    bottom-right (key j visible to query i iff j <= i + len_b - N_q).  A row without a visible key has O = 0 and L = -inf (L = sink
+    with a sink).  sink: as flash_attention_2_qk_forward.
+    n_splits: how many workgroups share a K/V head's keys, 1..256, or 0 = decode_num_splits(B, H_kv, N_cap, d).  More than one
+    split needs a workspace (decode_workspace); it is allocated per call when omitted -- PASS ONE FOR GRAPH CAPTURE, with O, L and a
+    seqlens_k tensor that is updated in place between replays.
+    The returned (O, L) is what merge_states_forward takes: a cache held in two allocations is two calls (the first with
+    causal=False and no sink, the last with the mask and the sink) and a merge."""
+    B, H, Hkv, Nq, Ncap, d = _decode_shapes(Q, K_cache, V_cache)
+    if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
+        raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
+    if seqlens_k is not None:
+        _seqlens_arg(seqlens_k, Q, B)
+    if sink is not None:
+        _sink_arg(sink, Q, 1)
+    _bhnd(Q, "Q")
+    _like(K_cache, "K_cache", Q, (B, Hkv, Ncap, d), Q.dtype)
+    _like(V_cache, "V_cache", Q, (B, Hkv, Ncap, d), Q.dtype)
+    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    if not scale > 0.0:
+        raise ValueError(f"softmax_scale: {scale}, expected a positive number")
+    O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
+    L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
+    lib = _capi.lib()
+    need = lib.fa2_decode_workspace_bytes(B, H, Hkv, Nq, Ncap, d, n_splits)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
+            raise ValueError("workspace must be a contiguous device tensor on Q's device")
+        if workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace: {workspace.numel() * workspace.element_size()} bytes, {need} needed (decode_workspace)")
+    st = lib.fa2_forward_decode(Q.data_ptr(), K_cache.data_ptr(), V_cache.data_ptr(), None if seqlens_k is None else seqlens_k.data_ptr(),
+                                None if sink is None else sink.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d, scale,
+                                FA2_DTYPE_BF16, 1 if causal else 0, n_splits, None if workspace is None else workspace.data_ptr(),
+                                0 if workspace is None else workspace.numel() * workspace.element_size(), _stream_ptr(stream))
+    check(st, "fa2_forward_decode")
+    return O, L
+
+
 def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=False,
                                   dQ=None, dK=None, dV=None, workspace=None, stream=None, phases=7, sink=None, dsink=None, dL=None):
     """dQ, dK, dV = FA2 backward of flash_attention_2_qk_forward (fa2_backward_qk): dO like O, dK / dV like K / V.  N_q != N_k

@@ -293,7 +293,7 @@ int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void*
  * FA2_ERR_INVALID_SHAPE; head_dim -> FA2_ERR_UNSUPPORTED_HEAD_DIM; fp32 and fp8 -> FA2_ERR_UNSUPPORTED_DTYPE; workspace ->
  * FA2_ERR_WORKSPACE; then (dense rectangle, phases bit 3) FA2_ERR_UNSUPPORTED.
  * NOT COVERED: the single-kernel backward on rectangles, fp32 and fp8, the ring, a paged or non-contiguous KV cache, sliding
- * windows, a split-KV decode kernel (q_len = 1 works but gets one workgroup per head). */
+ * windows.  (One or a few new tokens against a long cache: fa2_forward_decode below.) */
 int fa2_forward_qk(const void* Q, const void* K, const void* V, void* O, float* L,
                    int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
                    int dtype, int causal, void* stream);
@@ -395,6 +395,45 @@ int fa2_merge_states(const void* const* O_parts, const float* const* L_parts, in
 int fa2_merge_states_backward(const void* const* O_parts, const float* const* L_parts, const void* O, const float* L, const void* dO,
                               const float* dL, void* const* dO_parts, float* const* dL_parts, int n_parts, size_t rows, int head_dim,
                               int dtype, void* stream);
+
+/* ---- Decode: one or a few new query tokens per sequence against a preallocated KV cache, the keys split over the GPU.
+ * bf16, head_dim 64 or 128, H_q % H_kv == 0, forward only (inference: there is no backward).
+ * LAYOUT.  Q, O [B][H_q][q_len][d]; K_cache, V_cache [B][H_kv][kv_capacity][d], contiguous; L [B][H_q][q_len] fp32.
+ * seqlens_k: int32 [B] in DEVICE memory, or NULL (every sequence has kv_capacity keys).  Sequence b attends keys [0, len_b) of its
+ * own cache rows, len_b = min(max(seqlens_k[b], 0), kv_capacity): the clamp is done in the kernel, no loop bound and no address
+ * comes from the stored value.  The host never reads seqlens_k, and nothing the host decides depends on it: a captured graph of
+ * this call serves every decode step as the lengths grow.  Cache rows at and beyond len_b may hold anything (NaNs included): they
+ * are read as zeros and never enter a product.
+ * MASK.  The q_len queries are the sequence's LAST q_len tokens, already in the cache: with causal != 0 key j is visible to query i
+ * iff j <= i + len_b - q_len (bottom-right, as everywhere here); causal == 0: every query sees all len_b keys.  A row without a
+ * visible key (len_b == 0, or causal with i + len_b - q_len < 0) has O = 0 and L = -inf.
+ * sink: fp32 [H_q] DEVICE memory or NULL, the semantics of fa2_forward_sink: L' = logaddexp(L, sink[h]), O scaled by exp(L - L');
+ * sink[h] = -inf: no sink for that head; a keyless row has L = sink[h].
+ * WORK SPLIT.  One workgroup per (sequence, K/V head, key split); the M = (H_q / H_kv) q_len query rows of a K/V head share one
+ * 32-row MFMA tile, so a K/V head is streamed ONCE for its whole group.  1 <= M <= 32; a larger M returns FA2_ERR_UNSUPPORTED:
+ * that is a prefill chunk, and fa2_forward_qk takes it.  Split s of n_splits covers keys [s chunk, min((s + 1) chunk, len_b)) with
+ * chunk = roundup(ceil(len_b / n_splits), 128), computed on the device; a short sequence leaves its later splits empty.  With
+ * n_splits > 1 every split writes an fp32 partial (normalised O_s, L_s) into the workspace and a second kernel on the same
+ * stream combines them in ascending s in fp32 (L = logsumexp L_s, O = sum exp(L_s - L) O_s), applies the sink and rounds to bf16
+ * once.  With n_splits == 1 the one kernel writes O and L itself and no workspace is needed.  DETERMINISTIC: plain launches, no
+ * atomics, no communication between workgroups, every sum in a fixed order.  Nothing is allocated, nothing synchronises.
+ * n_splits: 1..256, or 0 = fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim), a pure host function: the smallest s with
+ * B H_kv s >= 256 (the MI355X's compute units), limited so that a split of a full cache keeps at least 256 keys, and to 256.
+ * fa2_decode_workspace_bytes resolves n_splits == 0 the same way; it is 0 for one split, else n_splits B H_q q_len (d + 1) x 4
+ * bytes rounded up to 256.  The workspace must be 16-byte aligned.
+ * (O, L) is what fa2_merge_states takes: a cache held in two allocations is two calls (the first with causal = 0 and no sink, the
+ * last carrying the mask and the sink) and a merge.
+ * STATUS CODES, in this order: NULL Q, K_cache, V_cache, O or L -> FA2_ERR_NULL_POINTER; B, heads, lengths, scale <= 0, H_kv not
+ * dividing H_q, n_splits outside 0..256, a (b, head) cache slab of 2 GiB or more (kv_capacity x head_dim x 2 bytes; the whole
+ * cache may be larger) -> FA2_ERR_INVALID_SHAPE; FA2_ERR_UNSUPPORTED_HEAD_DIM; FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace
+ * NULL, misaligned or too small while the resolved split count is > 1 -> FA2_ERR_WORKSPACE; M > 32 -> FA2_ERR_UNSUPPORTED.
+ * NOT COVERED: paged or block-table caches, [B][N][H][d] layouts, a cache-append kernel (a framework's scatter does it), M > 32,
+ * fp8 or fp32 caches, sliding windows, a backward, the ring. */
+int fa2_decode_num_splits(int B, int H_kv, int kv_capacity, int head_dim);
+size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, int n_splits);
+int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
+                       void* O, float* L, int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
+                       int dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output
