@@ -39,9 +39,16 @@ inline int check_bwd_planes(int B, int H, int rows)
     return (long long)B * H * padded * 8 > 0x7fffffffLL ? FA2_ERR_INVALID_SHAPE : FA2_OK;
 }
 
+// what the bf16-only entry points report: head_dim first, whatever the dtype
+inline int check_bf16(int head_dim, int dtype)
+{
+    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
+    return dtype == FA2_DTYPE_BF16 ? FA2_OK : FA2_ERR_UNSUPPORTED_DTYPE;
+}
+
 inline int check_dim(int d, int dtype)
 {
-    if (dtype == FA2_DTYPE_BF16) return (d == 64 || d == 128) ? FA2_OK : FA2_ERR_UNSUPPORTED_HEAD_DIM;
+    if (dtype == FA2_DTYPE_BF16) return check_bf16(d, dtype);
     if (dtype == FA2_DTYPE_F32) return (d >= 1 && d <= 128) ? FA2_OK : FA2_ERR_UNSUPPORTED_HEAD_DIM;
     if (dtype == FA2_DTYPE_FP8_E4M3) return d == 128 ? FA2_OK : FA2_ERR_UNSUPPORTED_HEAD_DIM;
     return FA2_ERR_UNSUPPORTED_DTYPE;
@@ -109,6 +116,44 @@ inline int varlen_check(const void* plan_host, const void* plan_dev, size_t plan
     return FA2_OK;
 }
 
+// The public entry point that asks: the order in which faults are reported is the asking entry point's (the backward ones
+// through bwd_route, the forward and packed ones through check_request).
+enum class Entry { phases, qk, block, fused, status, plan, forward_gqa, forward_qk, forward_packed, backward_packed };
+
+// What a caller asked for, whichever entry point it came through.  A packed call is one batch (B = 1) of q_len = T_q query and
+// kv_len = T_k key rows with a plan.  A new per-problem option is a field here, a rule in check_request (or bwd_route) and a
+// field of the kernel's struct in fa2_launch.h.
+struct Request {
+    int B = 1, H = 0, kv_heads = 0;      // kv_heads 0: an entry point without grouped heads (as many K/V heads as query heads)
+    int q_len = 0, kv_len = 0, q_stride = 0, kv_stride = 0, q_row0 = 0;      // strides 0: dense slabs of q_len / kv_len rows
+    int head_dim = 0, dtype = FA2_DTYPE_BF16;
+    float scale = 1.0f;
+    int causal = 0, shift = 0, phases = 0;
+    const void* ws = nullptr; size_t ws_bytes = 0;
+    const float* sink = nullptr; float* dsink = nullptr; const float* dL = nullptr;
+    bool need_sinks = false;      // fa2_backward_sink and its packed form: sink and dsink, both (otherwise: both or neither)
+    const void *plan_host = nullptr, *plan_dev = nullptr; size_t plan_bytes = 0; bool one_list = false;
+    bool ws_short(size_t need) const { return !ws || ws_bytes < need; }
+};
+
+// (H_kv = 0 from a grouped entry point must not read as "no grouped heads": -1 is as invalid)
+inline int grouped(int H_kv) { return H_kv ? H_kv : -1; }
+inline bool heads_divide(int H_q, int H_kv) { return H_kv > 0 && H_q % H_kv == 0; }
+
+// The checks of every grouped bf16 entry point, in the order its rung of the interface reports them: fa2_forward_gqa the dtype
+// before the head_dim, everything after it the head_dim first; the packed calls their plan (-> *plan) in between.
+inline int check_request(Entry entry, const Request& q, VarlenHeader* plan = nullptr)
+{
+    int st = check_common(q.B, q.H, q.q_len, q.head_dim, q.scale);
+    if (!st) st = check_common(q.B, q.H, q.kv_len, q.head_dim, q.scale);
+    if (st) return st;
+    if (!heads_divide(q.H, q.kv_heads)) return FA2_ERR_INVALID_SHAPE;
+    if (entry == Entry::backward_packed && (st = check_bwd_planes(q.B, q.H, q.q_len))) return st;
+    if (plan && (st = varlen_check(q.plan_host, q.plan_dev, q.plan_bytes, q.q_len, q.kv_len, q.one_list, q.H, plan))) return st;
+    if (entry == Entry::forward_gqa && q.dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    return check_bf16(q.head_dim, q.dtype);
+}
+
 }  // namespace
 
 extern "C" {
@@ -141,30 +186,43 @@ const char* fa2_status_string(int s)
     return "unknown status";
 }
 
-// the bf16 forward of H query heads against H / kv_group K/V heads (fa2_forward: kv_group = 1)
-// (kv_len = 0: seq_len keys.  Another kv_len: the causal mask is aligned bottom-right, key j visible to query i iff
-// j <= i + kv_len - seq_len)
-static int forward_bf16(const void* Q, const void* K, const void* V, void* O, float* L, int B, int H, int kv_group, int seq_len,
-                        int head_dim, float softmax_scale, int causal, void* stream, int kv_len = 0, const float* sink = nullptr)
+// Every bf16 forward but the resumable steps: the checks in the order of the asking entry point, then the dense launch or
+// (Entry::forward_packed, with a plan) the packed one.  Dense: the causal mask is aligned bottom-right, key j visible to query i
+// iff j <= i + kv_len - q_len.
+struct FwdTensors { const void *Q, *K, *V; void* O; float* L; };
+static int forward_bf16(Entry entry, const FwdTensors& t, const Request& q, void* stream)
 {
-    fa2::FwdArgs a{};
-    a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L; a.Oacc = nullptr; a.M = nullptr;
-    a.BH = B * H; a.Nq = seq_len; a.Nk = kv_len ? kv_len : seq_len; a.d = head_dim; a.scale = softmax_scale;
-    a.causal = causal ? 1 : 0; a.causal_shift = causal ? a.Nk - a.Nq : 0; a.resume = 0; a.finalize = 1; a.kv_group = kv_group;
-    a.sink = sink; a.sink_heads = H;
-    return hip_status(fa2::launch_fwd1_bf16(a, (hipStream_t)stream));
+    const bool packed = entry == Entry::forward_packed;
+    if (!t.Q || !t.K || !t.V || !t.O || !t.L || (packed && (!q.plan_host || !q.plan_dev))) return FA2_ERR_NULL_POINTER;
+    VarlenHeader h;
+    if (const int st = check_request(entry, q, packed ? &h : nullptr)) return st;
+    fa2::VarlenFwdArgs v{};
+    fa2::FwdArgs& a = v.a;
+    a.Q = t.Q; a.K = t.K; a.V = t.V; a.O = t.O; a.L = t.L;
+    a.BH = q.B * q.H; a.d = q.head_dim; a.scale = q.scale; a.causal = q.causal ? 1 : 0; a.finalize = 1;
+    a.kv_group = q.H / q.kv_heads; a.sink = q.sink; a.sink_heads = q.H;
+    if (!packed) {
+        a.Nq = q.q_len; a.Nk = q.kv_len; a.causal_shift = q.causal ? a.Nk - a.Nq : 0;
+        return hip_status(fa2::launch_fwd1_bf16(a, (hipStream_t)stream));
+    }
+    a.q_hs = q.q_len; a.k_hs = q.kv_len;      // Nq, Nk and the mask's shift are per item
+    v.items = reinterpret_cast<const fa2::VarlenItem*>((const char*)q.plan_dev + sizeof(VarlenHeader));
+    v.n_items = h.n_row_items;
+    return hip_status(fa2::launch_fwd1_varlen_bf16(v, (hipStream_t)stream));
 }
 
 int fa2_forward(const void* Q, const void* K, const void* V, void* O, float* L,
                 int B, int H, int seq_len, int head_dim, float softmax_scale,
                 int dtype, int causal, void* stream)
 {
+    if (dtype == FA2_DTYPE_BF16)      // fa2_forward_gqa's problem with as many K/V heads as query heads, and its checks
+        return forward_bf16(Entry::forward_gqa, {Q, K, V, O, L}, {.B = B, .H = H, .kv_heads = H, .q_len = seq_len, .kv_len = seq_len,
+                            .head_dim = head_dim, .scale = softmax_scale, .causal = causal}, stream);
     if (!Q || !K || !V || !O || !L) return FA2_ERR_NULL_POINTER;
     int st = check_common(B, H, seq_len, head_dim, softmax_scale);
     if (st) return st;
     st = check_dim(head_dim, dtype);
     if (st) return st;
-    if (dtype == FA2_DTYPE_BF16) return forward_bf16(Q, K, V, O, L, B, H, 1, seq_len, head_dim, softmax_scale, causal, stream);
     if (dtype == FA2_DTYPE_FP8_E4M3) {      // workspace from the stream-ordered allocator
         const size_t need = fa2_forward_fp8_workspace_bytes(B, H, seq_len, head_dim);
         void* ws = nullptr;
@@ -185,93 +243,25 @@ int fa2_forward_gqa(const void* Q, const void* K, const void* V, void* O, float*
                     int B, int H_q, int H_kv, int seq_len, int head_dim, float softmax_scale,
                     int dtype, int causal, void* stream)
 {
-    if (!Q || !K || !V || !O || !L) return FA2_ERR_NULL_POINTER;
-    int st = check_common(B, H_q, seq_len, head_dim, softmax_scale);
-    if (st) return st;
-    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;      // grouped-query attention: bf16 in this version
-    st = check_dim(head_dim, dtype);
-    if (st) return st;
-    return forward_bf16(Q, K, V, O, L, B, H_q, H_q / H_kv, seq_len, head_dim, softmax_scale, causal, stream);
+    return forward_bf16(Entry::forward_gqa, {Q, K, V, O, L}, {.B = B, .H = H_q, .kv_heads = grouped(H_kv), .q_len = seq_len,
+                        .kv_len = seq_len, .head_dim = head_dim, .dtype = dtype, .scale = softmax_scale, .causal = causal}, stream);
 }
 
 // ---- packed variable-length batches ---------------------------------------------------------------------------------------
-size_t fa2_varlen_plan_bytes(int n_seqs, int total_rows)
-{
-    if (n_seqs < 1 || total_rows < 1) return 0;
-    // a sequence of len rows has ceil(len / 256) <= len / 256 + 1 blocks, and only non-empty sequences have any
-    const long long most = (long long)total_rows / kVarlenBlock + std::min(n_seqs, total_rows);
-    return varlen_bytes(most, most);
-}
-
-int fa2_varlen_plan_build(const int* cu_seqlens_host, int n_seqs, void* plan_host, size_t plan_bytes)
-{
-    if (!cu_seqlens_host || !plan_host) return FA2_ERR_NULL_POINTER;
-    if (n_seqs < 1 || cu_seqlens_host[0] != 0) return FA2_ERR_INVALID_SHAPE;
-    for (int i = 0; i < n_seqs; ++i)
-        if (cu_seqlens_host[i + 1] < cu_seqlens_host[i]) return FA2_ERR_INVALID_SHAPE;
-    const int total = cu_seqlens_host[n_seqs];
-    if (total < 1 || total > kVarlenMaxRows) return FA2_ERR_INVALID_SHAPE;
-    // sequences by descending length, ties by index; empty ones have no work
-    std::vector<int> order(n_seqs);
-    std::iota(order.begin(), order.end(), 0);
-    const auto len = [&](int i) { return cu_seqlens_host[i + 1] - cu_seqlens_host[i]; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len(a) > len(b); });
-    long long n_items = 0;
-    for (int i = 0; i < n_seqs; ++i) n_items += (len(i) + kVarlenBlock - 1) / kVarlenBlock;
-    if (plan_bytes < varlen_bytes(n_items, n_items)) return FA2_ERR_WORKSPACE;
-    const VarlenHeader h{kVarlenMagic, kVarlenVersion, n_seqs, total, (int)n_items, (int)n_items, len(order[0]), 0};
-    memcpy(plan_host, &h, sizeof h);
-    // (written through memcpy: the caller's buffer has no alignment beyond a byte's)
-    char* out = (char*)plan_host + sizeof h;
-    const auto put = [&](int seq, int block) {
-        const int r0 = cu_seqlens_host[seq];
-        const fa2::VarlenItem it{r0, r0, len(seq), len(seq), block};
-        memcpy(out, &it, sizeof it);
-        out += sizeof it;
-    };
-    for (int seq : order)      // row blocks: descending within a sequence (the heaviest first under a causal mask)
-        for (int b = (len(seq) + kVarlenBlock - 1) / kVarlenBlock - 1; b >= 0; --b) put(seq, b);
-    for (int seq : order)      // key blocks: ascending (key block 0 is the heaviest)
-        for (int b = 0; b < (len(seq) + kVarlenBlock - 1) / kVarlenBlock; ++b) put(seq, b);
-    return FA2_OK;
-}
-
-int fa2_forward_qk(const void* Q, const void* K, const void* V, void* O, float* L,
-                   int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
-                   int dtype, int causal, void* stream)
-{
-    if (!Q || !K || !V || !O || !L) return FA2_ERR_NULL_POINTER;
-    int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
-    if (!st) st = check_common(B, H_q, kv_len, head_dim, softmax_scale);
-    if (st) return st;
-    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
-    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;      // as the packed calls: head_dim, then dtype
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
-    return forward_bf16(Q, K, V, O, L, B, H_q, H_q / H_kv, q_len, head_dim, softmax_scale, causal, stream, kv_len);
-}
-
-// ---- attention sinks: the _qk problems with one learned logit per query head in every row's softmax (include/fa2_mi355x.h)
-int fa2_forward_sink(const void* Q, const void* K, const void* V, const float* sink, void* O, float* L,
-                     int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
-                     int dtype, int causal, void* stream)
-{
-    if (!Q || !K || !V || !sink || !O || !L) return FA2_ERR_NULL_POINTER;
-    int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
-    if (!st) st = check_common(B, H_q, kv_len, head_dim, softmax_scale);
-    if (st) return st;
-    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
-    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
-    return forward_bf16(Q, K, V, O, L, B, H_q, H_q / H_kv, q_len, head_dim, softmax_scale, causal, stream, kv_len, sink);
-}
+size_t fa2_varlen_plan_bytes(int n_seqs, int total_rows) { return fa2_varlen_plan_bytes_qk(n_seqs, total_rows, total_rows); }
 
 size_t fa2_varlen_plan_bytes_qk(int n_seqs, int total_q, int total_k)
 {
     if (n_seqs < 1 || total_q < 1 || total_k < 1) return 0;
-    const long long n_row = (long long)total_q / kVarlenBlock + std::min(n_seqs, total_q);      // as fa2_varlen_plan_bytes, per side
+    // a sequence of len rows has ceil(len / 256) <= len / 256 + 1 blocks, and only non-empty sequences have any
+    const long long n_row = (long long)total_q / kVarlenBlock + std::min(n_seqs, total_q);
     const long long n_key = (long long)total_k / kVarlenBlock + std::min(n_seqs, total_k);
     return varlen_bytes(n_row, n_key);
+}
+
+int fa2_varlen_plan_build(const int* cu_seqlens_host, int n_seqs, void* plan_host, size_t plan_bytes)
+{
+    return fa2_varlen_plan_build_qk(cu_seqlens_host, nullptr, n_seqs, plan_host, plan_bytes);
 }
 
 int fa2_varlen_plan_build_qk(const int* cu_seqlens_q_host, const int* cu_seqlens_k_host, int n_seqs, void* plan_host, size_t plan_bytes)
@@ -279,8 +269,9 @@ int fa2_varlen_plan_build_qk(const int* cu_seqlens_q_host, const int* cu_seqlens
     const int *cq = cu_seqlens_q_host, *ck = cu_seqlens_k_host;
     if (!cq || !plan_host) return FA2_ERR_NULL_POINTER;
     if (n_seqs < 1) return FA2_ERR_INVALID_SHAPE;
-    // no key list, or the query list again: the one-sided plan, byte for byte
-    if (!ck || std::equal(cq, cq + n_seqs + 1, ck)) return fa2_varlen_plan_build(cq, n_seqs, plan_host, plan_bytes);
+    // no key list, or the query list again: the one-sided plan -- the two-sided plan of (cq, cq) with total_k = 0 in its header
+    const bool one_sided = !ck || std::equal(cq, cq + n_seqs + 1, ck);
+    if (one_sided) ck = cq;
     for (const int* cu : {cq, ck}) {
         if (cu[0] != 0) return FA2_ERR_INVALID_SHAPE;
         for (int i = 0; i < n_seqs; ++i)
@@ -290,7 +281,7 @@ int fa2_varlen_plan_build_qk(const int* cu_seqlens_q_host, const int* cu_seqlens
     const auto len_q = [&](int i) { return cq[i + 1] - cq[i]; };
     const auto len_k = [&](int i) { return ck[i + 1] - ck[i]; };
     const auto blocks = [](int len) { return (len + kVarlenBlock - 1) / kVarlenBlock; };
-    // sequences by descending work (len_q x len_k), ties by index: the one-sided order when the lengths are equal.  A sequence
+    // sequences by descending work (len_q x len_k), ties by index: by descending length in a one-sided plan.  A sequence
     // with one empty side has no product to form but still has outputs to write (O = 0, L = -inf; dK = dV = 0): it comes last
     std::vector<int> order(n_seqs);
     std::iota(order.begin(), order.end(), 0);
@@ -304,61 +295,57 @@ int fa2_varlen_plan_build_qk(const int* cu_seqlens_q_host, const int* cu_seqlens
         max_len = std::max(max_len, len_q(i));
     }
     if (plan_bytes < varlen_bytes(n_row, n_key)) return FA2_ERR_WORKSPACE;
-    const VarlenHeader h{kVarlenMagic, kVarlenVersion, n_seqs, cq[n_seqs], (int)n_row, (int)n_key, max_len, ck[n_seqs]};
+    const VarlenHeader h{kVarlenMagic, kVarlenVersion, n_seqs, cq[n_seqs], (int)n_row, (int)n_key, max_len, one_sided ? 0 : ck[n_seqs]};
     memcpy(plan_host, &h, sizeof h);
+    // (written through memcpy: the caller's buffer has no alignment beyond a byte's)
     char* out = (char*)plan_host + sizeof h;
     const auto put = [&](int seq, int block) {
         const fa2::VarlenItem it{cq[seq], ck[seq], len_q(seq), len_k(seq), block};
         memcpy(out, &it, sizeof it);
         out += sizeof it;
     };
-    for (int seq : order)      // row blocks of every sequence with a query (len_k = 0 included), descending
-        for (int b = blocks(len_q(seq)) - 1; b >= 0; --b) put(seq, b);
-    for (int seq : order)      // key blocks of every sequence with a key (len_q = 0 included), ascending
+    for (int seq : order)      // row blocks of every sequence with a query (len_k = 0 included), descending within a sequence
+        for (int b = blocks(len_q(seq)) - 1; b >= 0; --b) put(seq, b);      // (the heaviest first under a causal mask)
+    for (int seq : order)      // key blocks of every sequence with a key (len_q = 0 included), ascending (block 0 is the heaviest)
         for (int b = 0; b < blocks(len_k(seq)); ++b) put(seq, b);
     return FA2_OK;
 }
 
-// both packed forward entry points (one_list: fa2_forward_varlen, one T for both sides)
-static int forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
-                          int H_q, int H_kv, int total_q, int total_k, bool one_list, int head_dim, float softmax_scale, int dtype,
-                          int causal, const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream,
-                          const float* sink = nullptr)
+int fa2_forward_qk(const void* Q, const void* K, const void* V, void* O, float* L,
+                   int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                   int dtype, int causal, void* stream)
 {
-    if (!Q || !K || !V || !O || !L || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
-    int st = check_common(1, H_q, total_q, head_dim, softmax_scale);
-    if (!st) st = check_common(1, H_q, total_k, head_dim, softmax_scale);
-    if (st) return st;
-    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
-    VarlenHeader h;
-    if ((st = varlen_check(plan_host, plan_dev, plan_bytes, total_q, total_k, one_list, H_q, &h))) return st;
-    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;      // whatever the dtype: head_dim comes first
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
-    fa2::VarlenFwdArgs v{};
-    fa2::FwdArgs& a = v.a;
-    a.Q = Q; a.K = K; a.V = V; a.O = O; a.L = L;
-    a.BH = H_q; a.d = head_dim; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.finalize = 1;
-    a.q_hs = total_q; a.k_hs = total_k; a.kv_group = H_q / H_kv;
-    a.sink = sink; a.sink_heads = H_q;
-    v.items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
-    v.n_items = h.n_row_items;
-    return hip_status(fa2::launch_fwd1_varlen_bf16(v, (hipStream_t)stream));
+    return forward_bf16(Entry::forward_qk, {Q, K, V, O, L}, {.B = B, .H = H_q, .kv_heads = grouped(H_kv), .q_len = q_len, .kv_len = kv_len,
+                        .head_dim = head_dim, .dtype = dtype, .scale = softmax_scale, .causal = causal}, stream);
 }
 
+// ---- attention sinks: the _qk problems with one learned logit per query head in every row's softmax (include/fa2_mi355x.h)
+int fa2_forward_sink(const void* Q, const void* K, const void* V, const float* sink, void* O, float* L,
+                     int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
+                     int dtype, int causal, void* stream)
+{
+    if (!sink) return FA2_ERR_NULL_POINTER;
+    return forward_bf16(Entry::forward_qk, {Q, K, V, O, L}, {.B = B, .H = H_q, .kv_heads = grouped(H_kv), .q_len = q_len, .kv_len = kv_len,
+                        .head_dim = head_dim, .dtype = dtype, .scale = softmax_scale, .causal = causal, .sink = sink}, stream);
+}
+
+// the packed forward entry points (one_list: fa2_forward_varlen, one T for both sides, which refuses a two-sided plan)
 int fa2_forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
                        int H_q, int H_kv, int total_rows, int head_dim, float softmax_scale, int dtype, int causal,
                        const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
 {
-    return forward_varlen(Q, K, V, O, L, H_q, H_kv, total_rows, total_rows, true, head_dim, softmax_scale, dtype, causal, plan_host,
-                          plan_dev, plan_bytes, stream);
+    return forward_bf16(Entry::forward_packed, {Q, K, V, O, L}, {.H = H_q, .kv_heads = grouped(H_kv), .q_len = total_rows,
+                        .kv_len = total_rows, .head_dim = head_dim, .dtype = dtype, .scale = softmax_scale, .causal = causal,
+                        .plan_host = plan_host, .plan_dev = plan_dev, .plan_bytes = plan_bytes, .one_list = true}, stream);
 }
 
 int fa2_forward_varlen_qk(const void* Q, const void* K, const void* V, void* O, float* L,
                           int H_q, int H_kv, int total_q, int total_k, int head_dim, float softmax_scale, int dtype, int causal,
                           const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
 {
-    return forward_varlen(Q, K, V, O, L, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
-                          plan_dev, plan_bytes, stream);
+    return forward_bf16(Entry::forward_packed, {Q, K, V, O, L}, {.H = H_q, .kv_heads = grouped(H_kv), .q_len = total_q,
+                        .kv_len = total_k, .head_dim = head_dim, .dtype = dtype, .scale = softmax_scale, .causal = causal,
+                        .plan_host = plan_host, .plan_dev = plan_dev, .plan_bytes = plan_bytes}, stream);
 }
 
 int fa2_forward_varlen_sink(const void* Q, const void* K, const void* V, const float* sink, void* O, float* L,
@@ -366,8 +353,9 @@ int fa2_forward_varlen_sink(const void* Q, const void* K, const void* V, const f
                             const void* plan_host, const void* plan_dev, size_t plan_bytes, void* stream)
 {
     if (!sink) return FA2_ERR_NULL_POINTER;
-    return forward_varlen(Q, K, V, O, L, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
-                          plan_dev, plan_bytes, stream, sink);
+    return forward_bf16(Entry::forward_packed, {Q, K, V, O, L}, {.H = H_q, .kv_heads = grouped(H_kv), .q_len = total_q,
+                        .kv_len = total_k, .head_dim = head_dim, .dtype = dtype, .scale = softmax_scale, .causal = causal,
+                        .sink = sink, .plan_host = plan_host, .plan_dev = plan_dev, .plan_bytes = plan_bytes}, stream);
 }
 
 size_t fa2_forward_fp8_workspace_bytes(int B, int H, int seq_len, int head_dim)
@@ -455,7 +443,6 @@ static bool bwd_fused_allowed()
     return allowed;
 }
 
-enum class Entry { phases, qk, block, fused, status, plan };      // the public entry point that asks
 enum class Path { none, f32, two_kernel, single };
 struct Route {
     int status = FA2_OK;
@@ -467,48 +454,55 @@ struct Route {
     const char* why = "";         // fa2_backward_plan's reason
 };
 
-// The one place the backward is routed (the rule: include/fa2_mi355x.h, fa2_backward): validation in the order of the asking
-// entry point, then what to run, its arguments and its workspace.  `t` holds the nine tensors (none for status and plan);
-// `phases` is fa2_backward_fused's mode.  `kv_heads`: 0 = as many K/V heads as query heads (every multi-head entry point); anything
-// else comes from the grouped-query entry points (phases, qk and plan only), is validated here and changes nothing about WHICH
-// implementation runs -- rule (a) depends on seq_len and head_dim alone.
-static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int kv_heads, int q_len, int kv_len, int q_stride, int kv_stride,
-                       int q_row0, int d, int dtype, int causal, int shift, float scale, int phases, const void* ws, size_t ws_bytes)
+static bool any_null(const fa2::BwdArgs& t) { return !t.Q || !t.K || !t.V || !t.O || !t.L || !t.dO || !t.dQ || !t.dK || !t.dV; }
+
+// The arguments of a bf16 backward launch, dense or packed, from its nine tensors `t`, the request and the workspace's planes
+// (phases and reserve_cus are the caller's)
+static void bwd_args(fa2::BwdArgs& a, const fa2::BwdArgs& t, const Request& q, const BwdWs& ws)
+{
+    a.Q = t.Q; a.K = t.K; a.V = t.V; a.O = t.O; a.dO = t.dO; a.L = t.L; a.dQ = t.dQ; a.dK = t.dK; a.dV = t.dV;
+    a.D = ws.D; a.RC = ws.RC; a.BH = q.B * q.H; a.Nq = q.q_len; a.Nk = q.kv_len; a.d = q.head_dim;
+    a.q_hs = q.q_stride ? q.q_stride : q.q_len; a.k_hs = q.kv_stride ? q.kv_stride : q.kv_len; a.q_row0 = q.q_row0;
+    a.scale = q.scale; a.causal = q.causal ? 1 : 0; a.causal_shift = q.causal ? q.shift : 0;
+    a.kv_group = q.kv_heads > 0 ? q.H / q.kv_heads : 1;
+}
+
+// Where every DENSE backward is routed (the rule: include/fa2_mi355x.h, fa2_backward): validation in the order of the asking
+// entry point, then what to run, its arguments and its workspace.  The packed backward (backward_varlen) has one implementation
+// and nothing to route: it shares check_request and bwd_args with this.  `t` holds the nine tensors (none for status and plan);
+// q.phases is fa2_backward_fused's mode.  q.kv_heads != 0 comes from the grouped-query entry points (phases, qk and plan only), is
+// validated here and changes nothing about WHICH implementation runs -- rule (a) depends on seq_len and head_dim alone.
+static Route bwd_route(Entry entry, const fa2::BwdArgs& t, const Request& q)
 {
     Route r;
     const auto fail = [&r](int st) { r.status = st; return r; };
     const auto device_ok = [&r] { return fa2::bwd_fused_device_ok(&r.why); };
     const auto env_and_device_ok = [&] { return bwd_fused_allowed() && device_ok(); };      // rules (b) and (c)
-    if (entry <= Entry::fused && (!t.Q || !t.K || !t.V || !t.O || !t.L || !t.dO || !t.dQ || !t.dK || !t.dV))
-        return fail(FA2_ERR_NULL_POINTER);
-    const int q_hs = q_stride ? q_stride : q_len, k_hs = kv_stride ? kv_stride : kv_len;
-    const bool gqa = kv_heads != 0;           // asked through a grouped-query entry point (bf16 only, whatever the group size)
-    const auto kv_heads_ok = [&] { return kv_heads > 0 && H % kv_heads == 0; };
-    const int kv_group = gqa && kv_heads > 0 && H > 0 ? H / kv_heads : 1;
+    if (entry <= Entry::fused && any_null(t)) return fail(FA2_ERR_NULL_POINTER);
+    const int B = q.B, H = q.H, q_len = q.q_len, kv_len = q.kv_len, d = q.head_dim, dtype = q.dtype, phases = q.phases;
+    const int q_hs = q.q_stride ? q.q_stride : q_len, k_hs = q.kv_stride ? q.kv_stride : kv_len;
+    const bool gqa = q.kv_heads != 0;           // asked through a grouped-query entry point (bf16 only, whatever the group size)
     switch (entry) {
     case Entry::qk:          // fa2_backward_qk: q_len queries against kv_len keys, grouped or not, bf16
-        if ((r.status = check_common(B, H, q_len, d, scale)) || (r.status = check_common(B, H, kv_len, d, scale))) return r;
-        if (!kv_heads_ok()) return fail(FA2_ERR_INVALID_SHAPE);
-        if (d != 64 && d != 128) return fail(FA2_ERR_UNSUPPORTED_HEAD_DIM);      // as the packed calls: head_dim, then dtype
-        if (dtype != FA2_DTYPE_BF16) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
+        if ((r.status = check_request(entry, q))) return r;
         if (q_len != kv_len) {      // a rectangle: the two deterministic kernels, whatever the shape
             if ((r.status = check_bwd_planes(B, H, q_len))) return r;
-            r.ws = bwd_ws(ws, B, H, q_len, d, dtype);      // D and the two row-constant planes over [B][H][q_len], nothing else
+            r.ws = bwd_ws(q.ws, B, H, q_len, d, dtype);      // D and the two row-constant planes over [B][H][q_len], nothing else
             r.ws.single = false; r.ws.bytes = r.ws.base_bytes;
-            if (!ws || ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
+            if (q.ws_short(r.ws.bytes)) return fail(FA2_ERR_WORKSPACE);
             if (phases & 8) return fail(FA2_ERR_UNSUPPORTED);      // the single kernel takes no rectangle here
             r.path = Path::two_kernel; r.args.phases = phases & 7;
             break;
         }
         [[fallthrough]];     // equal lengths: fa2_backward_gqa's problem -- its rule, its workspace, its launches
     case Entry::phases:      // phases: 1 = D and the row constants, 2 = dQ kernel, 4 = dK/dV kernel, 8 = the single kernel
-        if ((r.status = check_common(B, H, q_len, d, scale))) return r;
-        if (gqa && !kv_heads_ok()) return fail(FA2_ERR_INVALID_SHAPE);
+        if ((r.status = check_common(B, H, q_len, d, q.scale))) return r;
+        if (gqa && !heads_divide(H, q.kv_heads)) return fail(FA2_ERR_INVALID_SHAPE);
         if (dtype == FA2_DTYPE_FP8_E4M3) return fail(FA2_ERR_UNSUPPORTED_DTYPE);      // fp8 is forward only
         if (gqa && dtype != FA2_DTYPE_BF16) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
         if ((r.status = check_dim(d, dtype))) return r;
-        r.ws = bwd_ws(ws, B, H, q_len, d, dtype, kv_group);
-        if (!ws || ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
+        r.ws = bwd_ws(q.ws, B, H, q_len, d, dtype, gqa ? H / q.kv_heads : 1);
+        if (q.ws_short(r.ws.bytes)) return fail(FA2_ERR_WORKSPACE);
         if (dtype == FA2_DTYPE_F32) { r.path = Path::f32; r.args.phases = phases & 7; break; }
         if ((r.status = check_bwd_planes(B, H, q_len))) return r;
         // bit 3 does not combine with bits 1 and 2 (two ways of computing the same outputs); 7 takes the single kernel where
@@ -521,19 +515,19 @@ static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int kv_
         }
         break;
     case Entry::block: {
-        r.status = check_common(B, H, q_len, d, scale);
-        if (!r.status) r.status = check_common(B, H, kv_len > 0 ? kv_len : 1, d, scale);
-        if (!r.status) r.status = check_common(B, H, q_hs > 0 ? q_hs : 1, d, scale);
+        r.status = check_common(B, H, q_len, d, q.scale);
+        if (!r.status) r.status = check_common(B, H, kv_len > 0 ? kv_len : 1, d, q.scale);
+        if (!r.status) r.status = check_common(B, H, q_hs > 0 ? q_hs : 1, d, q.scale);
         if (r.status) return r;
-        if (kv_len <= 0 || q_row0 < 0 || q_hs < q_row0 + q_len || k_hs < kv_len) return fail(FA2_ERR_INVALID_SHAPE);
+        if (kv_len <= 0 || q.q_row0 < 0 || q_hs < q.q_row0 + q_len || k_hs < kv_len) return fail(FA2_ERR_INVALID_SHAPE);
         if ((r.status = check_bwd_planes(B, H, q_hs))) return r;
         if (dtype != FA2_DTYPE_BF16) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
         if ((r.status = check_dim(d, dtype))) return r;
-        r.ws = bwd_ws(ws, B, H, q_hs, d, dtype);      // the square problem's layout for q_hs rows, whatever the block
-        if (!ws || ws_bytes < r.ws.base_bytes) return fail(FA2_ERR_WORKSPACE);
-        const bool ctl = r.ws.single && ws_bytes >= r.ws.bytes;      // room for the running sums and a control block
-        const bool square = q_len == kv_len && q_hs == q_len && k_hs == kv_len && q_row0 == 0 && (!causal || shift == 0);
-        const bool rect = !causal && d == 128 && q_len % 32 == 0 && q_len >= 512 && kv_len % 256 == 0 && kv_len <= fused_npad(q_hs);
+        r.ws = bwd_ws(q.ws, B, H, q_hs, d, dtype);      // the square problem's layout for q_hs rows, whatever the block
+        if (q.ws_short(r.ws.base_bytes)) return fail(FA2_ERR_WORKSPACE);
+        const bool ctl = r.ws.single && q.ws_bytes >= r.ws.bytes;      // room for the running sums and a control block
+        const bool square = q_len == kv_len && q_hs == q_len && k_hs == kv_len && q.q_row0 == 0 && (!q.causal || q.shift == 0);
+        const bool rect = !q.causal && d == 128 && q_len % 32 == 0 && q_len >= 512 && kv_len % 256 == 0 && kv_len <= fused_npad(q_hs);
         if ((phases & 6) == 6 && (square || rect) && ctl && env_and_device_ok()) {
             r.path = Path::single; r.args.phases = 8 | (phases & 1);
             // bits 8..15: how many CUs to leave (FA2_PHASE_LEAVE_CUS(n)); 0 there = the default of 16
@@ -544,26 +538,26 @@ static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int kv_
         break;
     }
     case Entry::fused:
-        if ((r.status = check_common(B, H, q_len, d, scale)) || (r.status = check_bwd_planes(B, H, q_len))) return r;
-        r.ws = bwd_ws(ws, B, H, q_len, d, FA2_DTYPE_BF16);
+        if ((r.status = check_common(B, H, q_len, d, q.scale)) || (r.status = check_bwd_planes(B, H, q_len))) return r;
+        r.ws = bwd_ws(q.ws, B, H, q_len, d, FA2_DTYPE_BF16);
         if (!r.ws.single || (phases != 0 && phases != 1)) return fail(FA2_ERR_UNSUPPORTED);
         if (phases == 0 && (q_len % 256 != 0 || d != 128)) return fail(FA2_ERR_UNSUPPORTED);      // the atomics form: d = 128, aligned
         if (phases == 1 && !device_ok()) return fail(FA2_ERR_UNSUPPORTED);
-        if (!ws || ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
+        if (q.ws_short(r.ws.bytes)) return fail(FA2_ERR_WORKSPACE);
         r.path = Path::single; r.mode = phases; r.args.phases = 9;
         break;
     case Entry::status:      // Path::single: read the error word.  Where this process never runs the single kernel (shape,
                              // environment or device) the caller's buffer is not to be trusted: Path::none, drain the stream
-        if (!ws) return fail(FA2_ERR_NULL_POINTER);
+        if (!q.ws) return fail(FA2_ERR_NULL_POINTER);
         if (B <= 0 || H <= 0 || q_len <= 0) return fail(FA2_ERR_INVALID_SHAPE);
-        r.ws = bwd_ws(ws, B, H, q_len, d, dtype);
+        r.ws = bwd_ws(q.ws, B, H, q_len, d, dtype);
         if (!r.ws.single || !env_and_device_ok()) break;
-        if (ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
+        if (q.ws_bytes < r.ws.bytes) return fail(FA2_ERR_WORKSPACE);
         r.path = Path::single;
         break;
     case Entry::plan:
         if (B <= 0 || H <= 0 || q_len <= 0) return fail(FA2_ERR_INVALID_SHAPE);
-        if (gqa && !kv_heads_ok()) return fail(FA2_ERR_INVALID_SHAPE);
+        if (gqa && !heads_divide(H, q.kv_heads)) return fail(FA2_ERR_INVALID_SHAPE);
         if (dtype == FA2_DTYPE_FP8_E4M3 || (gqa && dtype != FA2_DTYPE_BF16)) return fail(FA2_ERR_UNSUPPORTED_DTYPE);
         if ((r.status = check_dim(d, dtype))) return r;
         r.path = dtype == FA2_DTYPE_F32 ? Path::f32 : Path::two_kernel;
@@ -575,27 +569,38 @@ static Route bwd_route(Entry entry, const fa2::BwdArgs& t, int B, int H, int kv_
         else if (!bwd_fused_allowed()) r.why = "two kernels: FA2_BACKWARD_PATH=two_kernel";
         else if (device_ok()) r.path = Path::single;
         return r;
+    default: return fail(FA2_ERR_UNSUPPORTED);      // the forward and packed entries do not come here
     }
-    fa2::BwdArgs& a = r.args;
-    a.Q = t.Q; a.K = t.K; a.V = t.V; a.O = t.O; a.dO = t.dO; a.L = t.L; a.dQ = t.dQ; a.dK = t.dK; a.dV = t.dV;
-    a.D = r.ws.D; a.RC = r.ws.RC; a.BH = B * H; a.Nq = q_len; a.Nk = kv_len; a.d = d;
-    a.q_hs = q_hs; a.k_hs = k_hs; a.q_row0 = q_row0; a.scale = scale; a.causal = causal ? 1 : 0; a.causal_shift = causal ? shift : 0;
-    a.kv_group = kv_group;
+    bwd_args(r.args, t, q, r.ws);
     return r;
 }
 
-// sg: the attention sinks and their gradient (fa2_backward_sink), computed with phase bit 0 on either bf16 path
-static int bwd_launch(const Route& r, void* stream, const fa2::SinkGrad* sg = nullptr)
+// The sinks and the gradient of L a backward was handed, as the launchers take them beside BwdArgs (phase bit 0 computes with
+// them on either bf16 path; nullptr: a call without either).  fa2_backward_sink needs both sinks, fa2_backward_lse both or
+// neither; kernel 0 alone reads dL.
+struct Sinks { int status; bool any; fa2::SinkGrad sg; const fa2::SinkGrad* ptr() const { return any ? &sg : nullptr; } };
+static Sinks sink_grad(const Request& q)
+{
+    if (q.need_sinks ? !q.sink || !q.dsink : !q.sink != !q.dsink) return {FA2_ERR_NULL_POINTER, false, {}};
+    return {FA2_OK, q.sink || q.dL, {q.sink, q.dsink, q.H, q.dL}};
+}
+
+// every dense backward entry point: the sinks' rule, the route, the launches
+static int backward(Entry entry, const fa2::BwdArgs& t, const Request& q, void* stream)
 {
     const hipStream_t s = (hipStream_t)stream;
+    const Sinks sinks = sink_grad(q);
+    if (sinks.status) return sinks.status;
+    const Route r = bwd_route(entry, t, q);
     const fa2::BwdArgs& a = r.args;
     if (r.status) return r.status;
     if (r.clear_error) {
         const hipError_t e = fa2::bwd_fused_clear_error(r.ws.ctl, s);
         if (e != hipSuccess) return hip_status(e);
     }
-    if (r.path == Path::single) return hip_status(fa2::launch_bwd_fused_bf16(a, r.ws.acc, r.ws.ctl, r.mode, s, r.ws.rcpad, r.ws.kvpart, sg));
-    if (r.path == Path::two_kernel) return hip_status(fa2::launch_bwd_bf16(a, s, sg));
+    if (r.path == Path::single)
+        return hip_status(fa2::launch_bwd_fused_bf16(a, r.ws.acc, r.ws.ctl, r.mode, s, r.ws.rcpad, r.ws.kvpart, sinks.ptr()));
+    if (r.path == Path::two_kernel) return hip_status(fa2::launch_bwd_bf16(a, s, sinks.ptr()));
     const fa2::F32Args f{(const float*)a.Q, (const float*)a.K, (const float*)a.V, (float*)a.O, (float*)a.L, (const float*)a.dO,
                          (float*)a.dQ, (float*)a.dK, (float*)a.dV, a.D, a.BH, a.Nq, a.d, a.scale, a.causal, a.phases};
     return hip_status(fa2::launch_bwd_f32(f, s));
@@ -628,8 +633,8 @@ int fa2_backward_phases(const void* Q, const void* K, const void* V, const void*
                         int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream,
                         int phases)
 {
-    return bwd_launch(bwd_route(Entry::phases, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, 0, seq_len, seq_len, 0, 0, 0, head_dim, dtype,
-                                causal, 0, softmax_scale, phases, workspace, workspace_bytes), stream);
+    return backward(Entry::phases, {Q, K, V, O, dO, L, dQ, dK, dV}, {.B = B, .H = H, .q_len = seq_len, .kv_len = seq_len, .head_dim = head_dim, .dtype = dtype,
+                    .scale = softmax_scale, .causal = causal, .phases = phases, .ws = workspace, .ws_bytes = workspace_bytes}, stream);
 }
 
 int fa2_backward_block(const void* Q, const void* K, const void* V, const void* O, const float* L,
@@ -638,8 +643,9 @@ int fa2_backward_block(const void* Q, const void* K, const void* V, const void* 
                        int q_head_stride, int kv_head_stride, int q_row0, int causal, int causal_shift,
                        void* workspace, size_t workspace_bytes, void* stream, int phases)
 {
-    return bwd_launch(bwd_route(Entry::block, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, 0, q_len, kv_len, q_head_stride, kv_head_stride,
-                                q_row0, head_dim, dtype, causal, causal_shift, softmax_scale, phases, workspace, workspace_bytes), stream);
+    return backward(Entry::block, {Q, K, V, O, dO, L, dQ, dK, dV}, {.B = B, .H = H, .q_len = q_len, .kv_len = kv_len, .q_stride = q_head_stride,
+                    .kv_stride = kv_head_stride, .q_row0 = q_row0, .head_dim = head_dim, .dtype = dtype, .scale = softmax_scale,
+                    .causal = causal, .shift = causal_shift, .phases = phases, .ws = workspace, .ws_bytes = workspace_bytes}, stream);
 }
 
 int fa2_backward_fused(const void* Q, const void* K, const void* V, const void* O, const float* L,
@@ -647,15 +653,22 @@ int fa2_backward_fused(const void* Q, const void* K, const void* V, const void* 
                        int B, int H, int seq_len, int head_dim, float softmax_scale, int mode,
                        void* workspace, size_t workspace_bytes, void* stream)
 {
-    return bwd_launch(bwd_route(Entry::fused, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H, 0, seq_len, seq_len, 0, 0, 0, head_dim,
-                                FA2_DTYPE_BF16, 0, 0, softmax_scale, mode, workspace, workspace_bytes), stream);
+    return backward(Entry::fused, {Q, K, V, O, dO, L, dQ, dK, dV}, {.B = B, .H = H, .q_len = seq_len, .kv_len = seq_len, .head_dim = head_dim,
+                    .scale = softmax_scale, .phases = mode, .ws = workspace, .ws_bytes = workspace_bytes}, stream);
+}
+
+// both *_plan functions: 1 = the single kernel, 2 = the two kernels or fp32, and why
+static int backward_plan(const Request& q, const char** reason)
+{
+    const Route r = bwd_route(Entry::plan, {}, q);
+    if (reason) *reason = r.status ? "" : r.why;
+    return r.status ? r.status : r.path == Path::single ? 1 : 2;
 }
 
 int fa2_backward_plan(int B, int H, int seq_len, int head_dim, int dtype, int causal, const char** reason)
 {
-    const Route r = bwd_route(Entry::plan, {}, B, H, 0, seq_len, seq_len, 0, 0, 0, head_dim, dtype, causal, 0, 1.0f, 0, nullptr, 0);
-    if (reason) *reason = r.status ? "" : r.why;
-    return r.status ? r.status : r.path == Path::single ? 1 : 2;
+    return backward_plan({.B = B, .H = H, .q_len = seq_len, .kv_len = seq_len, .head_dim = head_dim, .dtype = dtype, .causal = causal},
+                         reason);
 }
 
 size_t fa2_backward_gqa_workspace_bytes(int B, int H_q, int H_kv, int seq_len, int head_dim, int dtype)
@@ -669,17 +682,15 @@ int fa2_backward_gqa(const void* Q, const void* K, const void* V, const void* O,
                      int B, int H_q, int H_kv, int seq_len, int head_dim, float softmax_scale,
                      int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases)
 {
-    // (H_kv = 0 must not read as "multi-head": -1 is as invalid and stays so through the route)
-    return bwd_launch(bwd_route(Entry::phases, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H_q, H_kv ? H_kv : -1, seq_len, seq_len, 0, 0, 0,
-                                head_dim, dtype, causal, 0, softmax_scale, phases, workspace, workspace_bytes), stream);
+    return backward(Entry::phases, {Q, K, V, O, dO, L, dQ, dK, dV}, {.B = B, .H = H_q, .kv_heads = grouped(H_kv), .q_len = seq_len, .kv_len = seq_len,
+                    .head_dim = head_dim, .dtype = dtype, .scale = softmax_scale, .causal = causal, .phases = phases, .ws = workspace,
+                    .ws_bytes = workspace_bytes}, stream);
 }
 
 int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, int dtype, int causal, const char** reason)
 {
-    const Route r = bwd_route(Entry::plan, {}, B, H_q, H_kv ? H_kv : -1, seq_len, seq_len, 0, 0, 0, head_dim, dtype, causal, 0, 1.0f, 0,
-                              nullptr, 0);
-    if (reason) *reason = r.status ? "" : r.why;
-    return r.status ? r.status : r.path == Path::single ? 1 : 2;
+    return backward_plan({.B = B, .H = H_q, .kv_heads = grouped(H_kv), .q_len = seq_len, .kv_len = seq_len, .head_dim = head_dim,
+                          .dtype = dtype, .causal = causal}, reason);
 }
 
 size_t fa2_backward_qk_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, int dtype)
@@ -695,8 +706,8 @@ int fa2_backward_qk(const void* Q, const void* K, const void* V, const void* O, 
                     int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
                     int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases)
 {
-    return bwd_launch(bwd_route(Entry::qk, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H_q, H_kv ? H_kv : -1, q_len, kv_len, 0, 0, 0, head_dim,
-                                dtype, causal, kv_len - q_len, softmax_scale, phases, workspace, workspace_bytes), stream);
+    return fa2_backward_lse(Q, K, V, nullptr, O, L, dO, nullptr, dQ, dK, dV, nullptr, B, H_q, H_kv, q_len, kv_len, head_dim, softmax_scale,
+                            dtype, causal, workspace, workspace_bytes, stream, phases);
 }
 
 size_t fa2_backward_sink_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, int dtype)
@@ -709,10 +720,9 @@ int fa2_backward_sink(const void* Q, const void* K, const void* V, const float* 
                       int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
                       int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases)
 {
-    if (!sink || !dsink) return FA2_ERR_NULL_POINTER;
-    const fa2::SinkGrad sg{sink, dsink, H_q};
-    return bwd_launch(bwd_route(Entry::qk, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H_q, H_kv ? H_kv : -1, q_len, kv_len, 0, 0, 0, head_dim,
-                                dtype, causal, kv_len - q_len, softmax_scale, phases, workspace, workspace_bytes), stream, &sg);
+    return backward(Entry::qk, {Q, K, V, O, dO, L, dQ, dK, dV}, {.B = B, .H = H_q, .kv_heads = grouped(H_kv), .q_len = q_len, .kv_len = kv_len, .head_dim = head_dim,
+                    .dtype = dtype, .scale = softmax_scale, .causal = causal, .shift = kv_len - q_len, .phases = phases,
+                    .ws = workspace, .ws_bytes = workspace_bytes, .sink = sink, .dsink = dsink, .need_sinks = true}, stream);
 }
 
 // fa2_backward_qk / fa2_backward_sink with a gradient for L (kernel 0 alone reads it, with phase bit 0)
@@ -721,11 +731,10 @@ int fa2_backward_lse(const void* Q, const void* K, const void* V, const float* s
                      int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
                      int dtype, int causal, void* workspace, size_t workspace_bytes, void* stream, int phases)
 {
-    if (!sink != !dsink) return FA2_ERR_NULL_POINTER;
-    const fa2::SinkGrad sg{sink, dsink, H_q, dL};
-    return bwd_launch(bwd_route(Entry::qk, {Q, K, V, O, dO, L, dQ, dK, dV}, B, H_q, H_kv ? H_kv : -1, q_len, kv_len, 0, 0, 0, head_dim,
-                                dtype, causal, kv_len - q_len, softmax_scale, phases, workspace, workspace_bytes), stream,
-                      sink || dL ? &sg : nullptr);
+    return backward(Entry::qk, {Q, K, V, O, dO, L, dQ, dK, dV}, {.B = B, .H = H_q, .kv_heads = grouped(H_kv), .q_len = q_len, .kv_len = kv_len, .head_dim = head_dim,
+                    .dtype = dtype, .scale = softmax_scale, .causal = causal, .shift = kv_len - q_len, .phases = phases,
+                    .ws = workspace, .ws_bytes = workspace_bytes, .sink = sink, .dsink = dsink, .dL = dL},
+                    stream);
 }
 
 // D [H_q][T] and the two row-constant planes, laid out as the front of every other backward workspace
@@ -735,34 +744,24 @@ size_t fa2_backward_varlen_workspace_bytes(int H_q, int H_kv, int total_rows, in
     return bwd_ws(nullptr, 1, H_q, total_rows, head_dim, dtype).base_bytes;
 }
 
-// both packed backward entry points (one_list: fa2_backward_varlen, one T for both sides)
-static int backward_varlen(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
-                           void* dQ, void* dK, void* dV,
-                           int H_q, int H_kv, int total_q, int total_k, bool one_list, int head_dim, float softmax_scale, int dtype,
-                           int causal, const void* plan_host, const void* plan_dev, size_t plan_bytes,
-                           void* workspace, size_t workspace_bytes, void* stream, const fa2::SinkGrad* sg = nullptr)
+// Every packed backward entry point.  One implementation (the two deterministic kernels over the plan's items), so there is
+// nothing to route: the checks are check_request's, the arguments bwd_args', as for the dense calls.
+static int backward_varlen(const fa2::BwdArgs& t, const Request& q, void* stream)
 {
-    if (!Q || !K || !V || !O || !L || !dO || !dQ || !dK || !dV || !plan_host || !plan_dev) return FA2_ERR_NULL_POINTER;
-    int st = check_common(1, H_q, total_q, head_dim, softmax_scale);
-    if (!st) st = check_common(1, H_q, total_k, head_dim, softmax_scale);
-    if (st) return st;
-    if (H_kv <= 0 || H_q % H_kv != 0) return FA2_ERR_INVALID_SHAPE;
-    if ((st = check_bwd_planes(1, H_q, total_q))) return st;
+    const Sinks sinks = sink_grad(q);
+    if (sinks.status) return sinks.status;
+    if (any_null(t) || !q.plan_host || !q.plan_dev) return FA2_ERR_NULL_POINTER;
     VarlenHeader h;
-    if ((st = varlen_check(plan_host, plan_dev, plan_bytes, total_q, total_k, one_list, H_q, &h))) return st;
-    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
-    const BwdWs ws = bwd_ws(workspace, 1, H_q, total_q, head_dim, dtype);
-    if (!workspace || workspace_bytes < ws.base_bytes) return FA2_ERR_WORKSPACE;
+    if (const int st = check_request(Entry::backward_packed, q, &h)) return st;
+    const BwdWs ws = bwd_ws(q.ws, 1, q.H, q.q_len, q.head_dim, q.dtype);
+    if (q.ws_short(ws.base_bytes)) return FA2_ERR_WORKSPACE;
     fa2::VarlenBwdArgs v{};
-    fa2::BwdArgs& a = v.a;
-    a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.L = L; a.dQ = dQ; a.dK = dK; a.dV = dV;
-    a.D = ws.D; a.RC = ws.RC; a.BH = H_q; a.Nq = total_q; a.Nk = total_k; a.d = head_dim;
-    a.q_hs = a.Nq; a.k_hs = a.Nk; a.scale = softmax_scale; a.causal = causal ? 1 : 0; a.phases = 7; a.kv_group = H_q / H_kv;
-    const auto* items = reinterpret_cast<const fa2::VarlenItem*>((const char*)plan_dev + sizeof(VarlenHeader));
+    bwd_args(v.a, t, q, ws);
+    v.a.phases = 7;
+    const auto* items = reinterpret_cast<const fa2::VarlenItem*>((const char*)q.plan_dev + sizeof(VarlenHeader));
     v.row_items = items; v.n_row_items = h.n_row_items;
     v.key_items = items + h.n_row_items; v.n_key_items = h.n_key_items;
-    return hip_status(fa2::launch_bwd_varlen_bf16(v, (hipStream_t)stream, sg));
+    return hip_status(fa2::launch_bwd_varlen_bf16(v, (hipStream_t)stream, sinks.ptr()));
 }
 
 int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void* O, const float* L, const void* dO,
@@ -771,8 +770,9 @@ int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void*
                         const void* plan_host, const void* plan_dev, size_t plan_bytes,
                         void* workspace, size_t workspace_bytes, void* stream)
 {
-    return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_rows, total_rows, true, head_dim, softmax_scale, dtype, causal, plan_host,
-                           plan_dev, plan_bytes, workspace, workspace_bytes, stream);
+    return backward_varlen({Q, K, V, O, dO, L, dQ, dK, dV}, {.H = H_q, .kv_heads = grouped(H_kv), .q_len = total_rows, .kv_len = total_rows, .head_dim = head_dim,
+                           .dtype = dtype, .scale = softmax_scale, .causal = causal, .ws = workspace, .ws_bytes = workspace_bytes,
+                           .plan_host = plan_host, .plan_dev = plan_dev, .plan_bytes = plan_bytes, .one_list = true}, stream);
 }
 
 // the planes are indexed by query rows: the key side does not enter the size
@@ -787,8 +787,8 @@ int fa2_backward_varlen_qk(const void* Q, const void* K, const void* V, const vo
                            const void* plan_host, const void* plan_dev, size_t plan_bytes,
                            void* workspace, size_t workspace_bytes, void* stream)
 {
-    return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
-                           plan_dev, plan_bytes, workspace, workspace_bytes, stream);
+    return fa2_backward_varlen_lse(Q, K, V, nullptr, O, L, dO, nullptr, dQ, dK, dV, nullptr, H_q, H_kv, total_q, total_k, head_dim, softmax_scale,
+                                   dtype, causal, plan_host, plan_dev, plan_bytes, workspace, workspace_bytes, stream);
 }
 
 size_t fa2_backward_varlen_sink_workspace_bytes(int H_q, int H_kv, int total_q, int total_k, int head_dim, int dtype)
@@ -802,10 +802,10 @@ int fa2_backward_varlen_sink(const void* Q, const void* K, const void* V, const 
                              const void* plan_host, const void* plan_dev, size_t plan_bytes,
                              void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!sink || !dsink) return FA2_ERR_NULL_POINTER;
-    const fa2::SinkGrad sg{sink, dsink, H_q};
-    return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
-                           plan_dev, plan_bytes, workspace, workspace_bytes, stream, &sg);
+    return backward_varlen({Q, K, V, O, dO, L, dQ, dK, dV}, {.H = H_q, .kv_heads = grouped(H_kv), .q_len = total_q, .kv_len = total_k, .head_dim = head_dim,
+                           .dtype = dtype, .scale = softmax_scale, .causal = causal, .ws = workspace, .ws_bytes = workspace_bytes,
+                           .sink = sink, .dsink = dsink, .need_sinks = true,
+                           .plan_host = plan_host, .plan_dev = plan_dev, .plan_bytes = plan_bytes}, stream);
 }
 
 int fa2_backward_varlen_lse(const void* Q, const void* K, const void* V, const float* sink, const void* O, const float* L,
@@ -814,10 +814,10 @@ int fa2_backward_varlen_lse(const void* Q, const void* K, const void* V, const f
                             const void* plan_host, const void* plan_dev, size_t plan_bytes,
                             void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!sink != !dsink) return FA2_ERR_NULL_POINTER;
-    const fa2::SinkGrad sg{sink, dsink, H_q, dL};
-    return backward_varlen(Q, K, V, O, L, dO, dQ, dK, dV, H_q, H_kv, total_q, total_k, false, head_dim, softmax_scale, dtype, causal, plan_host,
-                           plan_dev, plan_bytes, workspace, workspace_bytes, stream, sink || dL ? &sg : nullptr);
+    return backward_varlen({Q, K, V, O, dO, L, dQ, dK, dV}, {.H = H_q, .kv_heads = grouped(H_kv), .q_len = total_q, .kv_len = total_k, .head_dim = head_dim,
+                           .dtype = dtype, .scale = softmax_scale, .causal = causal, .ws = workspace, .ws_bytes = workspace_bytes,
+                           .sink = sink, .dsink = dsink, .dL = dL,
+                           .plan_host = plan_host, .plan_dev = plan_dev, .plan_bytes = plan_bytes}, stream);
 }
 
 // ---- merging partial results (include/fa2_mi355x.h): argument checks, then the part pointers by value into the kernels
@@ -828,9 +828,7 @@ static int merge_check(const void* const* O_parts, const float* const* L_parts, 
     for (int i = 0; i < n_parts; ++i)
         if (!O_parts[i] || !L_parts[i]) return FA2_ERR_NULL_POINTER;
     if (rows > (size_t)0x7fffffff * 8) return FA2_ERR_INVALID_SHAPE;      // the grid: one workgroup per 16 or 32 rows
-    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
-    return FA2_OK;
+    return check_bf16(head_dim, dtype);
 }
 
 int fa2_merge_states(const void* const* O_parts, const float* const* L_parts, int n_parts, void* O, float* L, size_t rows,
@@ -886,11 +884,10 @@ int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, 
     if (!Q || !K_cache || !V_cache || !O || !L) return FA2_ERR_NULL_POINTER;
     int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
     if (st) return st;
-    if (H_kv <= 0 || H_q % H_kv != 0 || kv_capacity <= 0) return FA2_ERR_INVALID_SHAPE;
+    if (!heads_divide(H_q, H_kv) || kv_capacity <= 0) return FA2_ERR_INVALID_SHAPE;
     if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
     if ((long long)kv_capacity * head_dim * 2 > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;      // one (b, head) slab, one buffer resource
-    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
+    if ((st = check_bf16(head_dim, dtype))) return st;
     if (n_splits == 0) n_splits = fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
     if ((long long)B * H_kv * n_splits > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;             // the grid
     const size_t need = fa2_decode_workspace_bytes(B, H_q, H_kv, q_len, kv_capacity, head_dim, n_splits);
@@ -908,8 +905,8 @@ int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, 
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,
                         void* stream)
 {
-    const Route r = bwd_route(Entry::status, {}, B, H, 0, seq_len, seq_len, 0, 0, 0, head_dim, dtype, 0, 0, 1.0f, 0, workspace,
-                              workspace_bytes);
+    const Route r = bwd_route(Entry::status, {}, {.B = B, .H = H, .q_len = seq_len, .kv_len = seq_len, .head_dim = head_dim,
+                                                  .dtype = dtype, .ws = workspace, .ws_bytes = workspace_bytes});
     if (r.status) return r.status;
     if (r.path != Path::single) return hip_status(hipStreamSynchronize((hipStream_t)stream));
     int err = 0;

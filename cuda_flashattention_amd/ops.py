@@ -31,6 +31,21 @@ def _stream_ptr(stream=None):
     return s.cuda_stream
 
 
+def _scale(softmax_scale, d):
+    """The softmax scale a call runs with: the caller's, or 1 / sqrt(head_dim)."""
+    return float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def _workspace_arg(workspace, Q):
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
+        raise ValueError("workspace must be a contiguous device tensor on Q's device")
+    return workspace
+
+
 def _bhnd(x, name):
     if not isinstance(x, torch.Tensor):
         raise ValueError(f"{name} must be a torch tensor")
@@ -133,7 +148,7 @@ def flash_attention_2_forward(Q, K, V, softmax_scale=None, causal=False, O=None,
     (q, k, v) per-tensor descales of tensors stored as x / descale (fa2_forward_fp8_scaled)."""
     B, H, N, d = shape = _bhnd(Q, "Q")
     Hkv = _kv_shape(Q, K, V, shape)[1]
-    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    scale = _scale(softmax_scale, d)
     odt = torch.bfloat16 if Q.dtype == torch.float8_e4m3fn else Q.dtype      # fp8 inputs (OCP e4m3, d = 128) produce a bf16 O
     if O is None:
         O = torch.empty(Q.shape, dtype=odt, device=Q.device)
@@ -144,24 +159,20 @@ def flash_attention_2_forward(Q, K, V, softmax_scale=None, causal=False, O=None,
     if Q.dtype == torch.float8_e4m3fn and (workspace is not None or descale is not None):
         if workspace is None:
             workspace = forward_fp8_workspace(B, H, N, d, Q.device)
-        if not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
-            raise ValueError("workspace must be a contiguous device tensor on Q's device")
+        _workspace_arg(workspace, Q)
         dq, dk, dv = (1.0, 1.0, 1.0) if descale is None else (float(x) for x in descale)
         st = _capi.lib().fa2_forward_fp8_scaled(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, N, d, scale,
-                                                dq, dk, dv, 1 if causal else 0, workspace.data_ptr(),
-                                                workspace.numel() * workspace.element_size(), _stream_ptr(stream))
+                                                dq, dk, dv, 1 if causal else 0, workspace.data_ptr(), _nbytes(workspace), _stream_ptr(stream))
         check(st, "fa2_forward_fp8_scaled")
         return O, L
     if workspace is not None or descale is not None:
         raise ValueError("workspace= / descale= belong to the fp8 (float8_e4m3fn) forward")
+    lib, ptrs = _capi.lib(), (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr())
+    tail = (N, d, scale, _dtype_code(Q), 1 if causal else 0, _stream_ptr(stream))
     if Hkv != H:
-        st = _capi.lib().fa2_forward_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
-                                         B, H, Hkv, N, d, scale, _dtype_code(Q), 1 if causal else 0, _stream_ptr(stream))
-        check(st, "fa2_forward_gqa")
-        return O, L
-    st = _capi.lib().fa2_forward(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
-                                 B, H, N, d, scale, _dtype_code(Q), 1 if causal else 0, _stream_ptr(stream))
-    check(st, "fa2_forward")
+        check(lib.fa2_forward_gqa(*ptrs, B, H, Hkv, *tail), "fa2_forward_gqa")
+    else:
+        check(lib.fa2_forward(*ptrs, B, H, *tail), "fa2_forward")
     return O, L
 
 
@@ -178,7 +189,7 @@ def flash_attention_2_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=Fal
     for n, t, dt in (("O", O, gdt), ("dO", dO, gdt)):
         _like(t, n, Q, shape, dt)
     _rows(L, "L", Q, B, H, N)
-    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    scale = _scale(softmax_scale, d)
     dQ = torch.empty_like(Q) if dQ is None else _like(dQ, "dQ", Q, shape, Q.dtype)
     dK = torch.empty_like(K) if dK is None else _like(dK, "dK", Q, kshape, Q.dtype)
     dV = torch.empty_like(V) if dV is None else _like(dV, "dV", Q, kshape, Q.dtype)
@@ -186,22 +197,13 @@ def flash_attention_2_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=Fal
     need = lib.fa2_backward_gqa_workspace_bytes(B, H, Hkv, N, d, _dtype_code(Q))
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
-    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
-        raise ValueError("workspace must be a contiguous device tensor on Q's device")
+    _workspace_arg(workspace, Q)
+    ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr())
+    tail = (N, d, scale, _dtype_code(Q), 1 if causal else 0, workspace.data_ptr(), _nbytes(workspace), _stream_ptr(stream), int(phases))
     if Hkv != H:
-        st = lib.fa2_backward_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
-                                  dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(),
-                                  B, H, Hkv, N, d, scale, _dtype_code(Q), 1 if causal else 0,
-                                  workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                  _stream_ptr(stream), int(phases))
-        check(st, "fa2_backward_gqa")
-        return dQ, dK, dV
-    st = lib.fa2_backward_phases(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
-                                 dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(),
-                                 B, H, N, d, scale, _dtype_code(Q), 1 if causal else 0,
-                                 workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                 _stream_ptr(stream), int(phases))
-    check(st, "fa2_backward")
+        check(lib.fa2_backward_gqa(*ptrs, B, H, Hkv, *tail), "fa2_backward_gqa")
+    else:
+        check(lib.fa2_backward_phases(*ptrs, B, H, *tail), "fa2_backward")
     return dQ, dK, dV
 
 
@@ -236,7 +238,7 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Q, K, V, softmax_scale, causal):
         Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
-        scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
+        scale = _scale(softmax_scale, Q.shape[-1])
         O, L = flash_attention_2_forward(Q, K, V, scale, causal=causal)
         ctx.save_for_backward(Q, K, V, O, L)
         ctx.scale, ctx.causal = scale, bool(causal)
@@ -261,26 +263,32 @@ def attention(Q, K, V, softmax_scale=None, causal=False, sink=None, return_lse=F
     return _Attention.apply(Q, K, V, softmax_scale, causal)
 
 
-def _qk_shapes(Q, K, V):
-    """(B, H, H_kv, N_q, N_k, d) of a problem with its own query and key lengths, every relation between Q, K and V checked: 4-D
-    bf16 contiguous device tensors, Q [B, H, N_q, d], K and V [B, H_kv, N_k, d] with H_kv dividing H.  Shapes first, then what the
-    C ABI takes on trust -- device, contiguity, dtype."""
-    for n, t in (("Q", Q), ("K", K), ("V", V)):
+def _qkv_shapes(Q, K, V, kname, vname, nk, family):
+    """(B, H, H_kv, N_q, N_k, d) of Q [B, H, N_q, d] against K and V [B, H_kv, N_k, d], H_kv dividing H, Q in bf16: the relations
+    between the shapes, with the names of the asking family (K or K_cache, N_k or N_cap) in the messages."""
+    for n, t in (("Q", Q), (kname, K), (vname, V)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise ValueError(f"{n}: expected a [B, H, N, d] tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
     B, H, Nq, d = Q.shape
     Bk, Hkv, Nk, dk = K.shape
     if (Bk, dk) != (B, d) or Hkv < 1 or H % Hkv != 0 or Nq < 1 or Nk < 1:
-        raise ValueError(f"K: shape {tuple(K.shape)} does not match Q {tuple(Q.shape)}: expected [B, H_kv, N_k, d] with B = {B}, "
-                         f"d = {d}, H_kv dividing H = {H} and N_q, N_k >= 1")
+        raise ValueError(f"{kname}: shape {tuple(K.shape)} does not match Q {tuple(Q.shape)}: expected [B, H_kv, {nk}, d] with B = {B}, "
+                         f"d = {d}, H_kv dividing H = {H} and N_q, {nk} >= 1")
     if tuple(V.shape) != tuple(K.shape):
-        raise ValueError(f"V: shape {tuple(V.shape)} does not match K {tuple(K.shape)}")
+        raise ValueError(f"{vname}: shape {tuple(V.shape)} does not match {kname} {tuple(K.shape)}")
     if Q.dtype != torch.bfloat16:
-        raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16 (different query and key lengths are bf16 in this version)")
+        raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16 ({family} bf16 in this version)")
+    return B, H, Hkv, Nq, Nk, d
+
+
+def _qk_shapes(Q, K, V):
+    """_qkv_shapes of a problem with its own query and key lengths, then what the C ABI takes on trust -- device, contiguity,
+    dtype."""
+    B, H, Hkv, Nq, Nk, d = shapes = _qkv_shapes(Q, K, V, "K", "V", "N_k", "different query and key lengths are")
     _bhnd(Q, "Q")
     _like(K, "K", Q, (B, Hkv, Nk, d), Q.dtype)
     _like(V, "V", Q, (B, Hkv, Nk, d), Q.dtype)
-    return B, H, Hkv, Nq, Nk, d
+    return shapes
 
 
 def flash_attention_2_qk_forward(Q, K, V, softmax_scale=None, causal=False, O=None, L=None, stream=None, sink=None):
@@ -294,17 +302,15 @@ def flash_attention_2_qk_forward(Q, K, V, softmax_scale=None, causal=False, O=No
     if sink is not None:
         _sink_arg(sink, Q, 1)
     B, H, Hkv, Nq, Nk, d = _qk_shapes(Q, K, V)
-    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    scale = _scale(softmax_scale, d)
     O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
     L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
+    lib, ptrs = _capi.lib(), (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr())
+    tail = (B, H, Hkv, Nq, Nk, d, scale, FA2_DTYPE_BF16, 1 if causal else 0, _stream_ptr(stream))
     if sink is not None:
-        st = _capi.lib().fa2_forward_sink(Q.data_ptr(), K.data_ptr(), V.data_ptr(), sink.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, Hkv,
-                                          Nq, Nk, d, scale, FA2_DTYPE_BF16, 1 if causal else 0, _stream_ptr(stream))
-        check(st, "fa2_forward_sink")
-        return O, L
-    st = _capi.lib().fa2_forward_qk(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Nk, d, scale,
-                                    FA2_DTYPE_BF16, 1 if causal else 0, _stream_ptr(stream))
-    check(st, "fa2_forward_qk")
+        check(lib.fa2_forward_sink(*ptrs[:3], sink.data_ptr(), *ptrs[3:], *tail), "fa2_forward_sink")
+    else:
+        check(lib.fa2_forward_qk(*ptrs, *tail), "fa2_forward_qk")
     return O, L
 
 
@@ -314,19 +320,8 @@ DECODE_MAX_SPLITS = 256
 
 def _decode_shapes(Q, K_cache, V_cache):
     """(B, H, H_kv, N_q, N_cap, d) of a decode problem: Q [B, H, N_q, d] against caches [B, H_kv, N_cap, d], bf16, H_kv dividing
-    H.  Shapes and dtypes first, then device and contiguity, as _qk_shapes."""
-    for n, t in (("Q", Q), ("K_cache", K_cache), ("V_cache", V_cache)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 4:
-            raise ValueError(f"{n}: expected a [B, H, N, d] tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
-    B, H, Nq, d = Q.shape
-    Bk, Hkv, Ncap, dk = K_cache.shape
-    if (Bk, dk) != (B, d) or Hkv < 1 or H % Hkv != 0 or Nq < 1 or Ncap < 1:
-        raise ValueError(f"K_cache: shape {tuple(K_cache.shape)} does not match Q {tuple(Q.shape)}: expected [B, H_kv, N_cap, d] with "
-                         f"B = {B}, d = {d}, H_kv dividing H = {H} and N_q, N_cap >= 1")
-    if tuple(V_cache.shape) != tuple(K_cache.shape):
-        raise ValueError(f"V_cache: shape {tuple(V_cache.shape)} does not match K_cache {tuple(K_cache.shape)}")
-    if Q.dtype != torch.bfloat16:
-        raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16 (decode is bf16 in this version)")
+    H.  Shapes and dtypes first (_qkv_shapes); device and contiguity are the caller's to check next."""
+    B, H, Hkv, Nq, Ncap, d = _qkv_shapes(Q, K_cache, V_cache, "K_cache", "V_cache", "N_cap", "decode is")
     for n, t in (("K_cache", K_cache), ("V_cache", V_cache)):
         if t.dtype != Q.dtype:
             raise ValueError(f"{n}: dtype {t.dtype}, expected {Q.dtype}")
@@ -392,7 +387,7 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     _bhnd(Q, "Q")
     _like(K_cache, "K_cache", Q, (B, Hkv, Ncap, d), Q.dtype)
     _like(V_cache, "V_cache", Q, (B, Hkv, Ncap, d), Q.dtype)
-    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    scale = _scale(softmax_scale, d)
     if not scale > 0.0:
         raise ValueError(f"softmax_scale: {scale}, expected a positive number")
     O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
@@ -401,17 +396,39 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     need = lib.fa2_decode_workspace_bytes(B, H, Hkv, Nq, Ncap, d, n_splits)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
-    if workspace is not None:
-        if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
-            raise ValueError("workspace must be a contiguous device tensor on Q's device")
-        if workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"workspace: {workspace.numel() * workspace.element_size()} bytes, {need} needed (decode_workspace)")
+    if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
+        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (decode_workspace)")
     st = lib.fa2_forward_decode(Q.data_ptr(), K_cache.data_ptr(), V_cache.data_ptr(), None if seqlens_k is None else seqlens_k.data_ptr(),
                                 None if sink is None else sink.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d, scale,
                                 FA2_DTYPE_BF16, 1 if causal else 0, n_splits, None if workspace is None else workspace.data_ptr(),
-                                0 if workspace is None else workspace.numel() * workspace.element_size(), _stream_ptr(stream))
+                                0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
     check(st, "fa2_forward_decode")
     return O, L
+
+
+def _sink_pair(sink, dsink, Q, heads_dim):
+    """sink= and dsink= of a backward, each checked beside Q (_sink_arg); dsink without sink is refused."""
+    if sink is not None:
+        _sink_arg(sink, Q, heads_dim)
+        if dsink is not None:
+            _sink_arg(dsink, Q, heads_dim, "dsink")
+    elif dsink is not None:
+        raise ValueError("dsink belongs to a call with sink=")
+
+
+def _backward_symbol(plain, ptrs, Q, H, sink, dsink, dL):
+    """(symbol, pointers, dsink) of a backward of the _qk or the packed family -- the one place the symbol is picked: `plain`
+    for a call without sinks and dL, else its _sink or _lse sibling with the optional pointers inserted among the nine (dsink
+    is allocated when the call has sinks and brought none)."""
+    stem = plain[:-len("_qk")] if plain.endswith("_qk") else plain
+    if sink is not None and dsink is None:
+        dsink = torch.empty(H, dtype=torch.float32, device=Q.device)
+    if dL is not None:
+        sp, dp = (None, None) if sink is None else (sink.data_ptr(), dsink.data_ptr())
+        return stem + "_lse", (*ptrs[:3], sp, *ptrs[3:6], dL.data_ptr(), *ptrs[6:], dp), dsink
+    if sink is not None:
+        return stem + "_sink", (*ptrs[:3], sink.data_ptr(), *ptrs[3:], dsink.data_ptr()), dsink
+    return plain, ptrs, dsink
 
 
 def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=False,
@@ -423,51 +440,26 @@ def flash_attention_2_qk_backward(Q, K, V, O, L, dO, softmax_scale=None, causal=
     phase bit 0).
     dL (fa2_backward_lse): the gradient of L, fp32 shaped like L -- dS = P o (dP - D + dL), through the row constant D' = D - dL
     that phase bit 0 writes; a row with L = -inf ignores it.  With or without sink=."""
-    if sink is not None:
-        _sink_arg(sink, Q, 1)
-        if dsink is not None:
-            _sink_arg(dsink, Q, 1, "dsink")
-    elif dsink is not None:
-        raise ValueError("dsink belongs to a call with sink=")
+    _sink_pair(sink, dsink, Q, 1)
     B, H, Hkv, Nq, Nk, d = _qk_shapes(Q, K, V)
     for n, t in (("O", O), ("dO", dO)):
         _like(t, n, Q, (B, H, Nq, d), Q.dtype)
     _rows(L, "L", Q, B, H, Nq)
     if dL is not None:
         _rows(dL, "dL", Q, B, H, Nq)
-    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    scale = _scale(softmax_scale, d)
     dQ = torch.empty_like(Q) if dQ is None else _like(dQ, "dQ", Q, (B, H, Nq, d), Q.dtype)
     dK = torch.empty_like(K) if dK is None else _like(dK, "dK", Q, (B, Hkv, Nk, d), Q.dtype)
     dV = torch.empty_like(V) if dV is None else _like(dV, "dV", Q, (B, Hkv, Nk, d), Q.dtype)
     lib = _capi.lib()
     if workspace is None:
         workspace = torch.empty(lib.fa2_backward_qk_workspace_bytes(B, H, Hkv, Nq, Nk, d, FA2_DTYPE_BF16), dtype=torch.uint8, device=Q.device)
-    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
-        raise ValueError("workspace must be a contiguous device tensor on Q's device")
-    if dL is not None:
-        if sink is not None and dsink is None:
-            dsink = torch.empty(H, dtype=torch.float32, device=Q.device)
-        st = lib.fa2_backward_lse(Q.data_ptr(), K.data_ptr(), V.data_ptr(), None if sink is None else sink.data_ptr(), O.data_ptr(),
-                                  L.data_ptr(), dO.data_ptr(), dL.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(),
-                                  None if sink is None else dsink.data_ptr(), B, H, Hkv, Nq, Nk, d, scale, FA2_DTYPE_BF16,
-                                  1 if causal else 0, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                  _stream_ptr(stream), int(phases))
-        check(st, "fa2_backward_lse")
-        return (dQ, dK, dV) if sink is None else (dQ, dK, dV, dsink)
-    if sink is not None:
-        dsink = torch.empty(H, dtype=torch.float32, device=Q.device) if dsink is None else dsink
-        st = lib.fa2_backward_sink(Q.data_ptr(), K.data_ptr(), V.data_ptr(), sink.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
-                                   dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), dsink.data_ptr(), B, H, Hkv, Nq, Nk, d, scale,
-                                   FA2_DTYPE_BF16, 1 if causal else 0, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                   _stream_ptr(stream), int(phases))
-        check(st, "fa2_backward_sink")
-        return dQ, dK, dV, dsink
-    st = lib.fa2_backward_qk(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(),
-                             dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, H, Hkv, Nq, Nk, d, scale, FA2_DTYPE_BF16,
-                             1 if causal else 0, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                             _stream_ptr(stream), int(phases))
-    check(st, "fa2_backward_qk")
-    return dQ, dK, dV
+    _workspace_arg(workspace, Q)
+    ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr())
+    name, ptrs, dsink = _backward_symbol("fa2_backward_qk", ptrs, Q, H, sink, dsink, dL)
+    check(getattr(lib, name)(*ptrs, B, H, Hkv, Nq, Nk, d, scale, FA2_DTYPE_BF16, 1 if causal else 0, workspace.data_ptr(), _nbytes(workspace),
+                             _stream_ptr(stream), int(phases)), name)
+    return (dQ, dK, dV) if sink is None else (dQ, dK, dV, dsink)
 
 
 def _grad_pair(O, dO, dL):
@@ -478,16 +470,20 @@ def _grad_pair(O, dO, dL):
 
 
 class _AttentionQK(torch.autograd.Function):
-    """flash_attention_2_qk_forward / _backward as one differentiable op (as _Attention)."""
+    """flash_attention_2_qk_forward / _backward or, with a plan, flash_attention_2_varlen_forward / _backward as one differentiable
+    op (as _Attention)."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, softmax_scale, causal, sink=None, return_lse=False):
+    def forward(ctx, Q, K, V, plan, softmax_scale, causal, sink=None, return_lse=False):
         Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
-        scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
+        scale = _scale(softmax_scale, Q.shape[-1])
         s32 = _sink_param(sink)                      # the kernels read fp32 sinks; the parameter may be bf16
-        O, L = flash_attention_2_qk_forward(Q, K, V, scale, causal=causal, sink=s32)
+        if plan is None:
+            O, L = flash_attention_2_qk_forward(Q, K, V, scale, causal=causal, sink=s32)
+        else:
+            O, L = flash_attention_2_varlen_forward(Q, K, V, plan, scale, causal=causal, sink=s32)
         ctx.save_for_backward(Q, K, V, O, L, s32)
-        ctx.scale, ctx.causal, ctx.sink_dtype = scale, bool(causal), None if sink is None else sink.dtype
+        ctx.plan, ctx.scale, ctx.causal, ctx.sink_dtype = plan, scale, bool(causal), None if sink is None else sink.dtype
         ctx.set_materialize_grads(False)             # an output nobody used arrives as None: no dL, the call of before
         return (O, L) if return_lse else O
 
@@ -495,11 +491,10 @@ class _AttentionQK(torch.autograd.Function):
     def backward(ctx, dO, dL=None):
         Q, K, V, O, L, s32 = ctx.saved_tensors
         dO, dL = _grad_pair(O, dO, dL)
-        if s32 is None:
-            dQ, dK, dV = flash_attention_2_qk_backward(Q, K, V, O, L, dO, ctx.scale, causal=ctx.causal, dL=dL)
-            return dQ, dK, dV, None, None, None, None
-        dQ, dK, dV, dsink = flash_attention_2_qk_backward(Q, K, V, O, L, dO, ctx.scale, causal=ctx.causal, sink=s32, dL=dL)
-        return dQ, dK, dV, None, None, dsink.to(ctx.sink_dtype), None
+        plan = () if ctx.plan is None else (ctx.plan,)
+        backward = flash_attention_2_qk_backward if ctx.plan is None else flash_attention_2_varlen_backward
+        dQ, dK, dV, *dsink = backward(Q, K, V, O, L, dO, *plan, ctx.scale, causal=ctx.causal, sink=s32, dL=dL)
+        return dQ, dK, dV, None, None, None, dsink[0].to(ctx.sink_dtype) if dsink else None, None
 
 
 def attention_qk(Q, K, V, softmax_scale=None, causal=False, sink=None, return_lse=False):
@@ -509,7 +504,7 @@ def attention_qk(Q, K, V, softmax_scale=None, causal=False, sink=None, return_ls
     back in its dtype.
     return_lse: return (O, L), L the fp32 [B, H, N_q] log-sum-exp of every row (-inf on a row without a key or sink), both
     differentiable (merge_attention_states, a z-loss)."""
-    return _AttentionQK.apply(Q, K, V, softmax_scale, causal, sink, bool(return_lse))
+    return _AttentionQK.apply(Q, K, V, None, softmax_scale, causal, sink, bool(return_lse))
 
 
 class VarlenPlan:
@@ -654,7 +649,7 @@ def flash_attention_2_varlen_forward(Q, K, V, plan, softmax_scale=None, causal=F
     if sink is not None:
         _sink_arg(sink, Q, 0)
     H, Hkv, T, Tk, d = _varlen_shapes(Q, K, V, plan)
-    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    scale = _scale(softmax_scale, d)
     O = torch.empty_like(Q) if O is None else _packed(O, "O", Q, (H, T, d))
     L = torch.empty(H, T, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, 1, H, T)
     lib, ptrs = _capi.lib(), (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr())
@@ -676,71 +671,27 @@ def flash_attention_2_varlen_backward(Q, K, V, O, L, dO, plan, softmax_scale=Non
     (fa2_backward_varlen_qk) dK / dV are [H_kv, T_k, d]; a sequence with keys and no queries gets dK = dV = 0.
     sink (fa2_backward_varlen_sink): the forward's sinks, with its O and L; returns (dQ, dK, dV, dsink), dsink fp32 [H].
     dL (fa2_backward_varlen_lse): the gradient of L, fp32 [H, T], as in flash_attention_2_qk_backward."""
-    if sink is not None:
-        _sink_arg(sink, Q, 0)
-        if dsink is not None:
-            _sink_arg(dsink, Q, 0, "dsink")
-    elif dsink is not None:
-        raise ValueError("dsink belongs to a call with sink=")
+    _sink_pair(sink, dsink, Q, 0)
     H, Hkv, T, Tk, d = _varlen_shapes(Q, K, V, plan)
     for n, t in (("O", O), ("dO", dO)):
         _packed(t, n, Q, (H, T, d))
     _rows(L, "L", Q, 1, H, T)
     if dL is not None:
         _rows(dL, "dL", Q, 1, H, T)
-    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(d)
+    scale = _scale(softmax_scale, d)
     dQ = torch.empty_like(Q) if dQ is None else _packed(dQ, "dQ", Q, (H, T, d))
     dK = torch.empty_like(K) if dK is None else _packed(dK, "dK", Q, (Hkv, Tk, d))
     dV = torch.empty_like(V) if dV is None else _packed(dV, "dV", Q, (Hkv, Tk, d))
     lib = _capi.lib()
     if workspace is None:
         workspace = torch.empty(lib.fa2_backward_varlen_workspace_bytes(H, Hkv, T, d, FA2_DTYPE_BF16), dtype=torch.uint8, device=Q.device)
-    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != Q.device:
-        raise ValueError("workspace must be a contiguous device tensor on Q's device")
+    _workspace_arg(workspace, Q)
     ptrs = (Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(), dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr())
-    tail = (d, scale, FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(), plan.nbytes,
-            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr(stream))
-    if dL is not None:
-        if sink is not None and dsink is None:
-            dsink = torch.empty(H, dtype=torch.float32, device=Q.device)
-        check(lib.fa2_backward_varlen_lse(*ptrs[:3], None if sink is None else sink.data_ptr(), *ptrs[3:6], dL.data_ptr(), *ptrs[6:],
-                                          None if sink is None else dsink.data_ptr(), H, Hkv, T, Tk, *tail), "fa2_backward_varlen_lse")
-        return (dQ, dK, dV) if sink is None else (dQ, dK, dV, dsink)
-    if sink is not None:
-        dsink = torch.empty(H, dtype=torch.float32, device=Q.device) if dsink is None else dsink
-        check(lib.fa2_backward_varlen_sink(*ptrs[:3], sink.data_ptr(), *ptrs[3:], dsink.data_ptr(), H, Hkv, T, Tk, *tail),
-              "fa2_backward_varlen_sink")
-        return dQ, dK, dV, dsink
-    if plan.two_sided:
-        check(lib.fa2_backward_varlen_qk(*ptrs, H, Hkv, T, Tk, *tail), "fa2_backward_varlen_qk")
-    else:
-        check(lib.fa2_backward_varlen(*ptrs, H, Hkv, T, *tail), "fa2_backward_varlen")
-    return dQ, dK, dV
-
-
-class _AttentionVarlen(torch.autograd.Function):
-    """flash_attention_2_varlen_forward / _backward as one differentiable op (as _Attention)."""
-
-    @staticmethod
-    def forward(ctx, Q, K, V, plan, softmax_scale, causal, sink=None, return_lse=False):
-        Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
-        scale = float(softmax_scale) if softmax_scale is not None else 1.0 / math.sqrt(Q.shape[-1])
-        s32 = _sink_param(sink)
-        O, L = flash_attention_2_varlen_forward(Q, K, V, plan, scale, causal=causal, sink=s32)
-        ctx.save_for_backward(Q, K, V, O, L, s32)
-        ctx.plan, ctx.scale, ctx.causal, ctx.sink_dtype = plan, scale, bool(causal), None if sink is None else sink.dtype
-        ctx.set_materialize_grads(False)
-        return (O, L) if return_lse else O
-
-    @staticmethod
-    def backward(ctx, dO, dL=None):
-        Q, K, V, O, L, s32 = ctx.saved_tensors
-        dO, dL = _grad_pair(O, dO, dL)
-        if s32 is None:
-            dQ, dK, dV = flash_attention_2_varlen_backward(Q, K, V, O, L, dO, ctx.plan, ctx.scale, causal=ctx.causal, dL=dL)
-            return dQ, dK, dV, None, None, None, None, None
-        dQ, dK, dV, dsink = flash_attention_2_varlen_backward(Q, K, V, O, L, dO, ctx.plan, ctx.scale, causal=ctx.causal, sink=s32, dL=dL)
-        return dQ, dK, dV, None, None, None, dsink.to(ctx.sink_dtype), None
+    name, ptrs, dsink = _backward_symbol("fa2_backward_varlen_qk" if plan.two_sided else "fa2_backward_varlen", ptrs, Q, H, sink, dsink, dL)
+    rows = (T,) if name == "fa2_backward_varlen" else (T, Tk)      # the one-list call has one T for both sides
+    check(getattr(lib, name)(*ptrs, H, Hkv, *rows, d, scale, FA2_DTYPE_BF16, 1 if causal else 0, plan.host_ptr(), plan.device(Q.device).data_ptr(),
+                             plan.nbytes, workspace.data_ptr(), _nbytes(workspace), _stream_ptr(stream)), name)
+    return (dQ, dK, dV) if sink is None else (dQ, dK, dV, dsink)
 
 
 def attention_varlen(Q, K, V, plan, softmax_scale=None, causal=False, sink=None, return_lse=False):
@@ -748,7 +699,9 @@ def attention_varlen(Q, K, V, plan, softmax_scale=None, causal=False, sink=None,
     dividing H), plan a VarlenPlan of the batch's cu_seqlens; every sequence attends itself only.  With gradients.  Under a
     two-sided plan K and V are [H_kv, T_k, d] and so are their gradients.  sink: attention sinks, as in attention_qk.
     return_lse: return (O, L), L fp32 [H, T], both differentiable."""
-    return _AttentionVarlen.apply(Q, K, V, plan, softmax_scale, causal, sink, bool(return_lse))
+    if not isinstance(plan, VarlenPlan):
+        raise ValueError("plan must be a VarlenPlan")
+    return _AttentionQK.apply(Q, K, V, plan, softmax_scale, causal, sink, bool(return_lse))
 
 
 MERGE_MAX_PARTS = 8
