@@ -902,6 +902,40 @@ int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, 
     return hip_status(fa2::launch_decode(a, head_dim, (hipStream_t)stream));
 }
 
+// The same call over a pool of pages.  Nothing here reads the block table either: the capacity max_pages_per_seq x page_size
+// stands where kv_capacity stood, and the kernel turns table entries into addresses (clamped to the pool).
+int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
+                             const int* seqlens_k, const float* sink, void* O, float* L,
+                             int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
+                             int head_dim, float softmax_scale, int dtype, int causal, int n_splits,
+                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!Q || !K_pages || !V_pages || !block_table || !O || !L) return FA2_ERR_NULL_POINTER;
+    int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
+    if (st) return st;
+    if (!heads_divide(H_q, H_kv) || n_pages <= 0 || page_size <= 0 || max_pages_per_seq <= 0) return FA2_ERR_INVALID_SHAPE;
+    if (page_size % fa2::kDecodeTile) return FA2_ERR_INVALID_SHAPE;                              // a tile never crosses a page
+    // key indices are ints, and the kernel forms begin = split chunk <= len + n_splits kDecodeKB and kb + 2 kDecodeKB
+    if ((long long)max_pages_per_seq * page_size > 0x7fffffffLL - (fa2::kDecodeMaxSplits + 2) * fa2::kDecodeKB) return FA2_ERR_INVALID_SHAPE;
+    if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
+    const int kv_capacity = max_pages_per_seq * page_size;
+    const int resolved = n_splits ? n_splits : fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
+    if ((long long)B * H_kv * resolved > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;             // the grid
+    if ((st = check_bf16(head_dim, dtype))) return st;
+    n_splits = resolved;
+    const size_t need = fa2_decode_workspace_bytes(B, H_q, H_kv, q_len, kv_capacity, head_dim, n_splits);
+    if (n_splits > 1 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return FA2_ERR_WORKSPACE;
+    if ((long long)(H_q / H_kv) * q_len > fa2::kDecodeMaxRows) return FA2_ERR_UNSUPPORTED;
+    fa2::DecodeArgs a{};
+    a.Q = Q; a.K = K_pages; a.V = V_pages; a.seqlens = seqlens_k; a.sink = sink; a.O = O; a.L = L;
+    a.wsO = (float*)workspace;
+    a.wsL = n_splits > 1 ? (float*)workspace + (size_t)n_splits * B * H_q * q_len * head_dim : nullptr;
+    a.B = B; a.Hq = H_q; a.Hkv = H_kv; a.Nq = q_len; a.Ncap = kv_capacity; a.n_splits = n_splits;
+    a.scale = softmax_scale; a.causal = causal ? 1 : 0;
+    a.block_table = block_table; a.n_pages = n_pages; a.page_size = page_size; a.max_pages = max_pages_per_seq;
+    return hip_status(fa2::launch_decode(a, head_dim, (hipStream_t)stream));
+}
+
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,
                         void* stream)
 {

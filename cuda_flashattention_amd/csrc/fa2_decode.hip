@@ -22,6 +22,7 @@
 // and L_s (-inf for a split without a visible key), which fa2_decode_combine_kernel -- a second plain launch on the same
 // stream -- folds in ascending s: L = logsumexp_s L_s, O = sum_s exp(L_s - L) O_s, then the sink, then ONE rounding to bf16.
 // No workgroup talks to another inside a launch: no atomics, no flags, no waiting; every sum has a fixed order.
+// PAGED (fa2_forward_decode_paged): the same body over a pool of pages and a block table, see decode_split_body.
 #include "fa2_common.h"
 #include "fa2_launch.h"
 
@@ -34,6 +35,7 @@ namespace {
 constexpr float kDecLn2 = 0.6931471805599453f;
 constexpr int kDecWaves = kDecodeKB / kDecodeTile;      // 4: one tile per wave and round
 typedef __attribute__((address_space(3))) bf16x4 dec_lds_bf16x4;
+typedef __attribute__((address_space(4))) int dec_const_int;
 constexpr int kCombineBatch = 8;      // partials of a row in flight in the combine
 
 // L <- log(exp L + exp s), returns exp(L_old - L_new), what O scales by (fa2_forward_sink's rule).  s = -inf: no sink, nothing
@@ -58,10 +60,15 @@ __device__ __forceinline__ bf16x4 to_bf16x4(const f32x4& v, float w)
     return r;
 }
 
-}  // namespace
-
-template <int D>
-__global__ void __launch_bounds__(256) fa2_decode_split_kernel(DecodeArgs a)
+// The body of both split kernels.  PAGED (fa2_forward_decode_paged): K and V are pools [n_pages][Hkv][page_size][d] and key j of
+// sequence b is row j % page_size of page block_table[b][j / page_size]; page_size is a multiple of the 32-key tile, so a tile
+// lies in one page and the ONLY difference is where a tile's two buffer resources start: at the tile's first row in (page, hkv),
+// min(32, end - kb) rows long, the lane offsets without the tile's base.  The tile's page is a wave-uniform scalar: its table
+// entry is loaded one iteration ahead of the K/V loads that need it (which themselves run one tile ahead of the arithmetic), and
+// becomes an address only after the clamp to [0, n_pages).  Only tiles with a key below `end` index the table, so the entries at
+// and beyond ceil(len_b / page_size) are never read; a tile past `end` gets a resource of no rows.
+template <int D, bool PAGED>
+__device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
 {
     constexpr int ROWB = 2 * D;               // bytes per cache row
     constexpr int KS = D / 16;                // k-steps of S^T = K Q^T
@@ -126,13 +133,44 @@ __global__ void __launch_bounds__(256) fa2_decode_split_kernel(DecodeArgs a)
     if (a.causal) kmax = min(end, r % a.Nq + len - a.Nq + 1);
     if (r >= M) kmax = 0;
 
-    const size_t slab = ((size_t)b * a.Hkv + hkv) * (size_t)a.Ncap * D;
+    const size_t slab = PAGED ? (size_t)hkv * a.page_size * D : ((size_t)b * a.Hkv + hkv) * (size_t)a.Ncap * D;
     const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.K + slab), 0, end * ROWB, 0x00020000);
     const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.V + slab), 0, end * ROWB, 0x00020000);
     const uint32_t koff = (uint32_t)r * ROWB + 16 * h;                       // + 32 t per k-step
     const uint32_t voff = (uint32_t)(lane / CPR) * ROWB + 16 * (lane % CPR);   // + RPI rows per load
     u32x4 kf[KS], vf[NV];
+    // PAGED.  (pg_i, pg_o): page index and row within the page of the tile whose table entry is fetched next; a wave's tiles are
+    // kDecodeKB keys apart, that is (pg_di, pg_do) further, carried without a division.  (ent, ent_o): the fetched entry and row
+    // of the tile that is LOADED next.  A tile with a key indexes the table below max_pages (kb < len <= max_pages page_size);
+    // one without reads entry 0 of its sequence, which the clamp and its resource of no rows keep from being used.
+    // The table does not change while the kernel runs: read through the constant address space, a uniform index is a scalar load
+    // whatever else the loop stores (the compiler gives up proving that for a plain global load this deep in a loop, and a
+    // vector load would leave the resource in VGPRs).
+    int pg_i = 0, pg_o = 0, pg_di = 0, pg_do = 0, ent = 0, ent_o = 0;
+    const dec_const_int* const table = (const dec_const_int*)a.block_table + (size_t)b * a.max_pages;
+    const auto fetch_entry = [&](int base) {
+        // (the outer readfirstlane costs nothing on a scalar; it keeps the compiler from merging this load with the one before
+        // the loop into a single load at the top of the iteration that uses it, which would undo the prefetch)
+        ent = __builtin_amdgcn_readfirstlane(table[__builtin_amdgcn_readfirstlane(base < end ? pg_i : 0)]);
+        ent_o = pg_o;
+        pg_i += pg_di;
+        pg_o += pg_do;
+        if (pg_o >= a.page_size) { pg_o -= a.page_size; ++pg_i; }
+    };
     const auto load_tile = [&](int base) {      // rows past `end` read as zeros (and cost no traffic)
+        if constexpr (PAGED) {
+            const int page = base < end ? min(max(ent, 0), a.n_pages - 1) : 0;      // the clamp is the contract
+            // (readfirstlane: the compiler clamps with v_med3_i32, and a resource with a VGPR word is loaded in a waterfall loop)
+            const int rows = __builtin_amdgcn_readfirstlane(max(min(kDecodeTile, end - base), 0));
+            const size_t at = slab + ((size_t)page * a.Hkv * a.page_size + ent_o) * D;      // 64-bit: a pool may exceed 4 GiB
+            const auto kp = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.K + at), 0, rows * ROWB, 0x00020000);
+            const auto vp = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.V + at), 0, rows * ROWB, 0x00020000);
+#pragma unroll
+            for (int t = 0; t < KS; ++t) kf[t] = __builtin_amdgcn_raw_buffer_load_b128(kp, koff + 32 * t, 0, 0);
+#pragma unroll
+            for (int n = 0; n < NV; ++n) vf[n] = __builtin_amdgcn_raw_buffer_load_b128(vp, voff + n * RPI * ROWB, 0, 0);
+            return;
+        }
         const uint32_t b0 = (uint32_t)base * ROWB;
 #pragma unroll
         for (int t = 0; t < KS; ++t) kf[t] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, b0 + koff + 32 * t, 0, 0);
@@ -154,7 +192,15 @@ __global__ void __launch_bounds__(256) fa2_decode_split_kernel(DecodeArgs a)
     const float sc = a.scale * kLog2e;
 
     int kb = begin + kDecodeTile * wave;
+    if constexpr (PAGED) {      // the two divisions of a workgroup
+        pg_i = kb / a.page_size;
+        pg_o = kb - pg_i * a.page_size;
+        pg_di = kDecodeKB / a.page_size;
+        pg_do = kDecodeKB - pg_di * a.page_size;
+        fetch_entry(kb);
+    }
     load_tile(kb);
+    if constexpr (PAGED) fetch_entry(kb + kDecodeKB);
     for (; kb < end; kb += kDecodeKB) {
 #pragma unroll
         for (int n = 0; n < NV; ++n)
@@ -166,6 +212,7 @@ __global__ void __launch_bounds__(256) fa2_decode_split_kernel(DecodeArgs a)
         for (int t = 0; t < KS; ++t)
             s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[t]), q[t], s, 0, 0, 0);
         load_tile(kb + kDecodeKB);
+        if constexpr (PAGED) fetch_entry(kb + 2 * kDecodeKB);      // the table entry of the tile after the next one
 
         float mx = -INFINITY;
 #pragma unroll
@@ -253,6 +300,20 @@ __global__ void __launch_bounds__(256) fa2_decode_split_kernel(DecodeArgs a)
     }
 }
 
+}  // namespace
+
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_split_kernel(DecodeArgs a)
+{
+    decode_split_body<D, false>(a);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_paged_split_kernel(DecodeArgs a)
+{
+    decode_split_body<D, true>(a);
+}
+
 // rows x d / 4 lanes, a lane owns four columns of one row: partials in, ascending s, fp32; the sink; one rounding
 template <int D>
 __global__ void __launch_bounds__(256) fa2_decode_combine_kernel(DecodeArgs a)
@@ -321,7 +382,8 @@ static hipError_t decode_launch(const DecodeArgs& a, hipStream_t stream)
     constexpr int lds = kDecWaves * 32 * (D + 4) * 4 + kDecWaves * 32 * 2 * 4;
     static_assert(kDecWaves * kDecodeTile * 2 * D <= kDecWaves * 32 * (D + 4) * 4, "the V images fit under the O images");
     const unsigned grid = (unsigned)a.B * a.Hkv * a.n_splits;
-    hipError_t e = launch_lds<fa2_decode_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
+    hipError_t e = a.block_table ? launch_lds<fa2_decode_paged_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a)
+                                 : launch_lds<fa2_decode_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
     if (e != hipSuccess || a.n_splits == 1) return e;
     const size_t threads = (size_t)a.B * a.Hq * a.Nq * (D / 4);
     hipLaunchKernelGGL(fa2_decode_combine_kernel<D>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
@@ -333,6 +395,9 @@ hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream)
     if (a.n_splits < 1 || a.n_splits > kDecodeMaxSplits || a.Hq % a.Hkv || a.Hq / a.Hkv * a.Nq > kDecodeMaxRows)
         return hipErrorInvalidValue;
     if ((long long)a.B * a.Hkv * a.n_splits > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (a.block_table && (a.n_pages < 1 || a.max_pages < 1 || a.page_size < kDecodeTile || a.page_size % kDecodeTile ||
+                          (long long)a.max_pages * a.page_size != a.Ncap))
+        return hipErrorInvalidValue;
     if (d == 128) return decode_launch<128>(a, stream);
     if (d == 64) return decode_launch<64>(a, stream);
     return hipErrorInvalidValue;

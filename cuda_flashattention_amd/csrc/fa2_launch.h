@@ -86,9 +86,13 @@ struct DecodeArgs {
     int B, Hq, Hkv, Nq, Ncap, n_splits;
     float scale;
     int causal;
+    // fa2_forward_decode_paged: K, V are page pools [n_pages][Hkv][page_size][d], Ncap = max_pages page_size, and key j of
+    // sequence b is row j % page_size of page block_table[b][j / page_size] (DEVICE, int [B][max_pages]).  All zero: contiguous.
+    const int* block_table;
+    int n_pages, page_size, max_pages;
 };
 int decode_num_splits(int B, int H_kv, int kv_capacity);      // pure host arithmetic: fa2_decode_num_splits
-hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream);      // d = 64 | 128; 1 <= G Nq <= 32
+hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream);      // d = 64 | 128; 1 <= G Nq <= 32; block_table: paged
 
 // fp8 (OCP e4m3) forward, d = 128: Q, K, V fp8 [BH][N][128]; O bf16; Vt: [BH][128][Npad] fp8 scratch the
 // launcher fills with V transposed (Npad = N rounded up to 64); kn: [BH][Npad / 64] fp32 scratch it fills with the largest

@@ -406,6 +406,108 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     return O, L
 
 
+DECODE_PAGE_GRAIN = 32      # kDecodeTile: a page is a whole number of the kernel's 32-key tiles, so a tile never crosses a page
+
+
+def _block_table_arg(block_table, Q, B):
+    """block_table beside Q: like seqlens_k it is read ON THE DEVICE when the kernels run (one captured graph serves every step as
+    pages are assigned), so a host list or a CPU tensor cannot stand in for it.  Returns max_pages."""
+    if not isinstance(block_table, torch.Tensor):
+        raise ValueError(f"block_table must be an int32 device tensor [{B}, max_pages], got {type(block_table).__name__}: the kernels read "
+                         "the table on the device when they run, the host never does; use torch.tensor(..., dtype=torch.int32, device=Q.device)")
+    if block_table.dtype != torch.int32:
+        raise ValueError(f"block_table: dtype {block_table.dtype}, expected torch.int32")
+    if block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1:
+        raise ValueError(f"block_table: shape {tuple(block_table.shape)}, expected ({B}, max_pages): one row of page numbers per sequence")
+    if not block_table.is_contiguous():
+        raise ValueError(f"block_table must be contiguous (got stride {tuple(block_table.stride())}; call .contiguous())")
+    if not block_table.is_cuda:
+        raise ValueError("block_table is a CPU tensor: the kernels read the table on the device when they run (the host never "
+                         "reads it), so it must live on Q's device")
+    if block_table.device != Q.device:
+        raise ValueError(f"block_table is on {block_table.device}, expected {Q.device}")
+    return block_table.shape[1]
+
+
+def _decode_paged_shapes(Q, K_pages, V_pages):
+    """(B, H, H_kv, N_q, n_pages, page_size, d) of a paged decode problem: Q [B, H, N_q, d] against pools [n_pages, H_kv, page_size,
+    d], bf16, H_kv dividing H, page_size a multiple of 32.  Device and contiguity are the caller's to check next."""
+    for n, t in (("Q", Q), ("K_pages", K_pages), ("V_pages", V_pages)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a 4-d tensor ({'[B, H, N_q, d]' if n == 'Q' else '[n_pages, H_kv, page_size, d]'}), got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    B, H, Nq, d = Q.shape
+    n_pages, Hkv, page_size, dk = K_pages.shape
+    if dk != d or Hkv < 1 or H % Hkv != 0 or B < 1 or Nq < 1 or n_pages < 1 or page_size < 1:
+        raise ValueError(f"K_pages: shape {tuple(K_pages.shape)} does not match Q {tuple(Q.shape)}: expected [n_pages, H_kv, page_size, d] "
+                         f"with d = {d}, H_kv dividing H = {H} and n_pages, page_size >= 1")
+    if page_size % DECODE_PAGE_GRAIN:
+        raise ValueError(f"K_pages: page_size {page_size} is not a multiple of {DECODE_PAGE_GRAIN} (the kernel's key tile; a page of 16 "
+                         "keys is not taken)")
+    if tuple(V_pages.shape) != tuple(K_pages.shape):
+        raise ValueError(f"V_pages: shape {tuple(V_pages.shape)} does not match K_pages {tuple(K_pages.shape)}")
+    if Q.dtype != torch.bfloat16:
+        raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16 (decode is bf16 in this version)")
+    for n, t in (("K_pages", K_pages), ("V_pages", V_pages)):
+        if t.dtype != Q.dtype:
+            raise ValueError(f"{n}: dtype {t.dtype}, expected {Q.dtype}")
+    if d not in (64, 128):
+        raise ValueError(f"Q: head_dim {d}, expected 64 or 128")
+    if (H // Hkv) * Nq > DECODE_MAX_ROWS:
+        raise ValueError(f"Q: {H // Hkv} query heads per K/V head x {Nq} query tokens = {(H // Hkv) * Nq} rows, decode takes at most "
+                         f"{DECODE_MAX_ROWS}: that is a prefill chunk, use flash_attention_2_qk_forward")
+    return B, H, Hkv, Nq, n_pages, page_size, d
+
+
+def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=None, softmax_scale=None, causal=True, sink=None,
+                                   n_splits=0, O=None, L=None, workspace=None, stream=None):
+    """O, L = flash_attention_2_decode over a KV cache held as a pool of pages (fa2_forward_decode_paged): Q [B, H, N_q, d], K_pages
+    and V_pages [n_pages, H_kv, page_size, d] (head-major; H_kv dividing H, (H / H_kv) N_q <= 32, page_size a multiple of 32, not
+    necessarily a power of two), bf16, d = 64 | 128.  A token-major pool [n_pages, page_size, H_kv, d] needs one permute when it is
+    allocated.  INFERENCE ONLY.
+    block_table: int32 [B, max_pages] DEVICE tensor; key j of sequence b is row j % page_size of page block_table[b, j // page_size].
+    Entries may repeat (shared prefix pages); entries past a sequence's last used page may hold anything; an entry in use is
+    clamped to [0, n_pages) in the kernel.  The pool is only read, and its rows past a length may hold anything (NaN included).
+    The host never reads the table.
+    The logical capacity is kv_capacity = max_pages * page_size, and everything flash_attention_2_decode says about seqlens_k, the
+    mask, rows without a key, sink and n_splits holds with it: n_splits=0 is decode_num_splits(B, H_kv, kv_capacity, d), the
+    workspace is decode_workspace(B, H, H_kv, N_q, kv_capacity, d, n_splits) -- PASS ONE FOR GRAPH CAPTURE, with O, L, and seqlens_k
+    and block_table tensors that are updated in place between replays (a sequence grows into a new page, pages are reassigned).
+    With the same n_splits the result is bit for bit flash_attention_2_decode's on the gathered cache of that capacity."""
+    B, H, Hkv, Nq, n_pages, page_size, d = _decode_paged_shapes(Q, K_pages, V_pages)
+    if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
+        raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
+    max_pages = _block_table_arg(block_table, Q, B)
+    kv_capacity = max_pages * page_size
+    if kv_capacity > 0x7fffffff - (DECODE_MAX_SPLITS + 2) * 128:
+        raise ValueError(f"block_table: {max_pages} pages of {page_size} keys is a capacity of {kv_capacity} keys, above what an int indexes")
+    if seqlens_k is not None:
+        _seqlens_arg(seqlens_k, Q, B)
+    if sink is not None:
+        _sink_arg(sink, Q, 1)
+    _bhnd(Q, "Q")
+    _like(K_pages, "K_pages", Q, (n_pages, Hkv, page_size, d), Q.dtype)
+    _like(V_pages, "V_pages", Q, (n_pages, Hkv, page_size, d), Q.dtype)
+    scale = _scale(softmax_scale, d)
+    if not scale > 0.0:
+        raise ValueError(f"softmax_scale: {scale}, expected a positive number")
+    O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
+    L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
+    lib = _capi.lib()
+    need = lib.fa2_decode_workspace_bytes(B, H, Hkv, Nq, kv_capacity, d, n_splits)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+    if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
+        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (decode_workspace)")
+    st = lib.fa2_forward_decode_paged(Q.data_ptr(), K_pages.data_ptr(), V_pages.data_ptr(), block_table.data_ptr(),
+                                      None if seqlens_k is None else seqlens_k.data_ptr(), None if sink is None else sink.data_ptr(),
+                                      O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, n_pages, page_size, max_pages, d, scale, FA2_DTYPE_BF16,
+                                      1 if causal else 0, n_splits, None if workspace is None else workspace.data_ptr(),
+                                      0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
+    check(st, "fa2_forward_decode_paged")
+    return O, L
+
+
 def _sink_pair(sink, dsink, Q, heads_dim):
     """sink= and dsink= of a backward, each checked beside Q (_sink_arg); dsink without sink is refused."""
     if sink is not None:

@@ -242,8 +242,9 @@ int fa2_backward_gqa_plan(int B, int H_q, int H_kv, int seq_len, int head_dim, i
  * FA2_ERR_WORKSPACE.  fa2_varlen_plan_build: NULL -> FA2_ERR_NULL_POINTER; n_seqs < 1, cu_seqlens[0] != 0, a decreasing entry,
  * T < 1 or T above 4194303 rows (the 2 GiB-per-plane rule of every call, at the widest row) -> FA2_ERR_INVALID_SHAPE; plan_bytes
  * too small for this cu_seqlens -> FA2_ERR_WORKSPACE.  fa2_varlen_plan_bytes returns 0 for n_seqs < 1 or total_rows < 1.
- * NOT COVERED in this version: the single-kernel backward on packed batches, fp32 and fp8, the ring, a paged KV cache.
- * (Different query and key lengths per sequence: the _qk calls below.) */
+ * NOT COVERED in this version: the single-kernel backward on packed batches, fp32 and fp8, the ring.
+ * (Different query and key lengths per sequence: the _qk calls below.  A paged KV cache is read at decode, by
+ * fa2_forward_decode_paged; a prompt chunk takes contiguous keys.) */
 size_t fa2_varlen_plan_bytes(int n_seqs, int total_rows);
 int fa2_varlen_plan_build(const int* cu_seqlens_host, int n_seqs, void* plan_host, size_t plan_bytes);
 int fa2_forward_varlen(const void* Q, const void* K, const void* V, void* O, float* L,
@@ -292,8 +293,8 @@ int fa2_backward_varlen(const void* Q, const void* K, const void* V, const void*
  * H_kv not dividing H_q, totals different from the plan's, a blob without the magic or longer than plan_bytes ->
  * FA2_ERR_INVALID_SHAPE; head_dim -> FA2_ERR_UNSUPPORTED_HEAD_DIM; fp32 and fp8 -> FA2_ERR_UNSUPPORTED_DTYPE; workspace ->
  * FA2_ERR_WORKSPACE; then (dense rectangle, phases bit 3) FA2_ERR_UNSUPPORTED.
- * NOT COVERED: the single-kernel backward on rectangles, fp32 and fp8, the ring, a paged or non-contiguous KV cache, sliding
- * windows.  (One or a few new tokens against a long cache: fa2_forward_decode below.) */
+ * NOT COVERED: the single-kernel backward on rectangles, fp32 and fp8, the ring, strided K / V, sliding windows.  (One or a
+ * few new tokens against a long cache: fa2_forward_decode below; against a pool of pages: fa2_forward_decode_paged.) */
 int fa2_forward_qk(const void* Q, const void* K, const void* V, void* O, float* L,
                    int B, int H_q, int H_kv, int q_len, int kv_len, int head_dim, float softmax_scale,
                    int dtype, int causal, void* stream);
@@ -427,13 +428,50 @@ int fa2_merge_states_backward(const void* const* O_parts, const float* const* L_
  * dividing H_q, n_splits outside 0..256, a (b, head) cache slab of 2 GiB or more (kv_capacity x head_dim x 2 bytes; the whole
  * cache may be larger) -> FA2_ERR_INVALID_SHAPE; FA2_ERR_UNSUPPORTED_HEAD_DIM; FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace
  * NULL, misaligned or too small while the resolved split count is > 1 -> FA2_ERR_WORKSPACE; M > 32 -> FA2_ERR_UNSUPPORTED.
- * NOT COVERED: paged or block-table caches, [B][N][H][d] layouts, a cache-append kernel (a framework's scatter does it), M > 32,
- * fp8 or fp32 caches, sliding windows, a backward, the ring. */
+ * NOT COVERED: [B][N][H][d] layouts, a cache-append kernel (a framework's scatter does it), M > 32, fp8 or fp32 caches, sliding
+ * windows, a backward, the ring.  (A cache held as a pool of pages with a block table: fa2_forward_decode_paged below.) */
 int fa2_decode_num_splits(int B, int H_kv, int kv_capacity, int head_dim);
 size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, int n_splits);
 int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
                        void* O, float* L, int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
                        int dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Paged decode: fa2_forward_decode over a KV cache held as a POOL OF PAGES with a per-sequence block table, the way serving
+ * stacks hold it.  The same kernels' body, the same split rule, combine, sink, mask and determinism; what differs is where a
+ * 32-key tile's rows are found.  bf16, head_dim 64 or 128, forward only.
+ * POOL.  K_pages, V_pages [n_pages][H_kv][page_size][d] bf16, contiguous: head-major like every layout here, the rows of one
+ * (page, head) are contiguous.  page_size >= 32 and page_size % 32 == 0 (it need not be a power of two): a 32-key tile never
+ * crosses a page.  The pool may exceed 4 GiB: a page's address is 64-bit arithmetic, and one buffer resource spans one tile.
+ * The pool is only read.
+ * TABLE.  block_table: int32 [B][max_pages_per_seq] in DEVICE memory.  Logical key j of sequence b is row j % page_size of page
+ * block_table[b][j / page_size].  Entries may repeat, within a sequence and across sequences (shared prefix pages).  The host
+ * never reads the table, and nothing the host decides depends on it: a captured graph of this call serves every step as
+ * sequences grow into new pages and pages are reassigned, the table and seqlens_k updated in place.
+ * CAPACITY.  kv_capacity = max_pages_per_seq x page_size is the logical capacity, and everything fa2_forward_decode says holds
+ * with it: len_b = min(max(seqlens_k[b], 0), kv_capacity), clamped in the kernel; seqlens_k == NULL: every sequence has
+ * kv_capacity keys; the bottom-right mask; rows without a visible key (O = 0, L = -inf or the sink); sink; n_splits (0 =
+ * fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim)); chunk = roundup(ceil(len_b / n_splits), 128); the workspace
+ * (fa2_decode_workspace_bytes with that kv_capacity, 16-byte aligned); the combine; (O, L) as fa2_merge_states takes them.  With
+ * the same n_splits the result is bit for bit fa2_forward_decode's on the gathered contiguous cache of that capacity: the
+ * tiles, their order and every sum are the same.
+ * PAGE CLAMP.  A table entry becomes an address only after min(max(entry, 0), n_pages - 1), in the kernel: the length clamp's
+ * contract.  An out-of-range entry IN USE gives an unspecified result and no access outside the pool.
+ * PAST THE LENGTH.  Table entries for pages at or beyond ceil(len_b / page_size) may hold anything: they are never read, and no
+ * table read (prefetches included) falls outside [0, B x max_pages_per_seq).  Rows of the last used page at or beyond len_b, and
+ * every unused page, may hold anything, NaNs included: they are read as zeros and never enter a product.
+ * STATUS CODES, in this order: NULL Q, K_pages, V_pages, block_table, O or L -> FA2_ERR_NULL_POINTER; B, heads, q_len, n_pages,
+ * page_size, max_pages_per_seq or scale <= 0, H_kv not dividing H_q, page_size % 32 != 0, max_pages_per_seq x page_size above
+ * INT_MAX - 33024 (the kernel's key arithmetic, up to len_b + (n_splits + 2) x 128, stays in int), n_splits outside 0..256, a grid B H_kv n_splits above INT_MAX -> FA2_ERR_INVALID_SHAPE; FA2_ERR_UNSUPPORTED_HEAD_DIM;
+ * FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace NULL, misaligned or too small while the resolved split count is > 1 ->
+ * FA2_ERR_WORKSPACE; M = (H_q / H_kv) q_len > 32 -> FA2_ERR_UNSUPPORTED.
+ * NOT COVERED: token-major pages [n_pages][page_size][H_kv][d] (permute such a pool once, when it is allocated), page_size 16, a
+ * cache-append kernel (a framework's scatter through the same table does it), fp8 pages; and what fa2_forward_decode leaves out:
+ * M > 32, sliding windows, a backward, the ring. */
+int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
+                             const int* seqlens_k, const float* sink, void* O, float* L,
+                             int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
+                             int head_dim, float softmax_scale, int dtype, int causal, int n_splits,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output

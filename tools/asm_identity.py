@@ -6,6 +6,7 @@ descriptor field shows like a changed instruction.  The one symbol hipcc derives
 (__hip_cuid_<hash>) is reduced to its prefix: it differs between any two checkouts.
 
     python3 tools/asm_identity.py OLD/_obj NEW/_obj      one line per .s file: equal, or the first differing lines
+    python3 tools/asm_identity.py --kernels OLD/_obj/x.s NEW/_obj/x.s      one line per kernel of a file that gained a kernel
 
 The acceptance check of a refactor of the hand-written glue around the generated bodies: a clobber list or an operand type that
 differs "harmlessly" moves hipcc's prologue, and in kernels with 32 - 64 compiler registers that can end in a spill."""
@@ -52,7 +53,48 @@ def main(old, new, show=3):
     return 1 if differing else 0
 
 
+KERNEL = re.compile(r"^(_Z\w+):")
+
+
+def kernel_streams(path):
+    """{mangled name: (instruction lines from the kernel's label to its .Lfunc_end, its .amdhsa_ lines)} of one .s file."""
+    out, name, part = {}, None, None
+    for line in normalised(path):
+        m = KERNEL.match(line)
+        if m:
+            name, part = m.group(1), "code"
+            out[name] = ([], [])
+        elif name and line.startswith(".Lfunc_end"):
+            name = None
+        elif name and line.lstrip().startswith(".amdhsa_kernel"):
+            part = "desc"
+        elif name and part == "code" and not line.lstrip().startswith("."):
+            out[name][0].append(re.sub(r"\.LBB\d+_", ".LBB_", line))      # (block labels carry the kernel's position in the file)
+        elif name and part == "desc" and line.lstrip().startswith(".amdhsa_"):
+            out[name][1].append(line.strip())
+    return out
+
+
+def per_kernel(old, new):
+    """A file that gained or lost a kernel differs as a whole; this mode compares kernel by kernel: the instruction stream, and
+    which descriptor fields (.amdhsa_*) changed."""
+    a, b = kernel_streams(old), kernel_streams(new)
+    differing = 0
+    for name in sorted(set(a) | set(b)):
+        if name not in a or name not in b:
+            print(f"{name}: only in {old if name in a else new}" + (f" ({len(b[name][0])} instructions)" if name in b else ""))
+            continue
+        same = a[name][0] == b[name][0]
+        fields = [f"{x} -> {y.split()[-1]}" for x, y in zip(a[name][1], b[name][1]) if x != y]
+        print(f"{name}: instructions {'equal' if same else 'DIFFER'} ({len(a[name][0])} / {len(b[name][0])})"
+              + (f"; descriptor: {', '.join(fields)}" if fields else "; descriptor equal"))
+        differing += not same
+    return 1 if differing else 0
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--kernels":      # --kernels OLD/_obj/x.s NEW/_obj/x.s
+        sys.exit(per_kernel(sys.argv[2], sys.argv[3]))
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     sys.exit(main(sys.argv[1], sys.argv[2]))
