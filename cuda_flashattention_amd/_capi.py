@@ -71,6 +71,8 @@ SIGNATURES = {
     "fa2_decode_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "fa2_forward_decode": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
     "fa2_forward_decode_paged": (_i, [_vp] * 8 + [_i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
+    "fa2_forward_decode_fp8kv": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "fa2_forward_decode_paged_fp8kv": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
     "fa2_backward_fused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fa2_backward_fused": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "fa2_backward_block": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),

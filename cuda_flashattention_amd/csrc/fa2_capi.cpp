@@ -877,17 +877,33 @@ size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_ca
     return align256((size_t)n_splits * B * H_q * q_len * ((size_t)head_dim + 1) * sizeof(float));
 }
 
-int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
-                       void* O, float* L, int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
-                       int dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream)
+// The caches of a decode call: bf16 like Q (kv_dtype = FA2_DTYPE_BF16, no descales), or -- the _fp8kv entry points -- OCP e4m3
+// with fp32 DEVICE descales per K/V head (nullptr = 1), which nothing here reads either.
+struct DecodeKv { int kv_dtype = FA2_DTYPE_BF16; const float* k_descale = nullptr; const float* v_descale = nullptr; };
+// Q's dtype, then the caches': both at the position of the dtype check, head_dim first
+static int decode_check_dtypes(int head_dim, int dtype, const DecodeKv& kv, bool fp8kv_entry)
+{
+    if (const int st = check_bf16(head_dim, dtype)) return st;
+    return kv.kv_dtype == (fp8kv_entry ? FA2_DTYPE_FP8_E4M3 : FA2_DTYPE_BF16) ? FA2_OK : FA2_ERR_UNSUPPORTED_DTYPE;
+}
+static void decode_kv_args(fa2::DecodeArgs& a, const DecodeKv& kv)
+{
+    a.kv_fp8 = kv.kv_dtype == FA2_DTYPE_FP8_E4M3; a.k_descale = kv.k_descale; a.v_descale = kv.v_descale;
+}
+
+static int decode_contiguous(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
+                             void* O, float* L, int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
+                             int dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream,
+                             const DecodeKv& kv, bool fp8kv_entry)
 {
     if (!Q || !K_cache || !V_cache || !O || !L) return FA2_ERR_NULL_POINTER;
     int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
     if (st) return st;
     if (!heads_divide(H_q, H_kv) || kv_capacity <= 0) return FA2_ERR_INVALID_SHAPE;
     if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
-    if ((long long)kv_capacity * head_dim * 2 > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;      // one (b, head) slab, one buffer resource
-    if ((st = check_bf16(head_dim, dtype))) return st;
+    // one (b, head) slab, one buffer resource: 2 bytes per element, 1 in an e4m3 cache
+    if ((long long)kv_capacity * head_dim * (fp8kv_entry ? 1 : 2) > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;
+    if ((st = decode_check_dtypes(head_dim, dtype, kv, fp8kv_entry))) return st;
     if (n_splits == 0) n_splits = fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
     if ((long long)B * H_kv * n_splits > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;             // the grid
     const size_t need = fa2_decode_workspace_bytes(B, H_q, H_kv, q_len, kv_capacity, head_dim, n_splits);
@@ -899,29 +915,49 @@ int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, 
     a.wsL = n_splits > 1 ? (float*)workspace + (size_t)n_splits * B * H_q * q_len * head_dim : nullptr;
     a.B = B; a.Hq = H_q; a.Hkv = H_kv; a.Nq = q_len; a.Ncap = kv_capacity; a.n_splits = n_splits;
     a.scale = softmax_scale; a.causal = causal ? 1 : 0;
+    decode_kv_args(a, kv);
     return hip_status(fa2::launch_decode(a, head_dim, (hipStream_t)stream));
+}
+
+int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
+                       void* O, float* L, int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
+                       int dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return decode_contiguous(Q, K_cache, V_cache, seqlens_k, sink, O, L, B, H_q, H_kv, q_len, kv_capacity, head_dim, softmax_scale, dtype,
+                             causal, n_splits, workspace, workspace_bytes, stream, {}, false);
+}
+
+// fa2_forward_decode over e4m3 caches: the same checks in the same order (the slab limit at one byte per element)
+int fa2_forward_decode_fp8kv(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
+                             const float* k_descale, const float* v_descale, void* O, float* L,
+                             int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
+                             int dtype, int kv_dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return decode_contiguous(Q, K_cache, V_cache, seqlens_k, sink, O, L, B, H_q, H_kv, q_len, kv_capacity, head_dim, softmax_scale, dtype,
+                             causal, n_splits, workspace, workspace_bytes, stream, {kv_dtype, k_descale, v_descale}, true);
 }
 
 // The same call over a pool of pages.  Nothing here reads the block table either: the capacity max_pages_per_seq x page_size
 // stands where kv_capacity stood, and the kernel turns table entries into addresses (clamped to the pool).
-int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
-                             const int* seqlens_k, const float* sink, void* O, float* L,
-                             int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
-                             int head_dim, float softmax_scale, int dtype, int causal, int n_splits,
-                             void* workspace, size_t workspace_bytes, void* stream)
+static int decode_paged(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
+                        const int* seqlens_k, const float* sink, void* O, float* L,
+                        int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
+                        int head_dim, float softmax_scale, int dtype, int causal, int n_splits,
+                        void* workspace, size_t workspace_bytes, void* stream, const DecodeKv& kv, bool fp8kv_entry)
 {
     if (!Q || !K_pages || !V_pages || !block_table || !O || !L) return FA2_ERR_NULL_POINTER;
     int st = check_common(B, H_q, q_len, head_dim, softmax_scale);
     if (st) return st;
     if (!heads_divide(H_q, H_kv) || n_pages <= 0 || page_size <= 0 || max_pages_per_seq <= 0) return FA2_ERR_INVALID_SHAPE;
     if (page_size % fa2::kDecodeTile) return FA2_ERR_INVALID_SHAPE;                              // a tile never crosses a page
-    // key indices are ints, and the kernel forms begin = split chunk <= len + n_splits kDecodeKB and kb + 2 kDecodeKB
+    // key indices are ints, and the kernel forms begin = split chunk <= len + n_splits kDecodeKB and kb + 2 kDecodeKB (kb + 4
+    // kDecodeKB over e4m3 pools, two tiles in flight)
     if ((long long)max_pages_per_seq * page_size > 0x7fffffffLL - (fa2::kDecodeMaxSplits + 2) * fa2::kDecodeKB) return FA2_ERR_INVALID_SHAPE;
     if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
     const int kv_capacity = max_pages_per_seq * page_size;
     const int resolved = n_splits ? n_splits : fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
     if ((long long)B * H_kv * resolved > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;             // the grid
-    if ((st = check_bf16(head_dim, dtype))) return st;
+    if ((st = decode_check_dtypes(head_dim, dtype, kv, fp8kv_entry))) return st;
     n_splits = resolved;
     const size_t need = fa2_decode_workspace_bytes(B, H_q, H_kv, q_len, kv_capacity, head_dim, n_splits);
     if (n_splits > 1 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return FA2_ERR_WORKSPACE;
@@ -933,7 +969,30 @@ int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_p
     a.B = B; a.Hq = H_q; a.Hkv = H_kv; a.Nq = q_len; a.Ncap = kv_capacity; a.n_splits = n_splits;
     a.scale = softmax_scale; a.causal = causal ? 1 : 0;
     a.block_table = block_table; a.n_pages = n_pages; a.page_size = page_size; a.max_pages = max_pages_per_seq;
+    decode_kv_args(a, kv);
     return hip_status(fa2::launch_decode(a, head_dim, (hipStream_t)stream));
+}
+
+int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
+                             const int* seqlens_k, const float* sink, void* O, float* L,
+                             int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
+                             int head_dim, float softmax_scale, int dtype, int causal, int n_splits,
+                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    return decode_paged(Q, K_pages, V_pages, block_table, seqlens_k, sink, O, L, B, H_q, H_kv, q_len, n_pages, page_size,
+                        max_pages_per_seq, head_dim, softmax_scale, dtype, causal, n_splits, workspace, workspace_bytes, stream, {}, false);
+}
+
+int fa2_forward_decode_paged_fp8kv(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
+                                   const int* seqlens_k, const float* sink, const float* k_descale, const float* v_descale,
+                                   void* O, float* L,
+                                   int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
+                                   int head_dim, float softmax_scale, int dtype, int kv_dtype, int causal, int n_splits,
+                                   void* workspace, size_t workspace_bytes, void* stream)
+{
+    return decode_paged(Q, K_pages, V_pages, block_table, seqlens_k, sink, O, L, B, H_q, H_kv, q_len, n_pages, page_size,
+                        max_pages_per_seq, head_dim, softmax_scale, dtype, causal, n_splits, workspace, workspace_bytes, stream,
+                        {kv_dtype, k_descale, v_descale}, true);
 }
 
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,

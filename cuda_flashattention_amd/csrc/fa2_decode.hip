@@ -23,10 +23,12 @@
 // stream -- folds in ascending s: L = logsumexp_s L_s, O = sum_s exp(L_s - L) O_s, then the sink, then ONE rounding to bf16.
 // No workgroup talks to another inside a launch: no atomics, no flags, no waiting; every sum has a fixed order.
 // PAGED (fa2_forward_decode_paged): the same body over a pool of pages and a block table, see decode_split_body.
+// FP8 CACHES (fa2_forward_decode_fp8kv, _paged_fp8kv): the same body over e4m3 K and V with a descale per K/V head, see there.
 #include "fa2_common.h"
 #include "fa2_launch.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace fa2 {
 
@@ -60,23 +62,43 @@ __device__ __forceinline__ bf16x4 to_bf16x4(const f32x4& v, float w)
     return r;
 }
 
-// The body of both split kernels.  PAGED (fa2_forward_decode_paged): K and V are pools [n_pages][Hkv][page_size][d] and key j of
+// Eight OCP e4m3 codes (two words, ascending bytes) as their bf16 values: one v_cvt_scalef32_pk_bf16_fp8 per pair, at scale 1.
+__device__ __forceinline__ bf16x8 e4m3x8_to_bf16(uint32_t w0, uint32_t w1)
+{
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+    const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true);
+    const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true);
+    return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// The body of the split kernels.  PAGED (fa2_forward_decode_paged): K and V are pools [n_pages][Hkv][page_size][d] and key j of
 // sequence b is row j % page_size of page block_table[b][j / page_size]; page_size is a multiple of the 32-key tile, so a tile
 // lies in one page and the ONLY difference is where a tile's two buffer resources start: at the tile's first row in (page, hkv),
 // min(32, end - kb) rows long, the lane offsets without the tile's base.  The tile's page is a wave-uniform scalar: its table
 // entry is loaded one iteration ahead of the K/V loads that need it (which themselves run one tile ahead of the arithmetic), and
 // becomes an address only after the clamp to [0, n_pages).  Only tiles with a key below `end` index the table, so the entries at
 // and beyond ceil(len_b / page_size) are never read; a tile past `end` gets a resource of no rows.
-template <int D, bool PAGED>
+//
+// EB: bytes per element of K and V.  2: bf16, everything above.  1 (fa2_forward_decode_fp8kv): OCP e4m3 caches with a descale per
+// K/V head (the cache holds x / descale[hkv]).  A row is D bytes, so a lane's 16-byte K load holds the elements of TWO k-steps
+// (load t', words 2u ..+2: k-step 2t' + u, elements 32t' + 16h + 8u ..+8; Q's fragments are loaded in that order) and a V load
+// covers twice the rows.  Both are widened to bf16 in VGPRs (exact: 3 mantissa bits, and every e4m3 exponent is a normal bf16
+// one): K's on the way into the first product, V's on the way into the wave's LDS image, which -- like the transposed reads,
+// both products and the softmax -- stays the bf16 one.  k_descale joins the scalar the scores are multiplied by, v_descale
+// multiplies the fp32 row piece a split emits, before anything is rounded.
+template <int D, bool PAGED, int EB>
 __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
 {
-    constexpr int ROWB = 2 * D;               // bytes per cache row
+    static_assert(EB == 1 || EB == 2, "bf16 or e4m3 caches");
+    using kv_t = std::conditional_t<EB == 2, __bf16, uint8_t>;      // one cache element: offsets below count elements
+    constexpr int ROWB = EB * D;              // bytes per cache row
     constexpr int KS = D / 16;                // k-steps of S^T = K Q^T
-    constexpr int CPR = D / 8;                // 16-byte chunks per row
+    constexpr int KL = ROWB / 32;             // K loads per tile: 16 bytes of the lane's row each
+    constexpr int CPR = ROWB / 16;            // 16-byte chunks per row
     constexpr int RPI = 64 / CPR;             // V rows one wave-wide load covers
     constexpr int NV = kDecodeTile / RPI;     // V loads per tile
     constexpr int DB = D / 32;                // 32-column tiles of O^T
-    constexpr int VIMG = kDecodeTile * ROWB;  // a wave's V image
+    constexpr int VIMG = kDecodeTile * 2 * D; // a wave's V image (bf16 whatever the cache holds)
     constexpr int OP = D + 4;                 // floats per row of a wave's O image (the pad spreads 32 rows over the banks)
     constexpr int C4 = D / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];      // kDecWaves x max(VIMG, 32 OP 4) | m, l: kDecWaves x 32 x 2 floats
@@ -100,8 +122,10 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
     const size_t row0 = ((size_t)b * a.Hq + (size_t)hkv * G) * a.Nq;      // the group's first row
 
     // what a finished row piece becomes: a partial, or the result
-    const auto emit = [&](int row, int c4, const f32x4& o, float Lrow) {
+    const float vd = EB == 1 && a.v_descale ? a.v_descale[hkv] : 1.0f;
+    const auto emit = [&](int row, int c4, f32x4 o, float Lrow) {
         const size_t gr = row0 + row;
+        if constexpr (EB == 1) o *= vd;
         if (a.n_splits > 1) {
             *reinterpret_cast<f32x4*>(a.wsO + ((size_t)split * R + gr) * D + 4 * c4) = o;
             if (c4 == 0) a.wsL[(size_t)split * R + gr] = Lrow;
@@ -118,13 +142,13 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
         return;
     }
 
-    // Q^T fragments: lane (row r, half h) holds Q[r][16 t + 8 h ..+8] for k-step t
+    // Q^T fragments: lane (row r, half h) holds Q[r][16 t + 8 h ..+8] for k-step t (EB = 1: Q[r][32 (t / 2) + 16 h + 8 (t % 2) ..+8])
     bf16x8 q[KS];
     {
-        const __bf16* Qg = (const __bf16*)a.Q + (row0 + (r < M ? r : 0)) * D + 8 * h;
+        const __bf16* Qg = (const __bf16*)a.Q + (row0 + (r < M ? r : 0)) * D + (EB == 2 ? 8 : 16) * h;
 #pragma unroll
         for (int t = 0; t < KS; ++t) {
-            q[t] = *reinterpret_cast<const bf16x8*>(Qg + 16 * t);
+            q[t] = *reinterpret_cast<const bf16x8*>(Qg + (EB == 2 ? 16 * t : 32 * (t / 2) + 8 * (t % 2)));
             if (r >= M) q[t] = bf16x8{};
         }
     }
@@ -134,11 +158,14 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
     if (r >= M) kmax = 0;
 
     const size_t slab = PAGED ? (size_t)hkv * a.page_size * D : ((size_t)b * a.Hkv + hkv) * (size_t)a.Ncap * D;
-    const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.K + slab), 0, end * ROWB, 0x00020000);
-    const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.V + slab), 0, end * ROWB, 0x00020000);
-    const uint32_t koff = (uint32_t)r * ROWB + 16 * h;                       // + 32 t per k-step
+    const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.K + slab), 0, end * ROWB, 0x00020000);
+    const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.V + slab), 0, end * ROWB, 0x00020000);
+    const uint32_t koff = (uint32_t)r * ROWB + 16 * h;                       // + 32 t per load
     const uint32_t voff = (uint32_t)(lane / CPR) * ROWB + 16 * (lane % CPR);   // + RPI rows per load
-    u32x4 kf[KS], vf[NV];
+    // Tiles a wave keeps in flight ahead of its arithmetic.  An e4m3 tile is half the bytes (and its fragments half the registers)
+    // of a bf16 one, and with one workgroup per CU one of them in flight left the loop waiting on memory: two.
+    constexpr int PF = EB == 1 ? 2 : 1;
+    u32x4 kf[PF][KL], vf[PF][NV];
     // PAGED.  (pg_i, pg_o): page index and row within the page of the tile whose table entry is fetched next; a wave's tiles are
     // kDecodeKB keys apart, that is (pg_di, pg_do) further, carried without a division.  (ent, ent_o): the fetched entry and row
     // of the tile that is LOADED next.  A tile with a key indexes the table below max_pages (kb < len <= max_pages page_size);
@@ -157,25 +184,25 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
         pg_o += pg_do;
         if (pg_o >= a.page_size) { pg_o -= a.page_size; ++pg_i; }
     };
-    const auto load_tile = [&](int base) {      // rows past `end` read as zeros (and cost no traffic)
+    const auto load_tile = [&](int base, int sl) {      // rows past `end` read as zeros (and cost no traffic)
         if constexpr (PAGED) {
             const int page = base < end ? min(max(ent, 0), a.n_pages - 1) : 0;      // the clamp is the contract
             // (readfirstlane: the compiler clamps with v_med3_i32, and a resource with a VGPR word is loaded in a waterfall loop)
             const int rows = __builtin_amdgcn_readfirstlane(max(min(kDecodeTile, end - base), 0));
             const size_t at = slab + ((size_t)page * a.Hkv * a.page_size + ent_o) * D;      // 64-bit: a pool may exceed 4 GiB
-            const auto kp = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.K + at), 0, rows * ROWB, 0x00020000);
-            const auto vp = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.V + at), 0, rows * ROWB, 0x00020000);
+            const auto kp = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.K + at), 0, rows * ROWB, 0x00020000);
+            const auto vp = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.V + at), 0, rows * ROWB, 0x00020000);
 #pragma unroll
-            for (int t = 0; t < KS; ++t) kf[t] = __builtin_amdgcn_raw_buffer_load_b128(kp, koff + 32 * t, 0, 0);
+            for (int t = 0; t < KL; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(kp, koff + 32 * t, 0, 0);
 #pragma unroll
-            for (int n = 0; n < NV; ++n) vf[n] = __builtin_amdgcn_raw_buffer_load_b128(vp, voff + n * RPI * ROWB, 0, 0);
+            for (int n = 0; n < NV; ++n) vf[sl][n] = __builtin_amdgcn_raw_buffer_load_b128(vp, voff + n * RPI * ROWB, 0, 0);
             return;
         }
         const uint32_t b0 = (uint32_t)base * ROWB;
 #pragma unroll
-        for (int t = 0; t < KS; ++t) kf[t] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, b0 + koff + 32 * t, 0, 0);
+        for (int t = 0; t < KL; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, b0 + koff + 32 * t, 0, 0);
 #pragma unroll
-        for (int n = 0; n < NV; ++n) vf[n] = __builtin_amdgcn_raw_buffer_load_b128(v_rsrc, b0 + voff + n * RPI * ROWB, 0, 0);
+        for (int n = 0; n < NV; ++n) vf[sl][n] = __builtin_amdgcn_raw_buffer_load_b128(v_rsrc, b0 + voff + n * RPI * ROWB, 0, 0);
     };
 
     char* const vimg = smem + wave * VIMG;
@@ -189,7 +216,8 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
     for (int c = 0; c < DB; ++c)
 #pragma unroll
         for (int e = 0; e < 16; ++e) o[c][e] = 0.0f;
-    const float sc = a.scale * kLog2e;
+    float sc = a.scale * kLog2e;
+    if constexpr (EB == 1) sc *= a.k_descale ? a.k_descale[hkv] : 1.0f;
 
     int kb = begin + kDecodeTile * wave;
     if constexpr (PAGED) {      // the two divisions of a workgroup
@@ -199,60 +227,27 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
         pg_do = kDecodeKB - pg_di * a.page_size;
         fetch_entry(kb);
     }
-    load_tile(kb);
+    load_tile(kb, 0);
     if constexpr (PAGED) fetch_entry(kb + kDecodeKB);
-    for (; kb < end; kb += kDecodeKB) {
-#pragma unroll
-        for (int n = 0; n < NV; ++n)
-            *reinterpret_cast<u32x4*>(vimg + lds_off<D>(n * RPI + lane / CPR, lane % CPR)) = vf[n];
-        f32x16 s;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) s[e] = 0.0f;
-#pragma unroll
-        for (int t = 0; t < KS; ++t)
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[t]), q[t], s, 0, 0, 0);
-        load_tile(kb + kDecodeKB);
-        if constexpr (PAGED) fetch_entry(kb + 2 * kDecodeKB);      // the table entry of the tile after the next one
-
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            s[e] *= sc;
-            mx = kb + acc_row(e, h) < kmax ? fmaxf(mx, s[e]) : mx;
+    if constexpr (PF == 1) {
+        for (; kb < end; kb += kDecodeKB) {
+#define DEC_KB kb
+#define DEC_SL 0
+#include "fa2_decode_tile.inc"
         }
-        mx = half_max(mx);
-        const float m_new = fmaxf(m, mx);
-        const float m0 = m_new == -INFINITY ? 0.0f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f(m - m0);      // m = -inf: 0, and there is nothing to scale yet
-        m = m_new;
-        float ps = 0.0f;
-        bf16x8 p[2];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float pe = kb + acc_row(e, h) < kmax ? __builtin_amdgcn_exp2f(s[e] - m0) : 0.0f;
-            ps += pe;
-            p[e >> 3][e & 7] = (__bf16)pe;
-        }
-        l = l * alpha + ps;
-#pragma unroll
-        for (int c = 0; c < DB; ++c)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[c][e] *= alpha;
-        // element j of half h of k-step ks is key 16 ks + 8 (j >> 2) + 4 h + (j & 3): two transposed reads of four keys each
-#pragma unroll
-        for (int c = 0; c < DB; ++c) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                bf16x8 vt;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int row = 16 * ks + 8 * u + 4 * h + qq, col = 32 * c + c0 + 4 * pp;
-                    const bf16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (dec_lds_bf16x4*)(vimg + lds_off<D>(row, col >> 3) + 8 * (pp & 1)));
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) vt[4 * u + e] = x[e];
-                }
-                o[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt, p[ks], o[c], 0, 0, 0);
+    } else {      // two tiles in flight: slot 0 holds the wave's even tiles, slot 1 the odd ones
+        load_tile(kb + kDecodeKB, 1);
+        if constexpr (PAGED) fetch_entry(kb + 2 * kDecodeKB);
+        for (; kb < end; kb += 2 * kDecodeKB) {
+            {
+#define DEC_KB kb
+#define DEC_SL 0
+#include "fa2_decode_tile.inc"
+            }
+            if (kb + kDecodeKB < end) {
+#define DEC_KB (kb + kDecodeKB)
+#define DEC_SL 1
+#include "fa2_decode_tile.inc"
             }
         }
     }
@@ -305,13 +300,26 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
 template <int D>
 __global__ void __launch_bounds__(256) fa2_decode_split_kernel(DecodeArgs a)
 {
-    decode_split_body<D, false>(a);
+    decode_split_body<D, false, 2>(a);
 }
 
 template <int D>
 __global__ void __launch_bounds__(256) fa2_decode_paged_split_kernel(DecodeArgs a)
 {
-    decode_split_body<D, true>(a);
+    decode_split_body<D, true, 2>(a);
+}
+
+// fa2_forward_decode_fp8kv / _paged_fp8kv: the same body over e4m3 caches (EB = 1)
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_f8_split_kernel(DecodeArgs a)
+{
+    decode_split_body<D, false, 1>(a);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_f8_paged_split_kernel(DecodeArgs a)
+{
+    decode_split_body<D, true, 1>(a);
 }
 
 // rows x d / 4 lanes, a lane owns four columns of one row: partials in, ascending s, fp32; the sink; one rounding
@@ -382,8 +390,13 @@ static hipError_t decode_launch(const DecodeArgs& a, hipStream_t stream)
     constexpr int lds = kDecWaves * 32 * (D + 4) * 4 + kDecWaves * 32 * 2 * 4;
     static_assert(kDecWaves * kDecodeTile * 2 * D <= kDecWaves * 32 * (D + 4) * 4, "the V images fit under the O images");
     const unsigned grid = (unsigned)a.B * a.Hkv * a.n_splits;
-    hipError_t e = a.block_table ? launch_lds<fa2_decode_paged_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a)
-                                 : launch_lds<fa2_decode_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
+    hipError_t e;
+    if (a.kv_fp8)
+        e = a.block_table ? launch_lds<fa2_decode_f8_paged_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a)
+                          : launch_lds<fa2_decode_f8_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
+    else
+        e = a.block_table ? launch_lds<fa2_decode_paged_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a)
+                          : launch_lds<fa2_decode_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
     if (e != hipSuccess || a.n_splits == 1) return e;
     const size_t threads = (size_t)a.B * a.Hq * a.Nq * (D / 4);
     hipLaunchKernelGGL(fa2_decode_combine_kernel<D>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);

@@ -90,9 +90,13 @@ struct DecodeArgs {
     // sequence b is row j % page_size of page block_table[b][j / page_size] (DEVICE, int [B][max_pages]).  All zero: contiguous.
     const int* block_table;
     int n_pages, page_size, max_pages;
+    // fa2_forward_decode_fp8kv / _paged_fp8kv: kv_fp8 = 1, K and V hold OCP e4m3 bytes, the stored value of head h being
+    // x / descale[h] (DEVICE, fp32 [Hkv]; nullptr = 1: scores softmax_scale k_descale[h] (Q . K8), O = v_descale[h] P V8).  All zero: bf16.
+    const float* k_descale; const float* v_descale;
+    int kv_fp8;
 };
 int decode_num_splits(int B, int H_kv, int kv_capacity);      // pure host arithmetic: fa2_decode_num_splits
-hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream);      // d = 64 | 128; 1 <= G Nq <= 32; block_table: paged
+hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream);      // d = 64 | 128; 1 <= G Nq <= 32; block_table: paged; kv_fp8: e4m3
 
 // fp8 (OCP e4m3) forward, d = 128: Q, K, V fp8 [BH][N][128]; O bf16; Vt: [BH][128][Npad] fp8 scratch the
 // launcher fills with V transposed (Npad = N rounded up to 64); kn: [BH][Npad / 64] fp32 scratch it fills with the largest

@@ -318,19 +318,60 @@ DECODE_MAX_ROWS = 32      # (H_q / H_kv) N_q: the query rows of one K/V head fil
 DECODE_MAX_SPLITS = 256
 
 
-def _decode_shapes(Q, K_cache, V_cache):
-    """(B, H, H_kv, N_q, N_cap, d) of a decode problem: Q [B, H, N_q, d] against caches [B, H_kv, N_cap, d], bf16, H_kv dividing
-    H.  Shapes and dtypes first (_qkv_shapes); device and contiguity are the caller's to check next."""
-    B, H, Hkv, Nq, Ncap, d = _qkv_shapes(Q, K_cache, V_cache, "K_cache", "V_cache", "N_cap", "decode is")
-    for n, t in (("K_cache", K_cache), ("V_cache", V_cache)):
+_FP8_NOT_TAKEN = tuple(getattr(torch, n) for n in ("float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz") if hasattr(torch, n))
+
+
+def _kv_dtypes(Q, K, V, kname, vname):
+    """The dtypes of a decode call's caches beside a bf16 Q: both Q's, or both torch.float8_e4m3fn (OCP e4m3; returns True)."""
+    for n, t in ((kname, K), (vname, V)):
+        if t.dtype in _FP8_NOT_TAKEN:
+            raise ValueError(f"{n}: dtype {t.dtype}; an fp8 cache is OCP e4m3 (torch.float8_e4m3fn), the encoding gfx950 converts natively")
+    fp8 = [t.dtype == torch.float8_e4m3fn for t in (K, V)]
+    if fp8[0] != fp8[1]:
+        raise ValueError(f"{vname}: dtype {V.dtype} beside {kname} {K.dtype}: K and V are both torch.float8_e4m3fn or both {Q.dtype}")
+    if all(fp8):
+        return True
+    for n, t in ((kname, K), (vname, V)):
         if t.dtype != Q.dtype:
             raise ValueError(f"{n}: dtype {t.dtype}, expected {Q.dtype}")
+    return False
+
+
+def _descale_arg(descale, Q, Hkv, name, fp8, kname):
+    """k_descale / v_descale beside Q and e4m3 caches, checked like a sink (_sink_arg): a contiguous fp32 tensor of H_kv elements
+    on Q's device.  The kernels read it ON THE DEVICE when they run, like seqlens_k; the host never does."""
+    if not fp8:
+        raise ValueError(f"{name}: a descale belongs to torch.float8_e4m3fn caches; {kname} is {Q.dtype} and holds its own values")
+    if not isinstance(descale, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor (fp32 [{Hkv}] on Q's device: the kernels read it on the device when they run)")
+    if descale.dtype != torch.float32:
+        raise ValueError(f"{name}: dtype {descale.dtype}, expected torch.float32")
+    if descale.dim() != 1 or descale.numel() != Hkv:
+        raise ValueError(f"{name}: shape {tuple(descale.shape)}, expected ({Hkv},): one descale per K/V head")
+    if not descale.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (got stride {tuple(descale.stride())}; call .contiguous())")
+    if not descale.is_cuda:
+        raise ValueError(f"{name} must be a device tensor")
+    if descale.device != Q.device:
+        raise ValueError(f"{name} is on {descale.device}, expected {Q.device}")
+    return descale
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _decode_shapes(Q, K_cache, V_cache):
+    """(B, H, H_kv, N_q, N_cap, d, fp8) of a decode problem: Q [B, H, N_q, d] bf16 against caches [B, H_kv, N_cap, d], bf16 or (fp8)
+    e4m3, H_kv dividing H.  Shapes and dtypes first (_qkv_shapes); device and contiguity are the caller's to check next."""
+    B, H, Hkv, Nq, Ncap, d = _qkv_shapes(Q, K_cache, V_cache, "K_cache", "V_cache", "N_cap", "decode is")
+    fp8 = _kv_dtypes(Q, K_cache, V_cache, "K_cache", "V_cache")
     if d not in (64, 128):
         raise ValueError(f"Q: head_dim {d}, expected 64 or 128")
     if (H // Hkv) * Nq > DECODE_MAX_ROWS:
         raise ValueError(f"Q: {H // Hkv} query heads per K/V head x {Nq} query tokens = {(H // Hkv) * Nq} rows, decode takes at most "
                          f"{DECODE_MAX_ROWS}: that is a prefill chunk, use flash_attention_2_qk_forward")
-    return B, H, Hkv, Nq, Ncap, d
+    return B, H, Hkv, Nq, Ncap, d, fp8
 
 
 def _seqlens_arg(seqlens_k, Q, B):
@@ -364,7 +405,7 @@ def decode_workspace(B, H, H_kv, N_q, kv_capacity, d, n_splits=0, device="cuda")
 
 
 def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=None, causal=True, sink=None, n_splits=0,
-                             O=None, L=None, workspace=None, stream=None):
+                             O=None, L=None, workspace=None, stream=None, k_descale=None, v_descale=None):
     """O, L = attention of a few new tokens per sequence against a preallocated KV cache (fa2_forward_decode): Q [B, H, N_q, d],
     K_cache and V_cache [B, H_kv, N_cap, d] (H_kv dividing H, (H / H_kv) N_q <= 32), bf16, d = 64 | 128.  INFERENCE ONLY: there is
     no autograd and no backward.
@@ -376,17 +417,27 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     split needs a workspace (decode_workspace); it is allocated per call when omitted -- PASS ONE FOR GRAPH CAPTURE, with O, L and a
     seqlens_k tensor that is updated in place between replays.
     The returned (O, L) is what merge_states_forward takes: a cache held in two allocations is two calls (the first with
-    causal=False and no sink, the last with the mask and the sink) and a merge."""
-    B, H, Hkv, Nq, Ncap, d = _decode_shapes(Q, K_cache, V_cache)
+    causal=False and no sink, the last with the mask and the sink) and a merge.
+    FP8 CACHES (fa2_forward_decode_fp8kv): K_cache and V_cache may both be torch.float8_e4m3fn (OCP e4m3), half the bytes to hold and
+    to stream; Q, O and L are unchanged.  k_descale, v_descale: fp32 [H_kv] DEVICE tensors or None (= 1).  A cache stores x as
+    x / descale[h_kv]: the scores are softmax_scale * k_descale[h] * (Q . K8) and O = v_descale[h] * P V8.  The kernels read them on
+    the device when they run (positive and finite by contract; the host never reads them), so they may be updated in place under a
+    captured graph.  Everything above holds unchanged; bytes past a length may be anything, e4m3's NaN codes included.  There is
+    still no append kernel: a framework cast and scatter, (x / descale).clamp(-448, 448).to(torch.float8_e4m3fn) -- torch's cast
+    does not saturate --, writes the cache."""
+    B, H, Hkv, Nq, Ncap, d, fp8 = _decode_shapes(Q, K_cache, V_cache)
     if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
     if seqlens_k is not None:
         _seqlens_arg(seqlens_k, Q, B)
     if sink is not None:
         _sink_arg(sink, Q, 1)
+    for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if t is not None:
+            _descale_arg(t, Q, Hkv, name, fp8, "K_cache")
     _bhnd(Q, "Q")
-    _like(K_cache, "K_cache", Q, (B, Hkv, Ncap, d), Q.dtype)
-    _like(V_cache, "V_cache", Q, (B, Hkv, Ncap, d), Q.dtype)
+    _like(K_cache, "K_cache", Q, (B, Hkv, Ncap, d), K_cache.dtype)
+    _like(V_cache, "V_cache", Q, (B, Hkv, Ncap, d), K_cache.dtype)
     scale = _scale(softmax_scale, d)
     if not scale > 0.0:
         raise ValueError(f"softmax_scale: {scale}, expected a positive number")
@@ -398,11 +449,15 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
     if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
         raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (decode_workspace)")
-    st = lib.fa2_forward_decode(Q.data_ptr(), K_cache.data_ptr(), V_cache.data_ptr(), None if seqlens_k is None else seqlens_k.data_ptr(),
-                                None if sink is None else sink.data_ptr(), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d, scale,
-                                FA2_DTYPE_BF16, 1 if causal else 0, n_splits, None if workspace is None else workspace.data_ptr(),
-                                0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
-    check(st, "fa2_forward_decode")
+    head = (Q.data_ptr(), K_cache.data_ptr(), V_cache.data_ptr(), _ptr(seqlens_k), _ptr(sink))
+    tail = (1 if causal else 0, n_splits, _ptr(workspace), 0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
+    if fp8:
+        st = lib.fa2_forward_decode_fp8kv(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d,
+                                          scale, FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3, *tail)
+        check(st, "fa2_forward_decode_fp8kv")
+    else:
+        st = lib.fa2_forward_decode(*head, O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d, scale, FA2_DTYPE_BF16, *tail)
+        check(st, "fa2_forward_decode")
     return O, L
 
 
@@ -430,8 +485,9 @@ def _block_table_arg(block_table, Q, B):
 
 
 def _decode_paged_shapes(Q, K_pages, V_pages):
-    """(B, H, H_kv, N_q, n_pages, page_size, d) of a paged decode problem: Q [B, H, N_q, d] against pools [n_pages, H_kv, page_size,
-    d], bf16, H_kv dividing H, page_size a multiple of 32.  Device and contiguity are the caller's to check next."""
+    """(B, H, H_kv, N_q, n_pages, page_size, d, fp8) of a paged decode problem: Q [B, H, N_q, d] bf16 against pools [n_pages, H_kv,
+    page_size, d], bf16 or (fp8) e4m3, H_kv dividing H, page_size a multiple of 32.  Device and contiguity are the caller's to check
+    next."""
     for n, t in (("Q", Q), ("K_pages", K_pages), ("V_pages", V_pages)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise ValueError(f"{n}: expected a 4-d tensor ({'[B, H, N_q, d]' if n == 'Q' else '[n_pages, H_kv, page_size, d]'}), got "
@@ -448,19 +504,17 @@ def _decode_paged_shapes(Q, K_pages, V_pages):
         raise ValueError(f"V_pages: shape {tuple(V_pages.shape)} does not match K_pages {tuple(K_pages.shape)}")
     if Q.dtype != torch.bfloat16:
         raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16 (decode is bf16 in this version)")
-    for n, t in (("K_pages", K_pages), ("V_pages", V_pages)):
-        if t.dtype != Q.dtype:
-            raise ValueError(f"{n}: dtype {t.dtype}, expected {Q.dtype}")
+    fp8 = _kv_dtypes(Q, K_pages, V_pages, "K_pages", "V_pages")
     if d not in (64, 128):
         raise ValueError(f"Q: head_dim {d}, expected 64 or 128")
     if (H // Hkv) * Nq > DECODE_MAX_ROWS:
         raise ValueError(f"Q: {H // Hkv} query heads per K/V head x {Nq} query tokens = {(H // Hkv) * Nq} rows, decode takes at most "
                          f"{DECODE_MAX_ROWS}: that is a prefill chunk, use flash_attention_2_qk_forward")
-    return B, H, Hkv, Nq, n_pages, page_size, d
+    return B, H, Hkv, Nq, n_pages, page_size, d, fp8
 
 
 def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=None, softmax_scale=None, causal=True, sink=None,
-                                   n_splits=0, O=None, L=None, workspace=None, stream=None):
+                                   n_splits=0, O=None, L=None, workspace=None, stream=None, k_descale=None, v_descale=None):
     """O, L = flash_attention_2_decode over a KV cache held as a pool of pages (fa2_forward_decode_paged): Q [B, H, N_q, d], K_pages
     and V_pages [n_pages, H_kv, page_size, d] (head-major; H_kv dividing H, (H / H_kv) N_q <= 32, page_size a multiple of 32, not
     necessarily a power of two), bf16, d = 64 | 128.  A token-major pool [n_pages, page_size, H_kv, d] needs one permute when it is
@@ -473,10 +527,17 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     mask, rows without a key, sink and n_splits holds with it: n_splits=0 is decode_num_splits(B, H_kv, kv_capacity, d), the
     workspace is decode_workspace(B, H, H_kv, N_q, kv_capacity, d, n_splits) -- PASS ONE FOR GRAPH CAPTURE, with O, L, and seqlens_k
     and block_table tensors that are updated in place between replays (a sequence grows into a new page, pages are reassigned).
-    With the same n_splits the result is bit for bit flash_attention_2_decode's on the gathered cache of that capacity."""
-    B, H, Hkv, Nq, n_pages, page_size, d = _decode_paged_shapes(Q, K_pages, V_pages)
+    With the same n_splits the result is bit for bit flash_attention_2_decode's on the gathered cache of that capacity.
+    FP8 POOLS (fa2_forward_decode_paged_fp8kv): K_pages and V_pages may both be torch.float8_e4m3fn with k_descale, v_descale (fp32
+    [H_kv] DEVICE tensors or None = 1; a pool stores x as x / descale[h_kv]), exactly as flash_attention_2_decode describes them:
+    read on the device, never by the host; unused pages may hold any byte.  There is still no append kernel: a framework cast
+    and scatter through the same table writes the pool."""
+    B, H, Hkv, Nq, n_pages, page_size, d, fp8 = _decode_paged_shapes(Q, K_pages, V_pages)
     if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
+    for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):      # (they belong to the pools' dtype: checked with it)
+        if t is not None:
+            _descale_arg(t, Q, Hkv, name, fp8, "K_pages")
     max_pages = _block_table_arg(block_table, Q, B)
     kv_capacity = max_pages * page_size
     if kv_capacity > 0x7fffffff - (DECODE_MAX_SPLITS + 2) * 128:
@@ -486,8 +547,8 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     if sink is not None:
         _sink_arg(sink, Q, 1)
     _bhnd(Q, "Q")
-    _like(K_pages, "K_pages", Q, (n_pages, Hkv, page_size, d), Q.dtype)
-    _like(V_pages, "V_pages", Q, (n_pages, Hkv, page_size, d), Q.dtype)
+    _like(K_pages, "K_pages", Q, (n_pages, Hkv, page_size, d), K_pages.dtype)
+    _like(V_pages, "V_pages", Q, (n_pages, Hkv, page_size, d), K_pages.dtype)
     scale = _scale(softmax_scale, d)
     if not scale > 0.0:
         raise ValueError(f"softmax_scale: {scale}, expected a positive number")
@@ -499,12 +560,16 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
     if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
         raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (decode_workspace)")
-    st = lib.fa2_forward_decode_paged(Q.data_ptr(), K_pages.data_ptr(), V_pages.data_ptr(), block_table.data_ptr(),
-                                      None if seqlens_k is None else seqlens_k.data_ptr(), None if sink is None else sink.data_ptr(),
-                                      O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, n_pages, page_size, max_pages, d, scale, FA2_DTYPE_BF16,
-                                      1 if causal else 0, n_splits, None if workspace is None else workspace.data_ptr(),
-                                      0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
-    check(st, "fa2_forward_decode_paged")
+    head = (Q.data_ptr(), K_pages.data_ptr(), V_pages.data_ptr(), block_table.data_ptr(), _ptr(seqlens_k), _ptr(sink))
+    dims = (B, H, Hkv, Nq, n_pages, page_size, max_pages, d, scale)
+    tail = (1 if causal else 0, n_splits, _ptr(workspace), 0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
+    if fp8:
+        st = lib.fa2_forward_decode_paged_fp8kv(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), *dims,
+                                                FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3, *tail)
+        check(st, "fa2_forward_decode_paged_fp8kv")
+    else:
+        st = lib.fa2_forward_decode_paged(*head, O.data_ptr(), L.data_ptr(), *dims, FA2_DTYPE_BF16, *tail)
+        check(st, "fa2_forward_decode_paged")
     return O, L
 
 

@@ -428,8 +428,9 @@ int fa2_merge_states_backward(const void* const* O_parts, const float* const* L_
  * dividing H_q, n_splits outside 0..256, a (b, head) cache slab of 2 GiB or more (kv_capacity x head_dim x 2 bytes; the whole
  * cache may be larger) -> FA2_ERR_INVALID_SHAPE; FA2_ERR_UNSUPPORTED_HEAD_DIM; FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace
  * NULL, misaligned or too small while the resolved split count is > 1 -> FA2_ERR_WORKSPACE; M > 32 -> FA2_ERR_UNSUPPORTED.
- * NOT COVERED: [B][N][H][d] layouts, a cache-append kernel (a framework's scatter does it), M > 32, fp8 or fp32 caches, sliding
- * windows, a backward, the ring.  (A cache held as a pool of pages with a block table: fa2_forward_decode_paged below.) */
+ * NOT COVERED: [B][N][H][d] layouts, a cache-append kernel (a framework's scatter does it), M > 32, fp32 caches, sliding
+ * windows, a backward, the ring.  (A cache held as a pool of pages with a block table: fa2_forward_decode_paged below; e4m3
+ * caches: the _fp8kv calls below.) */
 int fa2_decode_num_splits(int B, int H_kv, int kv_capacity, int head_dim);
 size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, int n_splits);
 int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
@@ -465,13 +466,45 @@ int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, 
  * FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace NULL, misaligned or too small while the resolved split count is > 1 ->
  * FA2_ERR_WORKSPACE; M = (H_q / H_kv) q_len > 32 -> FA2_ERR_UNSUPPORTED.
  * NOT COVERED: token-major pages [n_pages][page_size][H_kv][d] (permute such a pool once, when it is allocated), page_size 16, a
- * cache-append kernel (a framework's scatter through the same table does it), fp8 pages; and what fa2_forward_decode leaves out:
- * M > 32, sliding windows, a backward, the ring. */
+ * cache-append kernel (a framework's scatter through the same table does it); and what fa2_forward_decode leaves out:
+ * M > 32, sliding windows, a backward, the ring.  (e4m3 pages: fa2_forward_decode_paged_fp8kv below.) */
 int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
                              const int* seqlens_k, const float* sink, void* O, float* L,
                              int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
                              int head_dim, float softmax_scale, int dtype, int causal, int n_splits,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Decode over fp8 KV caches: fa2_forward_decode and fa2_forward_decode_paged with K and V stored in OCP e4m3
+ * (FA2_DTYPE_FP8_E4M3: torch.float8_e4m3fn, gfx950's native encoding; not e5m2, not the fnuz form), one byte per element: half
+ * the cache's footprint and half the traffic of a call that is bound by that traffic.  Q and O stay bf16, L fp32; P stays bf16.
+ * LAYOUT.  K_cache, V_cache [B][H_kv][kv_capacity][d], K_pages, V_pages [n_pages][H_kv][page_size][d]: the bf16 layouts, one byte
+ * per element.  K and V are both e4m3.
+ * DESCALES.  k_descale, v_descale: fp32 [H_kv] in DEVICE memory, or NULL (= 1).  The cache holds x / descale[h_kv], so the scores
+ * are softmax_scale x k_descale[h] x (Q . K8), O = v_descale[h] x P V8 and L is the log-sum-exp of those scores (then the sink).
+ * They are positive and finite by contract; like seqlens_k the kernel reads them when it runs and the host never does, so a
+ * captured graph serves a cache whose descales are updated in place.  The kernel widens e4m3 to bf16 in registers (exact), folds
+ * k_descale into the scalar every score is multiplied by and multiplies the fp32 result (a split's partial) by v_descale before
+ * the one rounding to bf16; both products are the bf16 MFMAs of the bf16 call, so the result is that call's on the dequantised
+ * cache up to the rounding of the descaled values to bf16, which this call does not do.
+ * EVERYTHING ELSE is the bf16 sibling's, word for word: seqlens_k and its clamp, the bottom-right mask, rows without a key, sink,
+ * n_splits and fa2_decode_num_splits, the workspace (fa2_decode_workspace_bytes: the same for both element sizes) and the combine,
+ * the block table, its clamp and shared pages, determinism, and paged == contiguous bit for bit at equal n_splits.  Cache bytes
+ * at or beyond a length and in unused pages may hold anything, the e4m3 NaN codes 0x7F and 0xFF included: they are read as zeros.
+ * dtype is Q's and O's (FA2_DTYPE_BF16); kv_dtype is the caches' (FA2_DTYPE_FP8_E4M3).
+ * STATUS CODES: the sibling's, in its order; either dtype other than the above -> FA2_ERR_UNSUPPORTED_DTYPE where the sibling
+ * reports its dtype (after the head_dim); the contiguous slab limit is kv_capacity x head_dim x 1 byte below 2 GiB.
+ * NOT COVERED: a quantising cache-append kernel (a framework's cast and scatter writes the cache), fp8 Q or an fp8 second
+ * product, per-token or per-page scales, e5m2, and what the siblings leave out. */
+int fa2_forward_decode_fp8kv(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
+                             const float* k_descale, const float* v_descale, void* O, float* L,
+                             int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
+                             int dtype, int kv_dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream);
+int fa2_forward_decode_paged_fp8kv(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
+                                   const int* seqlens_k, const float* sink, const float* k_descale, const float* v_descale,
+                                   void* O, float* L,
+                                   int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
+                                   int head_dim, float softmax_scale, int dtype, int kv_dtype, int causal, int n_splits,
+                                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output
