@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <numeric>
 #include <vector>
@@ -380,6 +381,7 @@ int fa2_forward_fp8_scaled(const void* Q, const void* K, const void* V, void* O,
 {
     if (!Q || !K || !V || !O || !L) return FA2_ERR_NULL_POINTER;
     if (!(q_descale > 0.0f) || !(k_descale > 0.0f) || !(v_descale > 0.0f)) return FA2_ERR_INVALID_SHAPE;
+    if (!std::isfinite(q_descale) || !std::isfinite(k_descale) || !std::isfinite(v_descale)) return FA2_ERR_INVALID_SHAPE;      // +inf
     int st = check_common(B, H, seq_len, head_dim, softmax_scale);
     if (st) return st;
     // scores are formed from the STORED values: the two descales belong to the softmax scale (the lazy reference, its

@@ -111,7 +111,8 @@ int fa2_forward_fp8(const void* Q, const void* K, const void* V, void* O, float*
  * the scores are softmax_scale (q_descale Q)(k_descale K)^T and O = P (v_descale V).  fa2_forward_fp8 is this call with the
  * three descales 1 -- i.e. for tensors whose own values fit e4m3 (|x| <= 448); a caller with scaled tensors who uses that
  * entry point must fold q_descale k_descale into softmax_scale and multiply O by v_descale himself.  L is the log-sum-exp
- * of the DESCALED scores either way.  Descales must be positive and finite. */
+ * of the DESCALED scores either way.  Each of the three descales must be positive and finite: zero, a negative number, NaN and
+ * +inf are refused with FA2_ERR_INVALID_SHAPE before anything is launched. */
 int fa2_forward_fp8_scaled(const void* Q, const void* K, const void* V, void* O, float* L,
                            int B, int H, int seq_len, int head_dim, float softmax_scale,
                            float q_descale, float k_descale, float v_descale, int causal,
