@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FA2_LIB_PATH") or os.path.join(_HERE, "lib", "libfa2_mi355x.so")
 RING_LIB_PATH = os.path.join(_HERE, "lib", "libfa2_ring_mi355x.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mi355x.h")
+KVCACHE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_kvcache_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -23,6 +24,7 @@ _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
+_ll = ctypes.c_longlong
 
 # name -> (restype, argtypes); mirrors include/fa2_mi355x.h declaration by declaration.
 SIGNATURES = {
@@ -88,6 +90,13 @@ SIGNATURES = {
     "fa2_convert_bf16_to_f32": (_i, [_vp, _vp, _sz, _vp]),
 }
 
+# include/fa2_kvcache_mi355x.h, the same library: a table of its own because SIGNATURES is pinned to fa2_mi355x.h (the C ABI is
+# also linked against stub launchers, which have no kernels of this header's).
+KVCACHE_SIGNATURES = {
+    "fa2_kv_append": (_i, [_vp] * 7 + [_i] * 5 + [_ll] * 3 + [_i, _i, _vp]),
+    "fa2_kv_append_paged": (_i, [_vp] * 8 + [_i] * 7 + [_ll] * 3 + [_i, _i, _vp]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -112,7 +121,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `make -C cuda_flashattention_amd/csrc` "
                 "(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

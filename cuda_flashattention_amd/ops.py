@@ -422,9 +422,11 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     to stream; Q, O and L are unchanged.  k_descale, v_descale: fp32 [H_kv] DEVICE tensors or None (= 1).  A cache stores x as
     x / descale[h_kv]: the scores are softmax_scale * k_descale[h] * (Q . K8) and O = v_descale[h] * P V8.  The kernels read them on
     the device when they run (positive and finite by contract; the host never reads them), so they may be updated in place under a
-    captured graph.  Everything above holds unchanged; bytes past a length may be anything, e4m3's NaN codes included.  There is
-    still no append kernel: a framework cast and scatter, (x / descale).clamp(-448, 448).to(torch.float8_e4m3fn) -- torch's cast
-    does not saturate --, writes the cache."""
+    captured graph.  Everything above holds unchanged; bytes past a length may be anything, e4m3's NaN codes included.
+    WRITING THE CACHE: there is no append kernel inside this call; kv_cache_append is that call, bf16 or e4m3, and takes this
+    call's seqlens_k tensor: bump the lengths in place, append, decode.  It stores (x / descale).clamp(-448, 448)
+    .to(torch.float8_e4m3fn) byte for byte and saturates; a framework cast in its place needs that clamp --
+    torch's cast does not saturate, an overflow becomes a NaN code."""
     B, H, Hkv, Nq, Ncap, d, fp8 = _decode_shapes(Q, K_cache, V_cache)
     if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
@@ -530,8 +532,9 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     With the same n_splits the result is bit for bit flash_attention_2_decode's on the gathered cache of that capacity.
     FP8 POOLS (fa2_forward_decode_paged_fp8kv): K_pages and V_pages may both be torch.float8_e4m3fn with k_descale, v_descale (fp32
     [H_kv] DEVICE tensors or None = 1; a pool stores x as x / descale[h_kv]), exactly as flash_attention_2_decode describes them:
-    read on the device, never by the host; unused pages may hold any byte.  There is still no append kernel: a framework cast
-    and scatter through the same table writes the pool."""
+    read on the device, never by the host; unused pages may hold any byte.
+    WRITING THE POOL: there is no append kernel inside this call; kv_cache_append_paged is that call, through the same table and
+    seqlens_k tensors: bump the lengths (and assign a new page's entry) in place, append, decode."""
     B, H, Hkv, Nq, n_pages, page_size, d, fp8 = _decode_paged_shapes(Q, K_pages, V_pages)
     if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
@@ -571,6 +574,137 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
         st = lib.fa2_forward_decode_paged(*head, O.data_ptr(), L.data_ptr(), *dims, FA2_DTYPE_BF16, *tail)
         check(st, "fa2_forward_decode_paged")
     return O, L
+
+
+def _kv_new_arg(K_new, V_new):
+    """(B, H_kv, n_new, d, (stride_b, stride_h, stride_t)) of an append's source: bf16 [B, H_kv, n_new, d] VIEWS with the last
+    dimension contiguous and one stride triple for both, each a non-negative multiple of 8 elements, 16-byte aligned -- a lane
+    loads 16 bytes.  No copy is made: a token-major tensor or a slice of a fused QKV output is passed permuted."""
+    how = ("pass [B, H_kv, n_new, d] views, e.g. x.permute(0, 2, 1, 3) of a token-major [B, n_new, H_kv, d] tensor or the K and V "
+           "slices of one fused QKV output")
+    for n, t in (("K_new", K_new), ("V_new", V_new)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a 4-d tensor [B, H_kv, n_new, d], got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}; {how}")
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{n}: dtype {t.dtype}, expected torch.bfloat16 (the source of an append is bf16; the cache may be e4m3)")
+    B, Hkv, n_new, d = K_new.shape
+    if min(B, Hkv, n_new) < 1:
+        raise ValueError(f"K_new: shape {tuple(K_new.shape)}, expected [B, H_kv, n_new, d] with B, H_kv, n_new >= 1")
+    if tuple(V_new.shape) != tuple(K_new.shape):
+        raise ValueError(f"V_new: shape {tuple(V_new.shape)} does not match K_new {tuple(K_new.shape)}")
+    if d not in (64, 128):
+        raise ValueError(f"K_new: head_dim {d}, expected 64 or 128")
+    for n, t in (("K_new", K_new), ("V_new", V_new)):
+        if t.stride(-1) != 1:
+            raise ValueError(f"{n}: stride {tuple(t.stride())}, the last dimension must be contiguous (stride(-1) == 1); {how}")
+    if tuple(V_new.stride()) != tuple(K_new.stride()):
+        raise ValueError(f"V_new: strides {tuple(V_new.stride())} differ from K_new's {tuple(K_new.stride())}: one (batch, head, token) "
+                         f"stride triple serves both; {how}")
+    strides = tuple(K_new.stride()[:3])
+    if any(s < 0 or s % 8 for s in strides):
+        raise ValueError(f"K_new: strides {strides} (batch, head, token) must be non-negative multiples of 8 elements: a lane loads 16 bytes")
+    for n, t in (("K_new", K_new), ("V_new", V_new)):
+        if t.storage_offset() % 8:
+            raise ValueError(f"{n}: storage offset {t.storage_offset()} elements is not 16-byte aligned (a multiple of 8): a lane loads 16 bytes")
+    return B, Hkv, n_new, d, strides
+
+
+def _kv_append_dtypes(K_new, K, V, kname, vname, Hkv, k_descale, v_descale):
+    """The caches' dtypes beside an append's source (returns fp8) and the descales that belong to them."""
+    fp8 = _kv_dtypes(K_new, K, V, kname, vname)
+    for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if t is not None:
+            _descale_arg(t, K_new, Hkv, name, fp8, kname)
+    return fp8
+
+
+def _kv_append_devices(K_new, V_new, K, V, kname, vname, shape):
+    """Last, like every wrapper here: the source on a device, the caches contiguous on that device (_like)."""
+    for n, t in (("K_new", K_new), ("V_new", V_new)):
+        if not t.is_cuda:
+            raise ValueError(f"{n} must be a device tensor")
+    if V_new.device != K_new.device:
+        raise ValueError(f"V_new is on {V_new.device}, expected {K_new.device}")
+    _like(K, kname, K_new, shape, K.dtype)
+    _like(V, vname, K_new, shape, K.dtype)
+
+
+def kv_cache_append(K_new, V_new, K_cache, V_cache, seqlens_k, k_descale=None, v_descale=None, stream=None):
+    """Append the n_new newest tokens' K and V of every sequence to the caches flash_attention_2_decode reads (fa2_kv_append), IN
+    PLACE, in one launch; returns None.  K_new, V_new: bf16 [B, H_kv, n_new, d] VIEWS (d = 64 | 128) with stride(-1) == 1 and equal
+    strides, non-negative multiples of 8 elements: a token-major [B, n_new, H_kv, d] tensor permuted, or the K and V slices of a
+    fused QKV projection output -- no .contiguous() copy.  K_cache, V_cache: [B, H_kv, N_cap, d] contiguous, both bf16 (the source
+    bits are copied) or both torch.float8_e4m3fn: head h then stores (x.float() / descale[h]).clamp(-448, 448).to(float8_e4m3fn),
+    byte for byte (saturating: inf -> +-448, NaN -> a NaN code), k_descale / v_descale fp32 [H_kv] DEVICE tensors or None (= 1), the
+    decode call's.
+    seqlens_k: int32 [B] DEVICE tensor, required, the lengths AFTER the append -- the tensor the decode call of the same step
+    reads.  A step is: seqlens_k += n_new (in place), kv_cache_append, flash_attention_2_decode; one captured graph serves every
+    step.  Token t of sequence b goes to row seqlens_k[b] - n_new + t and is written iff that row is in [0, N_cap); every other
+    token is dropped, nothing is clamped into range.  The host never reads seqlens_k or a descale, nothing is allocated.
+    A source that overlaps the cache is undefined."""
+    B, Hkv, n_new, d, strides = _kv_new_arg(K_new, V_new)
+    for n, t in (("K_cache", K_cache), ("V_cache", V_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a 4-d tensor [B, H_kv, N_cap, d], got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    Ncap = K_cache.shape[2]
+    shape = (B, Hkv, Ncap, d)
+    if tuple(K_cache.shape) != shape or Ncap < 1:
+        raise ValueError(f"K_cache: shape {tuple(K_cache.shape)} does not match K_new {tuple(K_new.shape)}: expected [{B}, {Hkv}, N_cap, {d}]")
+    if tuple(V_cache.shape) != shape:
+        raise ValueError(f"V_cache: shape {tuple(V_cache.shape)} does not match K_cache {tuple(K_cache.shape)}")
+    fp8 = _kv_append_dtypes(K_new, K_cache, V_cache, "K_cache", "V_cache", Hkv, k_descale, v_descale)
+    if seqlens_k is None:
+        raise ValueError("seqlens_k is required: an append writes token t of sequence b at row seqlens_k[b] - n_new + t (the lengths "
+                         "AFTER the append, the decode call's tensor); 'all of the capacity' has no meaning for a write")
+    _seqlens_arg(seqlens_k, K_new, B)
+    _kv_append_devices(K_new, V_new, K_cache, V_cache, "K_cache", "V_cache", shape)
+    st = _capi.lib().fa2_kv_append(K_new.data_ptr(), V_new.data_ptr(), K_cache.data_ptr(), V_cache.data_ptr(), seqlens_k.data_ptr(),
+                                   _ptr(k_descale), _ptr(v_descale), B, Hkv, n_new, Ncap, d, *strides, FA2_DTYPE_BF16,
+                                   FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, _stream_ptr(stream))
+    check(st, "fa2_kv_append")
+
+
+def kv_cache_append_paged(K_new, V_new, K_pages, V_pages, block_table, seqlens_k, k_descale=None, v_descale=None, stream=None):
+    """kv_cache_append into a pool of pages (fa2_kv_append_paged), the pool flash_attention_2_decode_paged reads: K_pages, V_pages
+    [n_pages, H_kv, page_size, d] contiguous, page_size a multiple of 32, bf16 or torch.float8_e4m3fn; block_table int32
+    [B, max_pages] DEVICE tensor.  Row pos = seqlens_k[b] - n_new + t is row pos % page_size of page block_table[b, pos // page_size];
+    it is written iff 0 <= pos < max_pages * page_size AND that table entry lies in [0, n_pages) -- a token whose entry does not is
+    DROPPED (the decode clamps such an entry; a write through a clamped entry would corrupt another sequence's page) while its
+    neighbours on other pages are written.  Only the table entries of written rows are read; the host reads none.
+    PAGES WRITTEN BY ONE CALL MUST BELONG TO ONE SEQUENCE EACH: shared prefix pages are read-only to an append, and allocating
+    pages (assign the entry before the step that grows into it) and copy-on-write stay the allocator's.  Everything else is
+    kv_cache_append's: the source views, the values, the descales, seqlens_k (required, the lengths after the append), in place,
+    one launch, returns None."""
+    B, Hkv, n_new, d, strides = _kv_new_arg(K_new, V_new)
+    for n, t in (("K_pages", K_pages), ("V_pages", V_pages)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a 4-d tensor [n_pages, H_kv, page_size, d], got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    n_pages, hk, page_size, dk = K_pages.shape
+    if hk != Hkv or dk != d or n_pages < 1 or page_size < 1:
+        raise ValueError(f"K_pages: shape {tuple(K_pages.shape)} does not match K_new {tuple(K_new.shape)}: expected "
+                         f"[n_pages, {Hkv}, page_size, {d}] with n_pages, page_size >= 1")
+    if page_size % DECODE_PAGE_GRAIN:
+        raise ValueError(f"K_pages: page_size {page_size} is not a multiple of {DECODE_PAGE_GRAIN} (the decode kernel's key tile; a page "
+                         "of 16 keys is not taken)")
+    shape = (n_pages, Hkv, page_size, d)
+    if tuple(V_pages.shape) != shape:
+        raise ValueError(f"V_pages: shape {tuple(V_pages.shape)} does not match K_pages {tuple(K_pages.shape)}")
+    fp8 = _kv_append_dtypes(K_new, K_pages, V_pages, "K_pages", "V_pages", Hkv, k_descale, v_descale)
+    if seqlens_k is None:
+        raise ValueError("seqlens_k is required: an append writes token t of sequence b at row seqlens_k[b] - n_new + t (the lengths "
+                         "AFTER the append, the decode call's tensor); 'all of the capacity' has no meaning for a write")
+    max_pages = _block_table_arg(block_table, K_new, B)
+    if max_pages * page_size > 0x7fffffff - (DECODE_MAX_SPLITS + 2) * 128:
+        raise ValueError(f"block_table: {max_pages} pages of {page_size} keys is a capacity of {max_pages * page_size} keys, above what an int indexes")
+    _seqlens_arg(seqlens_k, K_new, B)
+    _kv_append_devices(K_new, V_new, K_pages, V_pages, "K_pages", "V_pages", shape)
+    st = _capi.lib().fa2_kv_append_paged(K_new.data_ptr(), V_new.data_ptr(), K_pages.data_ptr(), V_pages.data_ptr(),
+                                         block_table.data_ptr(), seqlens_k.data_ptr(), _ptr(k_descale), _ptr(v_descale),
+                                         B, Hkv, n_new, n_pages, page_size, max_pages, d, *strides, FA2_DTYPE_BF16,
+                                         FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, _stream_ptr(stream))
+    check(st, "fa2_kv_append_paged")
 
 
 def _sink_pair(sink, dsink, Q, heads_dim):

@@ -429,9 +429,9 @@ int fa2_merge_states_backward(const void* const* O_parts, const float* const* L_
  * dividing H_q, n_splits outside 0..256, a (b, head) cache slab of 2 GiB or more (kv_capacity x head_dim x 2 bytes; the whole
  * cache may be larger) -> FA2_ERR_INVALID_SHAPE; FA2_ERR_UNSUPPORTED_HEAD_DIM; FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace
  * NULL, misaligned or too small while the resolved split count is > 1 -> FA2_ERR_WORKSPACE; M > 32 -> FA2_ERR_UNSUPPORTED.
- * NOT COVERED: [B][N][H][d] layouts, a cache-append kernel (a framework's scatter does it), M > 32, fp32 caches, sliding
- * windows, a backward, the ring.  (A cache held as a pool of pages with a block table: fa2_forward_decode_paged below; e4m3
- * caches: the _fp8kv calls below.) */
+ * NOT COVERED: [B][N][H][d] layouts, M > 32, fp32 caches, sliding windows, a backward, the ring.  (A cache held as a pool of
+ * pages with a block table: fa2_forward_decode_paged below; e4m3 caches: the _fp8kv calls below; WRITING the cache:
+ * fa2_kv_append, fa2_kvcache_mi355x.h.) */
 int fa2_decode_num_splits(int B, int H_kv, int kv_capacity, int head_dim);
 size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, int n_splits);
 int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
@@ -466,9 +466,9 @@ int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, 
  * INT_MAX - 33024 (the kernel's key arithmetic, up to len_b + (n_splits + 2) x 128, stays in int), n_splits outside 0..256, a grid B H_kv n_splits above INT_MAX -> FA2_ERR_INVALID_SHAPE; FA2_ERR_UNSUPPORTED_HEAD_DIM;
  * FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace NULL, misaligned or too small while the resolved split count is > 1 ->
  * FA2_ERR_WORKSPACE; M = (H_q / H_kv) q_len > 32 -> FA2_ERR_UNSUPPORTED.
- * NOT COVERED: token-major pages [n_pages][page_size][H_kv][d] (permute such a pool once, when it is allocated), page_size 16, a
- * cache-append kernel (a framework's scatter through the same table does it); and what fa2_forward_decode leaves out:
- * M > 32, sliding windows, a backward, the ring.  (e4m3 pages: fa2_forward_decode_paged_fp8kv below.) */
+ * NOT COVERED: token-major pages [n_pages][page_size][H_kv][d] (permute such a pool once, when it is allocated), page_size 16; and
+ * what fa2_forward_decode leaves out: M > 32, sliding windows, a backward, the ring.  (e4m3 pages:
+ * fa2_forward_decode_paged_fp8kv below; WRITING the pool through the same table: fa2_kv_append_paged, fa2_kvcache_mi355x.h.) */
 int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
                              const int* seqlens_k, const float* sink, void* O, float* L,
                              int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
@@ -494,8 +494,8 @@ int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_p
  * dtype is Q's and O's (FA2_DTYPE_BF16); kv_dtype is the caches' (FA2_DTYPE_FP8_E4M3).
  * STATUS CODES: the sibling's, in its order; either dtype other than the above -> FA2_ERR_UNSUPPORTED_DTYPE where the sibling
  * reports its dtype (after the head_dim); the contiguous slab limit is kv_capacity x head_dim x 1 byte below 2 GiB.
- * NOT COVERED: a quantising cache-append kernel (a framework's cast and scatter writes the cache), fp8 Q or an fp8 second
- * product, per-token or per-page scales, e5m2, and what the siblings leave out. */
+ * NOT COVERED: fp8 Q or an fp8 second product, per-token or per-page scales, e5m2, and what the siblings leave out.  (The
+ * quantising append that writes these caches with these descales: fa2_kv_append, fa2_kv_append_paged, fa2_kvcache_mi355x.h.) */
 int fa2_forward_decode_fp8kv(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
                              const float* k_descale, const float* v_descale, void* O, float* L,
                              int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
