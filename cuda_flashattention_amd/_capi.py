@@ -75,6 +75,9 @@ SIGNATURES = {
     "fa2_forward_decode_paged": (_i, [_vp] * 8 + [_i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
     "fa2_forward_decode_fp8kv": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
     "fa2_forward_decode_paged_fp8kv": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "fa2_decode_window_num_splits": (_i, [_i, _i, _i, _i, _i, _i]),
+    "fa2_forward_decode_window": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
+    "fa2_forward_decode_paged_window": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
     "fa2_backward_fused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fa2_backward_fused": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "fa2_backward_block": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i]),

@@ -870,6 +870,23 @@ int fa2_decode_num_splits(int B, int H_kv, int kv_capacity, int head_dim)
     return fa2::decode_num_splits(B, H_kv, kv_capacity);
 }
 
+// The window a call runs with: -1 (none: the plain kernels, the plain split rule) unless it can exclude a key of a full cache.
+static int decode_window(int window_left, int kv_capacity)
+{
+    return window_left < 0 || window_left >= kv_capacity - 1 ? -1 : window_left;
+}
+
+// With a window a sequence's splits share at most window_left + q_len + 127 keys (from rounddown(lo_b, 128) to len_b): the
+// rule above on that capacity.
+int fa2_decode_window_num_splits(int B, int H_kv, int q_len, int kv_capacity, int head_dim, int window_left)
+{
+    if (B <= 0 || H_kv <= 0 || kv_capacity <= 0) return 1;
+    const int w = decode_window(window_left, kv_capacity);
+    if (w < 0 || q_len <= 0) return fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
+    const long long span = (long long)w + q_len + (fa2::kDecodeKB - 1);
+    return fa2_decode_num_splits(B, H_kv, (int)std::min<long long>(kv_capacity, span), head_dim);
+}
+
 size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, int n_splits)
 {
     if (B <= 0 || H_q <= 0 || H_kv <= 0 || q_len <= 0 || kv_capacity <= 0 || head_dim <= 0) return 0;
@@ -880,17 +897,26 @@ size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_ca
 }
 
 // The caches of a decode call: bf16 like Q (kv_dtype = FA2_DTYPE_BF16, no descales), or -- the _fp8kv entry points -- OCP e4m3
-// with fp32 DEVICE descales per K/V head (nullptr = 1), which nothing here reads either.
-struct DecodeKv { int kv_dtype = FA2_DTYPE_BF16; const float* k_descale = nullptr; const float* v_descale = nullptr; };
+// with fp32 DEVICE descales per K/V head (nullptr = 1), which nothing here reads either.  The _window entry points take either
+// (any_kv; a descale beside a bf16 cache is refused where the dtype is) and a window_left; every other one has none (-1).
+struct DecodeKv {
+    int kv_dtype = FA2_DTYPE_BF16; const float* k_descale = nullptr; const float* v_descale = nullptr;
+    bool any_kv = false; int window_left = -1;
+};
 // Q's dtype, then the caches': both at the position of the dtype check, head_dim first
 static int decode_check_dtypes(int head_dim, int dtype, const DecodeKv& kv, bool fp8kv_entry)
 {
     if (const int st = check_bf16(head_dim, dtype)) return st;
+    if (kv.any_kv) {
+        if (kv.kv_dtype == FA2_DTYPE_FP8_E4M3) return FA2_OK;
+        return kv.kv_dtype == FA2_DTYPE_BF16 && !kv.k_descale && !kv.v_descale ? FA2_OK : FA2_ERR_UNSUPPORTED_DTYPE;
+    }
     return kv.kv_dtype == (fp8kv_entry ? FA2_DTYPE_FP8_E4M3 : FA2_DTYPE_BF16) ? FA2_OK : FA2_ERR_UNSUPPORTED_DTYPE;
 }
-static void decode_kv_args(fa2::DecodeArgs& a, const DecodeKv& kv)
+static void decode_kv_args(fa2::DecodeArgs& a, const DecodeKv& kv, int kv_capacity)
 {
     a.kv_fp8 = kv.kv_dtype == FA2_DTYPE_FP8_E4M3; a.k_descale = kv.k_descale; a.v_descale = kv.v_descale;
+    a.window_left = decode_window(kv.window_left, kv_capacity);
 }
 
 static int decode_contiguous(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
@@ -905,19 +931,21 @@ static int decode_contiguous(const void* Q, const void* K_cache, const void* V_c
     if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
     // one (b, head) slab, one buffer resource: 2 bytes per element, 1 in an e4m3 cache
     if ((long long)kv_capacity * head_dim * (fp8kv_entry ? 1 : 2) > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;
+    if (kv.window_left < -1) return FA2_ERR_INVALID_SHAPE;
     if ((st = decode_check_dtypes(head_dim, dtype, kv, fp8kv_entry))) return st;
-    if (n_splits == 0) n_splits = fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
+    if (n_splits == 0) n_splits = fa2_decode_window_num_splits(B, H_kv, q_len, kv_capacity, head_dim, kv.window_left);
     if ((long long)B * H_kv * n_splits > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;             // the grid
     const size_t need = fa2_decode_workspace_bytes(B, H_q, H_kv, q_len, kv_capacity, head_dim, n_splits);
     if (n_splits > 1 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return FA2_ERR_WORKSPACE;
     if ((long long)(H_q / H_kv) * q_len > fa2::kDecodeMaxRows) return FA2_ERR_UNSUPPORTED;
+    if (kv.window_left >= 0 && !causal) return FA2_ERR_UNSUPPORTED;      // (whatever the capacity: the window is a causal one)
     fa2::DecodeArgs a{};
     a.Q = Q; a.K = K_cache; a.V = V_cache; a.seqlens = seqlens_k; a.sink = sink; a.O = O; a.L = L;
     a.wsO = (float*)workspace;
     a.wsL = n_splits > 1 ? (float*)workspace + (size_t)n_splits * B * H_q * q_len * head_dim : nullptr;
     a.B = B; a.Hq = H_q; a.Hkv = H_kv; a.Nq = q_len; a.Ncap = kv_capacity; a.n_splits = n_splits;
     a.scale = softmax_scale; a.causal = causal ? 1 : 0;
-    decode_kv_args(a, kv);
+    decode_kv_args(a, kv, kv_capacity);
     return hip_status(fa2::launch_decode(a, head_dim, (hipStream_t)stream));
 }
 
@@ -956,14 +984,16 @@ static int decode_paged(const void* Q, const void* K_pages, const void* V_pages,
     // kDecodeKB over e4m3 pools, two tiles in flight)
     if ((long long)max_pages_per_seq * page_size > 0x7fffffffLL - (fa2::kDecodeMaxSplits + 2) * fa2::kDecodeKB) return FA2_ERR_INVALID_SHAPE;
     if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
+    if (kv.window_left < -1) return FA2_ERR_INVALID_SHAPE;
     const int kv_capacity = max_pages_per_seq * page_size;
-    const int resolved = n_splits ? n_splits : fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim);
+    const int resolved = n_splits ? n_splits : fa2_decode_window_num_splits(B, H_kv, q_len, kv_capacity, head_dim, kv.window_left);
     if ((long long)B * H_kv * resolved > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;             // the grid
     if ((st = decode_check_dtypes(head_dim, dtype, kv, fp8kv_entry))) return st;
     n_splits = resolved;
     const size_t need = fa2_decode_workspace_bytes(B, H_q, H_kv, q_len, kv_capacity, head_dim, n_splits);
     if (n_splits > 1 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return FA2_ERR_WORKSPACE;
     if ((long long)(H_q / H_kv) * q_len > fa2::kDecodeMaxRows) return FA2_ERR_UNSUPPORTED;
+    if (kv.window_left >= 0 && !causal) return FA2_ERR_UNSUPPORTED;
     fa2::DecodeArgs a{};
     a.Q = Q; a.K = K_pages; a.V = V_pages; a.seqlens = seqlens_k; a.sink = sink; a.O = O; a.L = L;
     a.wsO = (float*)workspace;
@@ -971,7 +1001,7 @@ static int decode_paged(const void* Q, const void* K_pages, const void* V_pages,
     a.B = B; a.Hq = H_q; a.Hkv = H_kv; a.Nq = q_len; a.Ncap = kv_capacity; a.n_splits = n_splits;
     a.scale = softmax_scale; a.causal = causal ? 1 : 0;
     a.block_table = block_table; a.n_pages = n_pages; a.page_size = page_size; a.max_pages = max_pages_per_seq;
-    decode_kv_args(a, kv);
+    decode_kv_args(a, kv, kv_capacity);
     return hip_status(fa2::launch_decode(a, head_dim, (hipStream_t)stream));
 }
 
@@ -995,6 +1025,30 @@ int fa2_forward_decode_paged_fp8kv(const void* Q, const void* K_pages, const voi
     return decode_paged(Q, K_pages, V_pages, block_table, seqlens_k, sink, O, L, B, H_q, H_kv, q_len, n_pages, page_size,
                         max_pages_per_seq, head_dim, softmax_scale, dtype, causal, n_splits, workspace, workspace_bytes, stream,
                         {kv_dtype, k_descale, v_descale}, true);
+}
+
+// fa2_forward_decode / _fp8kv and their paged forms with a sliding window: the siblings' checks in their order
+int fa2_forward_decode_window(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
+                              const float* k_descale, const float* v_descale, void* O, float* L,
+                              int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
+                              int dtype, int kv_dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream,
+                              int window_left)
+{
+    return decode_contiguous(Q, K_cache, V_cache, seqlens_k, sink, O, L, B, H_q, H_kv, q_len, kv_capacity, head_dim, softmax_scale, dtype,
+                             causal, n_splits, workspace, workspace_bytes, stream, {kv_dtype, k_descale, v_descale, true, window_left},
+                             kv_dtype == FA2_DTYPE_FP8_E4M3);
+}
+
+int fa2_forward_decode_paged_window(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
+                                    const int* seqlens_k, const float* sink, const float* k_descale, const float* v_descale,
+                                    void* O, float* L,
+                                    int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
+                                    int head_dim, float softmax_scale, int dtype, int kv_dtype, int causal, int n_splits,
+                                    void* workspace, size_t workspace_bytes, void* stream, int window_left)
+{
+    return decode_paged(Q, K_pages, V_pages, block_table, seqlens_k, sink, O, L, B, H_q, H_kv, q_len, n_pages, page_size,
+                        max_pages_per_seq, head_dim, softmax_scale, dtype, causal, n_splits, workspace, workspace_bytes, stream,
+                        {kv_dtype, k_descale, v_descale, true, window_left}, kv_dtype == FA2_DTYPE_FP8_E4M3);
 }
 
 int fa2_backward_status(const void* workspace, size_t workspace_bytes, int B, int H, int seq_len, int head_dim, int dtype,

@@ -24,6 +24,7 @@
 // No workgroup talks to another inside a launch: no atomics, no flags, no waiting; every sum has a fixed order.
 // PAGED (fa2_forward_decode_paged): the same body over a pool of pages and a block table, see decode_split_body.
 // FP8 CACHES (fa2_forward_decode_fp8kv, _paged_fp8kv): the same body over e4m3 K and V with a descale per K/V head, see there.
+// SLIDING WINDOW (fa2_forward_decode_window, _paged_window): the same body with a lower bound on the key range, see there.
 #include "fa2_common.h"
 #include "fa2_launch.h"
 
@@ -86,7 +87,17 @@ __device__ __forceinline__ bf16x8 e4m3x8_to_bf16(uint32_t w0, uint32_t w1)
 // one): K's on the way into the first product, V's on the way into the wave's LDS image, which -- like the transposed reads,
 // both products and the softmax -- stays the bf16 one.  k_descale joins the scalar the scores are multiplied by, v_descale
 // multiplies the fp32 row piece a split emits, before anything is rounded.
-template <int D, bool PAGED, int EB>
+//
+// WIN (fa2_forward_decode_window, _paged_window): a sliding window under the causal mask.  Row i sees keys [kmin_i, kmax_i),
+// kmin_i = max(0, pos_i - window_left), and no row of the sequence sees a key below lo = max(0, len - Nq - window_left).  The
+// splits share [base, len), base = rounddown(lo, kDecodeKB), instead of [0, len): they still start on multiples of kDecodeKB and
+// a wave's tiles are the tiles of the plain call.  What lies below lo may hold anything, table entries included, so
+//   a tile wholly below lo (at most three, in [base, base + kDecodeKB)) is treated like a tile past `end`: a resource of no rows
+//   (every tile is bound by a resource of its own here, contiguous caches too) and table index 0;
+//   the one tile that straddles lo is loaded whole -- its rows are in the slab, or in a page that holds a visible key -- and
+//   its V rows below lo are zeroed in VGPRs before they enter the LDS image (0 x NaN is NaN; K's scores are selected away);
+//   the two selects of a tile take kmin beside kmax.
+template <int D, bool PAGED, int EB, bool WIN = false>
 __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
 {
     static_assert(EB == 1 || EB == 2, "bf16 or e4m3 caches");
@@ -113,9 +124,13 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
     // the clamp is the contract: nothing below sees the stored value
     int len = a.Ncap;
     if (a.seqlens) len = min(max(__builtin_amdgcn_readfirstlane(a.seqlens[b]), 0), a.Ncap);
-    const int per = (len + a.n_splits - 1) / a.n_splits;
+    // WIN: lo without forming len - Nq - window_left (window_left may be INT_MAX, len < Nq happens); 0 otherwise
+    int lo = 0;
+    if constexpr (WIN) lo = len - a.Nq > a.window_left ? len - a.Nq - a.window_left : 0;
+    const int base0 = WIN ? lo / kDecodeKB * kDecodeKB : 0;
+    const int per = (len - base0 + a.n_splits - 1) / a.n_splits;
     const int chunk = (per + kDecodeKB - 1) / kDecodeKB * kDecodeKB;
-    const int begin = split * chunk;                      // <= len + n_splits kDecodeKB: no overflow
+    const int begin = base0 + split * chunk;              // <= len + n_splits kDecodeKB: no overflow
     const int end = min(begin + chunk, len);
 
     const size_t R = (size_t)a.B * a.Hq * a.Nq;           // rows of O, L and of one split's partials
@@ -156,6 +171,11 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
     int kmax = end;
     if (a.causal) kmax = min(end, r % a.Nq + len - a.Nq + 1);
     if (r >= M) kmax = 0;
+    int kmin = 0;      // WIN: keys [kmin, kmax); a row with pos < 0 has no key whatever kmin is
+    if constexpr (WIN) {
+        const int pos = r % a.Nq + len - a.Nq;
+        kmin = pos > a.window_left ? pos - a.window_left : 0;
+    }
 
     const size_t slab = PAGED ? (size_t)hkv * a.page_size * D : ((size_t)b * a.Hkv + hkv) * (size_t)a.Ncap * D;
     const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.K + slab), 0, end * ROWB, 0x00020000);
@@ -178,13 +198,29 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
     const auto fetch_entry = [&](int base) {
         // (the outer readfirstlane costs nothing on a scalar; it keeps the compiler from merging this load with the one before
         // the loop into a single load at the top of the iteration that uses it, which would undo the prefetch)
-        ent = __builtin_amdgcn_readfirstlane(table[__builtin_amdgcn_readfirstlane(base < end ? pg_i : 0)]);
+        if constexpr (WIN)      // a tile wholly below lo reads entry 0 too: the entries of pages below lo are never read
+            ent = __builtin_amdgcn_readfirstlane(table[__builtin_amdgcn_readfirstlane(base < end && base + kDecodeTile > lo ? pg_i : 0)]);
+        else
+            ent = __builtin_amdgcn_readfirstlane(table[__builtin_amdgcn_readfirstlane(base < end ? pg_i : 0)]);
         ent_o = pg_o;
         pg_i += pg_di;
         pg_o += pg_do;
         if (pg_o >= a.page_size) { pg_o -= a.page_size; ++pg_i; }
     };
     const auto load_tile = [&](int base, int sl) {      // rows past `end` read as zeros (and cost no traffic)
+        if constexpr (WIN) {      // a resource per tile, of no rows where the tile has no key at or above lo
+            const bool live = base < end && base + kDecodeTile > lo;
+            const int page = PAGED && live ? min(max(ent, 0), a.n_pages - 1) : 0;      // the clamp is the contract
+            const int rows = __builtin_amdgcn_readfirstlane(live ? min(kDecodeTile, end - base) : 0);
+            const size_t at = slab + (PAGED ? (size_t)page * a.Hkv * a.page_size + ent_o : (size_t)(live ? base : 0)) * D;
+            const auto kp = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.K + at), 0, rows * ROWB, 0x00020000);
+            const auto vp = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.V + at), 0, rows * ROWB, 0x00020000);
+#pragma unroll
+            for (int t = 0; t < KL; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(kp, koff + 32 * t, 0, 0);
+#pragma unroll
+            for (int n = 0; n < NV; ++n) vf[sl][n] = __builtin_amdgcn_raw_buffer_load_b128(vp, voff + n * RPI * ROWB, 0, 0);
+            return;
+        }
         if constexpr (PAGED) {
             const int page = base < end ? min(max(ent, 0), a.n_pages - 1) : 0;      // the clamp is the contract
             // (readfirstlane: the compiler clamps with v_med3_i32, and a resource with a VGPR word is loaded in a waterfall loop)
@@ -322,6 +358,31 @@ __global__ void __launch_bounds__(256) fa2_decode_f8_paged_split_kernel(DecodeAr
     decode_split_body<D, true, 1>(a);
 }
 
+// fa2_forward_decode_window / _paged_window: the same body with the window (WIN), over both element sizes
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_win_split_kernel(DecodeArgs a)
+{
+    decode_split_body<D, false, 2, true>(a);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_win_paged_split_kernel(DecodeArgs a)
+{
+    decode_split_body<D, true, 2, true>(a);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_win_f8_split_kernel(DecodeArgs a)
+{
+    decode_split_body<D, false, 1, true>(a);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) fa2_decode_win_f8_paged_split_kernel(DecodeArgs a)
+{
+    decode_split_body<D, true, 1, true>(a);
+}
+
 // rows x d / 4 lanes, a lane owns four columns of one row: partials in, ascending s, fp32; the sink; one rounding
 template <int D>
 __global__ void __launch_bounds__(256) fa2_decode_combine_kernel(DecodeArgs a)
@@ -391,7 +452,13 @@ static hipError_t decode_launch(const DecodeArgs& a, hipStream_t stream)
     static_assert(kDecWaves * kDecodeTile * 2 * D <= kDecWaves * 32 * (D + 4) * 4, "the V images fit under the O images");
     const unsigned grid = (unsigned)a.B * a.Hkv * a.n_splits;
     hipError_t e;
-    if (a.kv_fp8)
+    if (a.window_left >= 0 && a.kv_fp8)
+        e = a.block_table ? launch_lds<fa2_decode_win_f8_paged_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a)
+                          : launch_lds<fa2_decode_win_f8_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
+    else if (a.window_left >= 0)
+        e = a.block_table ? launch_lds<fa2_decode_win_paged_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a)
+                          : launch_lds<fa2_decode_win_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
+    else if (a.kv_fp8)
         e = a.block_table ? launch_lds<fa2_decode_f8_paged_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a)
                           : launch_lds<fa2_decode_f8_split_kernel<D>>(dim3(grid), dim3(256), lds, stream, a);
     else
@@ -407,6 +474,7 @@ hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream)
 {
     if (a.n_splits < 1 || a.n_splits > kDecodeMaxSplits || a.Hq % a.Hkv || a.Hq / a.Hkv * a.Nq > kDecodeMaxRows)
         return hipErrorInvalidValue;
+    if (a.window_left >= 0 && !a.causal) return hipErrorInvalidValue;      // the window is a causal one
     if ((long long)a.B * a.Hkv * a.n_splits > 0x7fffffffLL) return hipErrorInvalidValue;
     if (a.block_table && (a.n_pages < 1 || a.max_pages < 1 || a.page_size < kDecodeTile || a.page_size % kDecodeTile ||
                           (long long)a.max_pages * a.page_size != a.Ncap))

@@ -2,6 +2,13 @@
 // over a wave's tiles stands: the tile's first key is DEC_KB and its K / V fragments wait in slot DEC_SL (kf[DEC_SL], vf[DEC_SL]),
 // which -- behind the first product -- takes the loads of the tile PF rounds ahead.  Included text and not a lambda: called through
 // a lambda, the bf16 kernels' loop came out of the compiler re-scheduled (tools/asm_identity.py against the parent).
+        if constexpr (WIN) {      // the tile that straddles lo: its V rows below lo may hold anything, and 0 x NaN is NaN
+            if (DEC_KB < lo) {
+#pragma unroll
+                for (int n = 0; n < NV; ++n)
+                    if (DEC_KB + n * RPI + lane / CPR < lo) vf[DEC_SL][n] = u32x4{0u, 0u, 0u, 0u};
+            }
+        }
 #pragma unroll
         for (int n = 0; n < NV; ++n) {
             if constexpr (EB == 2) {
@@ -31,7 +38,10 @@
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             s[e] *= sc;
-            mx = DEC_KB + acc_row(e, h) < kmax ? fmaxf(mx, s[e]) : mx;
+            if constexpr (WIN)
+                mx = DEC_KB + acc_row(e, h) < kmax && DEC_KB + acc_row(e, h) >= kmin ? fmaxf(mx, s[e]) : mx;
+            else
+                mx = DEC_KB + acc_row(e, h) < kmax ? fmaxf(mx, s[e]) : mx;
         }
         mx = half_max(mx);
         const float m_new = fmaxf(m, mx);
@@ -42,7 +52,11 @@
         bf16x8 p[2];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const float pe = DEC_KB + acc_row(e, h) < kmax ? __builtin_amdgcn_exp2f(s[e] - m0) : 0.0f;
+            float pe;
+            if constexpr (WIN)
+                pe = DEC_KB + acc_row(e, h) < kmax && DEC_KB + acc_row(e, h) >= kmin ? __builtin_amdgcn_exp2f(s[e] - m0) : 0.0f;
+            else
+                pe = DEC_KB + acc_row(e, h) < kmax ? __builtin_amdgcn_exp2f(s[e] - m0) : 0.0f;
             ps += pe;
             p[e >> 3][e & 7] = (__bf16)pe;
         }

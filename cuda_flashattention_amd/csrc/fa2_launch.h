@@ -94,6 +94,10 @@ struct DecodeArgs {
     // x / descale[h] (DEVICE, fp32 [Hkv]; nullptr = 1: scores softmax_scale k_descale[h] (Q . K8), O = v_descale[h] P V8).  All zero: bf16.
     const float* k_descale; const float* v_descale;
     int kv_fp8;
+    // fa2_forward_decode_window / _paged_window: window_left >= 0, query i of sequence b sees keys [pos_i - window_left, pos_i],
+    // pos_i = i + len_b - Nq (causal only); rows and table entries below lo_b = max(0, len_b - Nq - window_left) are never read.
+    // Negative: no window, the kernels above (every other entry point sets -1).
+    int window_left;
 };
 int decode_num_splits(int B, int H_kv, int kv_capacity);      // pure host arithmetic: fa2_decode_num_splits
 hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream);      // d = 64 | 128; 1 <= G Nq <= 32; block_table: paged; kv_fp8: e4m3

@@ -394,18 +394,50 @@ def _seqlens_arg(seqlens_k, Q, B):
     return seqlens_k
 
 
-def decode_num_splits(B, H_kv, kv_capacity, head_dim):
-    """The split count n_splits=0 stands for (fa2_decode_num_splits): host arithmetic on the capacity, never on a length."""
-    return _capi.lib().fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim)
+def _window_arg(window_left, causal):
+    """window_left of a decode call: None (no window) or an int >= 0, the number of keys before its own position a query sees;
+    the window is a causal one."""
+    if window_left is None:
+        return None
+    if isinstance(window_left, bool) or not isinstance(window_left, int):
+        raise ValueError(f"window_left: {window_left!r}, expected an int >= 0 (the keys before its own position a query sees; a "
+                         "model's sliding_window = 128 is window_left = 127), or None for no window")
+    if window_left < 0:
+        raise ValueError(f"window_left: {window_left}, expected an int >= 0, or None for no window")
+    if not causal:
+        raise ValueError(f"window_left: {window_left} with causal=False; the window is a causal one (keys pos - window_left .. pos)")
+    return min(window_left, 0x7fffffff)
 
 
-def decode_workspace(B, H, H_kv, N_q, kv_capacity, d, n_splits=0, device="cuda"):
-    """Scratch for flash_attention_2_decode (the splits' fp32 partials): allocate once, pass as workspace= (graph capture)."""
-    return torch.empty(_capi.lib().fa2_decode_workspace_bytes(B, H, H_kv, N_q, kv_capacity, d, n_splits), dtype=torch.uint8, device=device)
+def decode_num_splits(B, H_kv, kv_capacity, head_dim, *, q_len=1, window_left=None):
+    """The split count n_splits=0 stands for (fa2_decode_num_splits): host arithmetic on the capacity, never on a length.
+    window_left (with the call's q_len): the count of a windowed call (fa2_decode_window_num_splits), the same rule on
+    min(kv_capacity, window_left + q_len + 127) keys."""
+    w = _window_arg(window_left, True)
+    if w is None:
+        return _capi.lib().fa2_decode_num_splits(B, H_kv, kv_capacity, head_dim)
+    return _capi.lib().fa2_decode_window_num_splits(B, H_kv, q_len, kv_capacity, head_dim, w)
+
+
+def _decode_need(lib, B, H, Hkv, Nq, Ncap, d, n_splits, window_left):
+    """Workspace bytes of a decode call: n_splits = 0 resolved by the window's rule where there is one."""
+    if window_left is not None and n_splits == 0:
+        n_splits = lib.fa2_decode_window_num_splits(B, Hkv, Nq, Ncap, d, window_left)
+    return lib.fa2_decode_workspace_bytes(B, H, Hkv, Nq, Ncap, d, n_splits)
+
+
+def decode_workspace(B, H, H_kv, N_q, kv_capacity, d, n_splits=0, device="cuda", *, q_len=1, window_left=None):
+    """Scratch for flash_attention_2_decode (the splits' fp32 partials): allocate once, pass as workspace= (graph capture).
+    window_left: the windowed call's (n_splits=0 is then decode_num_splits(..., q_len=N_q, window_left=window_left); the
+    partials have N_q rows, q_len is accepted for symmetry with decode_num_splits and must equal N_q where both are given)."""
+    w = _window_arg(window_left, True)
+    if w is not None and q_len not in (1, N_q):
+        raise ValueError(f"q_len: {q_len} beside N_q = {N_q}")
+    return torch.empty(_decode_need(_capi.lib(), B, H, H_kv, N_q, kv_capacity, d, n_splits, w), dtype=torch.uint8, device=device)
 
 
 def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=None, causal=True, sink=None, n_splits=0,
-                             O=None, L=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+                             O=None, L=None, workspace=None, stream=None, k_descale=None, v_descale=None, window_left=None):
     """O, L = attention of a few new tokens per sequence against a preallocated KV cache (fa2_forward_decode): Q [B, H, N_q, d],
     K_cache and V_cache [B, H_kv, N_cap, d] (H_kv dividing H, (H / H_kv) N_q <= 32), bf16, d = 64 | 128.  INFERENCE ONLY: there is
     no autograd and no backward.
@@ -426,10 +458,19 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     WRITING THE CACHE: there is no append kernel inside this call; kv_cache_append is that call, bf16 or e4m3, and takes this
     call's seqlens_k tensor: bump the lengths in place, append, decode.  It stores (x / descale).clamp(-448, 448)
     .to(torch.float8_e4m3fn) byte for byte and saturates; a framework cast in its place needs that clamp --
-    torch's cast does not saturate, an overflow becomes a NaN code."""
+    torch's cast does not saturate, an overflow becomes a NaN code.
+    SLIDING WINDOW (fa2_forward_decode_window): window_left = None (no window, this call as it always was) or an int >= 0, the
+    number of keys BEFORE its own position a query sees: with pos_i = i + len_b - N_q key j is visible iff pos_i - window_left <= j
+    <= pos_i.  A model's sliding_window = 128 is window_left = 127; flash-attn's window_size = (left, 0) is window_left = left.
+    It needs causal=True.  Only keys from rounddown(max(0, len_b - N_q - window_left), 128) on are split over the workgroups and
+    read; cache rows BEFORE THE WINDOW (below len_b - N_q - window_left) may hold anything, NaN included.  n_splits=0 is then
+    decode_num_splits(B, H_kv, N_cap, d, q_len=N_q, window_left=window_left) and the workspace decode_workspace(..., q_len=N_q,
+    window_left=window_left).  bf16 and e4m3 caches, sinks, GQA and graph capture as above; a window >= N_cap - 1 is this call
+    without one, bit for bit."""
     B, H, Hkv, Nq, Ncap, d, fp8 = _decode_shapes(Q, K_cache, V_cache)
     if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
+    window_left = _window_arg(window_left, causal)
     if seqlens_k is not None:
         _seqlens_arg(seqlens_k, Q, B)
     if sink is not None:
@@ -446,14 +487,18 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
     L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
     lib = _capi.lib()
-    need = lib.fa2_decode_workspace_bytes(B, H, Hkv, Nq, Ncap, d, n_splits)
+    need = _decode_need(lib, B, H, Hkv, Nq, Ncap, d, n_splits, window_left)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
     if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
         raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (decode_workspace)")
     head = (Q.data_ptr(), K_cache.data_ptr(), V_cache.data_ptr(), _ptr(seqlens_k), _ptr(sink))
     tail = (1 if causal else 0, n_splits, _ptr(workspace), 0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
-    if fp8:
+    if window_left is not None:
+        st = lib.fa2_forward_decode_window(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d,
+                                           scale, FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, *tail, window_left)
+        check(st, "fa2_forward_decode_window")
+    elif fp8:
         st = lib.fa2_forward_decode_fp8kv(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d,
                                           scale, FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3, *tail)
         check(st, "fa2_forward_decode_fp8kv")
@@ -516,7 +561,8 @@ def _decode_paged_shapes(Q, K_pages, V_pages):
 
 
 def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=None, softmax_scale=None, causal=True, sink=None,
-                                   n_splits=0, O=None, L=None, workspace=None, stream=None, k_descale=None, v_descale=None):
+                                   n_splits=0, O=None, L=None, workspace=None, stream=None, k_descale=None, v_descale=None,
+                                   window_left=None):
     """O, L = flash_attention_2_decode over a KV cache held as a pool of pages (fa2_forward_decode_paged): Q [B, H, N_q, d], K_pages
     and V_pages [n_pages, H_kv, page_size, d] (head-major; H_kv dividing H, (H / H_kv) N_q <= 32, page_size a multiple of 32, not
     necessarily a power of two), bf16, d = 64 | 128.  A token-major pool [n_pages, page_size, H_kv, d] needs one permute when it is
@@ -534,10 +580,15 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     [H_kv] DEVICE tensors or None = 1; a pool stores x as x / descale[h_kv]), exactly as flash_attention_2_decode describes them:
     read on the device, never by the host; unused pages may hold any byte.
     WRITING THE POOL: there is no append kernel inside this call; kv_cache_append_paged is that call, through the same table and
-    seqlens_k tensors: bump the lengths (and assign a new page's entry) in place, append, decode."""
+    seqlens_k tensors: bump the lengths (and assign a new page's entry) in place, append, decode.
+    SLIDING WINDOW (fa2_forward_decode_paged_window): window_left as flash_attention_2_decode describes it (None: no window).
+    BEFORE THE WINDOW: with lo_b = max(0, len_b - N_q - window_left), every table entry of a page that lies wholly below lo_b may
+    hold anything (stale, -1, out of range) and so may those pages: they are never read, prefetches included, so a server may
+    free the pages behind the window and hand them to other sequences."""
     B, H, Hkv, Nq, n_pages, page_size, d, fp8 = _decode_paged_shapes(Q, K_pages, V_pages)
     if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
+    window_left = _window_arg(window_left, causal)
     for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):      # (they belong to the pools' dtype: checked with it)
         if t is not None:
             _descale_arg(t, Q, Hkv, name, fp8, "K_pages")
@@ -558,7 +609,7 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
     L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
     lib = _capi.lib()
-    need = lib.fa2_decode_workspace_bytes(B, H, Hkv, Nq, kv_capacity, d, n_splits)
+    need = _decode_need(lib, B, H, Hkv, Nq, kv_capacity, d, n_splits, window_left)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
     if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
@@ -566,7 +617,11 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     head = (Q.data_ptr(), K_pages.data_ptr(), V_pages.data_ptr(), block_table.data_ptr(), _ptr(seqlens_k), _ptr(sink))
     dims = (B, H, Hkv, Nq, n_pages, page_size, max_pages, d, scale)
     tail = (1 if causal else 0, n_splits, _ptr(workspace), 0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
-    if fp8:
+    if window_left is not None:
+        st = lib.fa2_forward_decode_paged_window(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), *dims,
+                                                 FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, *tail, window_left)
+        check(st, "fa2_forward_decode_paged_window")
+    elif fp8:
         st = lib.fa2_forward_decode_paged_fp8kv(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), *dims,
                                                 FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3, *tail)
         check(st, "fa2_forward_decode_paged_fp8kv")

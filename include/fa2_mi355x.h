@@ -429,9 +429,9 @@ int fa2_merge_states_backward(const void* const* O_parts, const float* const* L_
  * dividing H_q, n_splits outside 0..256, a (b, head) cache slab of 2 GiB or more (kv_capacity x head_dim x 2 bytes; the whole
  * cache may be larger) -> FA2_ERR_INVALID_SHAPE; FA2_ERR_UNSUPPORTED_HEAD_DIM; FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace
  * NULL, misaligned or too small while the resolved split count is > 1 -> FA2_ERR_WORKSPACE; M > 32 -> FA2_ERR_UNSUPPORTED.
- * NOT COVERED: [B][N][H][d] layouts, M > 32, fp32 caches, sliding windows, a backward, the ring.  (A cache held as a pool of
- * pages with a block table: fa2_forward_decode_paged below; e4m3 caches: the _fp8kv calls below; WRITING the cache:
- * fa2_kv_append, fa2_kvcache_mi355x.h.) */
+ * NOT COVERED: [B][N][H][d] layouts, M > 32, fp32 caches, a backward, the ring.  (A cache held as a pool of
+ * pages with a block table: fa2_forward_decode_paged below; e4m3 caches: the _fp8kv calls below; a sliding window:
+ * fa2_forward_decode_window below; WRITING the cache: fa2_kv_append, fa2_kvcache_mi355x.h.) */
 int fa2_decode_num_splits(int B, int H_kv, int kv_capacity, int head_dim);
 size_t fa2_decode_workspace_bytes(int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, int n_splits);
 int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
@@ -467,8 +467,8 @@ int fa2_forward_decode(const void* Q, const void* K_cache, const void* V_cache, 
  * FA2_ERR_UNSUPPORTED_DTYPE (bf16 only); workspace NULL, misaligned or too small while the resolved split count is > 1 ->
  * FA2_ERR_WORKSPACE; M = (H_q / H_kv) q_len > 32 -> FA2_ERR_UNSUPPORTED.
  * NOT COVERED: token-major pages [n_pages][page_size][H_kv][d] (permute such a pool once, when it is allocated), page_size 16; and
- * what fa2_forward_decode leaves out: M > 32, sliding windows, a backward, the ring.  (e4m3 pages:
- * fa2_forward_decode_paged_fp8kv below; WRITING the pool through the same table: fa2_kv_append_paged, fa2_kvcache_mi355x.h.) */
+ * what fa2_forward_decode leaves out: M > 32, a backward, the ring.  (e4m3 pages:
+ * fa2_forward_decode_paged_fp8kv below; a sliding window: fa2_forward_decode_paged_window below; WRITING the pool through the same table: fa2_kv_append_paged, fa2_kvcache_mi355x.h.) */
 int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
                              const int* seqlens_k, const float* sink, void* O, float* L,
                              int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
@@ -494,8 +494,8 @@ int fa2_forward_decode_paged(const void* Q, const void* K_pages, const void* V_p
  * dtype is Q's and O's (FA2_DTYPE_BF16); kv_dtype is the caches' (FA2_DTYPE_FP8_E4M3).
  * STATUS CODES: the sibling's, in its order; either dtype other than the above -> FA2_ERR_UNSUPPORTED_DTYPE where the sibling
  * reports its dtype (after the head_dim); the contiguous slab limit is kv_capacity x head_dim x 1 byte below 2 GiB.
- * NOT COVERED: fp8 Q or an fp8 second product, per-token or per-page scales, e5m2, and what the siblings leave out.  (The
- * quantising append that writes these caches with these descales: fa2_kv_append, fa2_kv_append_paged, fa2_kvcache_mi355x.h.) */
+ * NOT COVERED: fp8 Q or an fp8 second product, per-token or per-page scales, e5m2, and what the siblings leave out.  (A sliding
+ * window over e4m3 caches: the _window calls below.  The quantising append that writes these caches with these descales: fa2_kv_append, fa2_kv_append_paged, fa2_kvcache_mi355x.h.) */
 int fa2_forward_decode_fp8kv(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
                              const float* k_descale, const float* v_descale, void* O, float* L,
                              int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
@@ -506,6 +506,51 @@ int fa2_forward_decode_paged_fp8kv(const void* Q, const void* K_pages, const voi
                                    int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
                                    int head_dim, float softmax_scale, int dtype, int kv_dtype, int causal, int n_splits,
                                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Decode with a sliding window: the four calls above (bf16 or e4m3 caches, contiguous or paged) for a layer that sees only
+ * the last keys, the way GPT-OSS (128 keys and a sink), Mistral and Gemma layers do.  The same kernels' body with a lower bound
+ * on the key range; the combine, the sink (applied after the combine), GQA (M <= 32), determinism and "nothing allocated, nothing
+ * synchronised" are the siblings'.
+ * WINDOW.  window_left is the number of keys BEFORE a query's own position that it sees.  With pos_i = i + len_b - q_len (the
+ * bottom-right position used everywhere here) key j is visible to query i iff pos_i - window_left <= j <= pos_i.  A model's
+ * sliding_window = 128 "including itself" is window_left = 127; flash-attn's window_size = (left, 0) is window_left = left.
+ * window_left = -1: no window.  The window is a causal one: window_left >= 0 with causal == 0 returns FA2_ERR_UNSUPPORTED.  A row
+ * with pos_i < 0 has no key, as in the siblings: O = 0, L = -inf or the sink.  window_left may be INT_MAX.
+ * KEY RANGE.  lo_b = max(0, len_b - q_len - window_left) is the lowest key any row of sequence b may see.  The splits share
+ * [base_b, len_b), base_b = rounddown(lo_b, 128): chunk = roundup(ceil((len_b - base_b) / n_splits), 128) and split s covers
+ * [base_b + s chunk, min(base_b + (s + 1) chunk, len_b)), computed on the device from len_b.  Splits start on multiples of 128 and
+ * the 32-key tiles are those of the plain call, so with q_len == 1 and lo_b a multiple of 128 the result is bit for bit the plain
+ * call's on the cache rows from lo_b on, at equal n_splits.  The host reads neither lengths nor table nor descales: one captured
+ * graph serves every step as the lengths grow and the window slides.
+ * BEFORE THE WINDOW (the "past the length" contract, mirrored).  Cache rows below lo_b may hold anything, NaNs and the e4m3 NaN
+ * codes included.  Paged: every table entry of a page that lies wholly below lo_b may hold anything (stale, -1, out of range): it
+ * is never read, prefetches included, which is what lets a server free the pages behind the window.  Tiles wholly below lo_b are
+ * not loaded; the one 32-key tile that straddles lo_b lies in a page that holds a visible key, and its rows below lo_b never
+ * reach a product as data (K's scores are selected away, V's rows are zeroed in registers).  Rows in [lo_b, len_b) are real data.
+ * n_splits: 1..256, or 0 = fa2_decode_window_num_splits(B, H_kv, q_len, kv_capacity, head_dim, window_left), a pure host function:
+ * fa2_decode_num_splits on min(kv_capacity, window_left + q_len + 127), the most keys a sequence's splits can share.  Pass its
+ * result to fa2_decode_workspace_bytes as n_splits.
+ * ROUTING.  window_left == -1 or window_left >= kv_capacity - 1 excludes no key of any length: the call IS the sibling's, its
+ * kernels and its default split count, bit for bit (fa2_decode_window_num_splits then equals fa2_decode_num_splits).
+ * dtype is Q's and O's (FA2_DTYPE_BF16); kv_dtype is the caches', FA2_DTYPE_BF16 or FA2_DTYPE_FP8_E4M3.  k_descale, v_descale: as
+ * in the _fp8kv calls, NULL = 1; they belong to e4m3 caches, and a non-NULL one beside a bf16 cache is refused.
+ * STATUS CODES: the siblings', in their order; window_left < -1 -> FA2_ERR_INVALID_SHAPE, the last of the shape checks; a kv_dtype
+ * other than the two, or a descale beside a bf16 cache -> FA2_ERR_UNSUPPORTED_DTYPE where the siblings report their dtype;
+ * window_left >= 0 with causal == 0 -> FA2_ERR_UNSUPPORTED, after M > 32.
+ * NOT COVERED: non-causal and right-sided windows, a window in the training forward or backward, a ring-buffer (modulo) cache
+ * layout, a window per sequence or per head, and what the siblings leave out (M > 32, a backward, the ring). */
+int fa2_decode_window_num_splits(int B, int H_kv, int q_len, int kv_capacity, int head_dim, int window_left);
+int fa2_forward_decode_window(const void* Q, const void* K_cache, const void* V_cache, const int* seqlens_k, const float* sink,
+                              const float* k_descale, const float* v_descale, void* O, float* L,
+                              int B, int H_q, int H_kv, int q_len, int kv_capacity, int head_dim, float softmax_scale,
+                              int dtype, int kv_dtype, int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream,
+                              int window_left);
+int fa2_forward_decode_paged_window(const void* Q, const void* K_pages, const void* V_pages, const int* block_table,
+                                    const int* seqlens_k, const float* sink, const float* k_descale, const float* v_descale,
+                                    void* O, float* L,
+                                    int B, int H_q, int H_kv, int q_len, int n_pages, int page_size, int max_pages_per_seq,
+                                    int head_dim, float softmax_scale, int dtype, int kv_dtype, int causal, int n_splits,
+                                    void* workspace, size_t workspace_bytes, void* stream, int window_left);
 
 /* fa2_backward restricted to some of its kernels -- bit 0: D = rowsum(dO o O) and the row constants into the
  * workspace, bit 1: the dQ kernel, bit 2: the dK/dV kernel, bit 3: the single five-product kernel and its output
