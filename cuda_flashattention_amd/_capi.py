@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("FA2_LIB_PATH") or os.path.join(_HERE, "lib", "libfa2_
 RING_LIB_PATH = os.path.join(_HERE, "lib", "libfa2_ring_mi355x.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mi355x.h")
 KVCACHE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_kvcache_mi355x.h")
+ROPE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -100,6 +101,12 @@ KVCACHE_SIGNATURES = {
     "fa2_kv_append_paged": (_i, [_vp] * 8 + [_i] * 7 + [_ll] * 3 + [_i, _i, _vp]),
 }
 
+# include/fa2_rope_mi355x.h, the same library: the append with rotary embedding in front and the step's queries beside it.
+ROPE_SIGNATURES = {
+    "fa2_rope_kv_append": (_i, [_vp] * 11 + [_i] * 9 + [_ll] * 6 + [_i, _i, _vp]),
+    "fa2_rope_kv_append_paged": (_i, [_vp] * 12 + [_i] * 11 + [_ll] * 6 + [_i, _i, _vp]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -124,7 +131,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `make -C cuda_flashattention_amd/csrc` "
                 "(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

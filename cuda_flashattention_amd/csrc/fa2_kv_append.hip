@@ -12,11 +12,10 @@
 // ADDRESSES.  A destination is formed by fa2_kv_append_addr.h and nothing else: a token is written iff its row passes
 // 0 <= pos < capacity (and, paged, its table entry lies inside the pool); every other token is skipped, source load included.
 // No loop bound comes from device memory.  Source rows are read only for t < n_new, through the caller's three strides.
-// E4M3.  x -> float (exact), a correctly rounded fp32 division by the head's descale, v_med3_f32 against +-448 -- which returns
-// a bound for a NaN operand, hence the select that keeps the NaN --, then v_cvt_pk_fp8_f32 (round to nearest even; NaN -> 0x7F
-// or 0xFF).  +-inf is clamped to +-448; -0.0 / descale = -0.0 keeps its sign through all three.
+// E4M3.  The quantiser is fa2_kv_quantise.h's, shared with fa2_rope_append.hip.
 #include "fa2_common.h"
 #include "fa2_kv_append_addr.h"
+#include "fa2_kv_quantise.h"
 #include "fa2_kvcache_mi355x.h"
 #include "fa2_launch.h"
 
@@ -28,7 +27,6 @@ namespace {
 
 constexpr int kKvPasses = 2;           // rows of a lane per unit: both passes' loads are issued before the first store
 constexpr int kKvMaxBlocks = 2048;     // 256 CUs x 8 workgroups of 4 waves: a memory-bound grid is capped and strides
-constexpr float kE4m3Max = 448.0f;
 // what a wave reads once per unit, at a wave-uniform address: the constant address space makes these scalar loads
 typedef __attribute__((address_space(4))) int kv_const_int;
 typedef __attribute__((address_space(4))) float kv_const_float;
@@ -40,30 +38,6 @@ struct KvAppendArgs {
     int n_pages, page_size, max_pages;           // paged only
     long long sb, sh, st;                        // the source's element strides: batch, head, token
 };
-
-__device__ __forceinline__ float kv_e4m3_operand(float x, float descale)
-{
-    const float y = x / descale;
-    const float c = __builtin_amdgcn_fmed3f(y, -kE4m3Max, kE4m3Max);
-    return y != y ? y : c;
-}
-
-// Eight bf16 (four words, ascending) -> eight e4m3 codes (two words, ascending bytes).
-__device__ __forceinline__ u32x2 kv_quantise8(const u32x4& w, float descale)
-{
-    float f[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = kv_e4m3_operand(__uint_as_float(w[i] << 16), descale);
-        f[2 * i + 1] = kv_e4m3_operand(__uint_as_float(w[i] & 0xffff0000u), descale);
-    }
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-    return u32x2{(uint32_t)lo, (uint32_t)hi};
-}
 
 template <int D, bool FP8, bool PAGED>
 __global__ __launch_bounds__(256) void fa2_kv_append_kernel(const KvAppendArgs a)

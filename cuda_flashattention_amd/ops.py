@@ -762,6 +762,177 @@ def kv_cache_append_paged(K_new, V_new, K_pages, V_pages, block_table, seqlens_k
     check(st, "fa2_kv_append_paged")
 
 
+def _rope_q_arg(Q, K_new):
+    """(H_q, (stride_b, stride_h, stride_t)) of the step's queries beside K_new: a bf16 [B, H_q, n_new, d] VIEW with strides of its
+    own, under the rules of K_new (_kv_new_arg); None is a K/V-only call (H_q = 0)."""
+    if Q is None:
+        return 0, (0, 0, 0)
+    B, _, n_new, d = K_new.shape
+    how = ("pass a [B, H_q, n_new, d] view, e.g. x.permute(0, 2, 1, 3) of a token-major [B, n_new, H_q, d] tensor or the Q slice of the "
+           "fused QKV output")
+    if not isinstance(Q, torch.Tensor) or Q.dim() != 4:
+        raise ValueError(f"Q: expected a 4-d tensor [B, H_q, n_new, d], got {tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}; {how}")
+    if Q.dtype != torch.bfloat16:
+        raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16")
+    if Q.shape[0] != B or Q.shape[1] < 1 or Q.shape[2] != n_new or Q.shape[3] != d:
+        raise ValueError(f"Q: shape {tuple(Q.shape)} does not match K_new {tuple(K_new.shape)}: expected [{B}, H_q, {n_new}, {d}] with H_q >= 1")
+    if Q.stride(-1) != 1:
+        raise ValueError(f"Q: stride {tuple(Q.stride())}, the last dimension must be contiguous (stride(-1) == 1); {how}")
+    strides = tuple(Q.stride()[:3])
+    if any(s < 0 or s % 8 for s in strides):
+        raise ValueError(f"Q: strides {strides} (batch, head, token) must be non-negative multiples of 8 elements: a lane loads 16 bytes")
+    if Q.storage_offset() % 8:
+        raise ValueError(f"Q: storage offset {Q.storage_offset()} elements is not 16-byte aligned (a multiple of 8): a lane loads 16 bytes")
+    return Q.shape[1], strides
+
+
+def _rope_tables_arg(cos, sin, d, capacity):
+    """(rot_dim, n_positions) of the cos/sin tables: fp32 [n_positions, rot_dim / 2], one shape for both, rot_dim a multiple of 16 in
+    [16, d], a row for every row of the cache.  Device and contiguity are checked last (_rope_devices)."""
+    for n, t in (("cos", cos), ("sin", sin)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{n}: expected a 2-d tensor [n_positions, rot_dim / 2], got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{n}: dtype {t.dtype}, expected torch.float32 (the rotation is fp32 arithmetic on fp32 tables)")
+    n_positions, half = cos.shape
+    if tuple(sin.shape) != tuple(cos.shape):
+        raise ValueError(f"sin: shape {tuple(sin.shape)} does not match cos {tuple(cos.shape)}")
+    if half < 8 or half % 8 or 2 * half > d:
+        raise ValueError(f"cos: shape {tuple(cos.shape)} is a rot_dim of {2 * half}, expected a multiple of 16 in [16, {d}] (head_dim)")
+    if n_positions < capacity:
+        raise ValueError(f"cos: {n_positions} positions for a cache of {capacity} rows: a token's position is its cache row, so the "
+                         "tables need a row for every row of the cache")
+    return 2 * half, n_positions
+
+
+def _rope_devices(Q, Q_out, cos, sin, K_new, B, Hq, n_new, d):
+    """Last: the tables contiguous on the source's device, Q there too, Q_out (allocated here when not given: the only
+    allocation) dense [B, H_q, n_new, d] there."""
+    if Q is not None and not Q.is_cuda:
+        raise ValueError("Q must be a device tensor")
+    if Q is not None and Q.device != K_new.device:
+        raise ValueError(f"Q is on {Q.device}, expected {K_new.device}")
+    for n, t in (("cos", cos), ("sin", sin)):
+        if not t.is_cuda:
+            raise ValueError(f"{n} must be a device tensor: the kernel reads the tables on the device when it runs")
+        if t.device != K_new.device:
+            raise ValueError(f"{n} is on {t.device}, expected {K_new.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous (got stride {tuple(t.stride())}; call .contiguous())")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{n}: not 16-byte aligned (storage offset {t.storage_offset()} elements): a lane loads 16 bytes")
+    if Q is None:
+        if Q_out is not None:
+            raise ValueError("Q_out: given without Q (a K/V-only call has neither)")
+        return None
+    if Q_out is None:
+        return torch.empty(B, Hq, n_new, d, dtype=torch.bfloat16, device=K_new.device)
+    return _like(Q_out, "Q_out", K_new, (B, Hq, n_new, d), torch.bfloat16)
+
+
+def _rope_interleaved(interleaved):
+    if not isinstance(interleaved, bool):
+        raise ValueError(f"interleaved: {interleaved!r}, expected a bool (False: rotate-half pairs (i, i + rot_dim/2); True: pairs (2i, 2i+1))")
+    return 1 if interleaved else 0
+
+
+def rope_kv_cache_append(Q, K_new, V_new, K_cache, V_cache, cos, sin, seqlens_k, *, interleaved=False, k_descale=None,
+                         v_descale=None, Q_out=None, stream=None):
+    """kv_cache_append with rotary position embedding (RoPE) in front, and the step's queries beside it (fa2_rope_kv_append): ONE
+    launch rotates the n_new newest tokens' K and writes it into K_cache, copies their V into V_cache -- both exactly as
+    kv_cache_append stores them, bf16 or torch.float8_e4m3fn with descales -- and writes the rotated queries; returns Q_out,
+    bf16 [B, H_q, n_new, d] contiguous, what flash_attention_2_decode takes.  A step is: seqlens_k += n_new (in place),
+    rope_kv_cache_append, flash_attention_2_decode(Q_out, ...); one captured graph serves every step.
+    Q, K_new, V_new: bf16 [B, H, n_new, d] VIEWS (d = 64 | 128) as kv_cache_append describes them; Q has strides of its own, so the
+    three slices of a fused QKV projection output are passed as they are -- no .contiguous() copy.  Q=None is a K/V-only call
+    (returns None).
+    POSITION: token t of sequence b has position seqlens_k[b] - n_new + t -- its cache row, the position the decode's mask gives
+    query t, and the row of the tables.  cos, sin: fp32 [n_positions, rot_dim / 2] contiguous DEVICE tensors the caller builds (any
+    frequency scaling is the caller's), n_positions >= the cache's capacity, rot_dim a multiple of 16 in [16, d]; elements past
+    rot_dim pass through (partial rotary).  interleaved=False: rotate-half (NeoX, HF) pairs (i, i + rot_dim/2); True: GPT-J pairs
+    (2i, 2i + 1); both use table column i.
+    ARITHMETIC: byte for byte (x1.float()*c - x2.float()*s).bfloat16() and (x2.float()*c + x1.float()*s).bfloat16(), every product
+    and sum one fp32 rounding (no fused multiply-add).  HF's all-bf16 arithmetic is a different, less exact expression and is not
+    reproduced.  An e4m3 cache stores the quantised ROUNDED bf16 value, so the call is byte for byte {rotate in torch to bf16,
+    kv_cache_append}.
+    Q_out: EVERY row is written: rotated where 0 <= position < capacity, +0.0 throughout elsewhere (such a token's K and V are
+    dropped, as kv_cache_append drops them).  Allocated when not given -- the ONLY allocation; pass one for graph capture.  The host
+    never reads seqlens_k, a descale or a table.  Q_out overlapping an input is undefined."""
+    B, Hkv, n_new, d, strides = _kv_new_arg(K_new, V_new)
+    Hq, q_strides = _rope_q_arg(Q, K_new)
+    for n, t in (("K_cache", K_cache), ("V_cache", V_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a 4-d tensor [B, H_kv, N_cap, d], got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    Ncap = K_cache.shape[2]
+    shape = (B, Hkv, Ncap, d)
+    if tuple(K_cache.shape) != shape or Ncap < 1:
+        raise ValueError(f"K_cache: shape {tuple(K_cache.shape)} does not match K_new {tuple(K_new.shape)}: expected [{B}, {Hkv}, N_cap, {d}]")
+    if tuple(V_cache.shape) != shape:
+        raise ValueError(f"V_cache: shape {tuple(V_cache.shape)} does not match K_cache {tuple(K_cache.shape)}")
+    fp8 = _kv_append_dtypes(K_new, K_cache, V_cache, "K_cache", "V_cache", Hkv, k_descale, v_descale)
+    rot_dim, n_positions = _rope_tables_arg(cos, sin, d, Ncap)
+    flag = _rope_interleaved(interleaved)
+    if seqlens_k is None:
+        raise ValueError("seqlens_k is required: token t of sequence b has position seqlens_k[b] - n_new + t (the lengths AFTER the "
+                         "append, the decode call's tensor)")
+    _seqlens_arg(seqlens_k, K_new, B)
+    _kv_append_devices(K_new, V_new, K_cache, V_cache, "K_cache", "V_cache", shape)
+    Q_out = _rope_devices(Q, Q_out, cos, sin, K_new, B, Hq, n_new, d)
+    st = _capi.lib().fa2_rope_kv_append(_ptr(Q), _ptr(Q_out), K_new.data_ptr(), V_new.data_ptr(), K_cache.data_ptr(), V_cache.data_ptr(),
+                                        cos.data_ptr(), sin.data_ptr(), seqlens_k.data_ptr(), _ptr(k_descale), _ptr(v_descale),
+                                        B, Hq, Hkv, n_new, Ncap, d, rot_dim, n_positions, flag, *q_strides, *strides, FA2_DTYPE_BF16,
+                                        FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, _stream_ptr(stream))
+    check(st, "fa2_rope_kv_append")
+    return Q_out
+
+
+def rope_kv_cache_append_paged(Q, K_new, V_new, K_pages, V_pages, block_table, cos, sin, seqlens_k, *, interleaved=False,
+                               k_descale=None, v_descale=None, Q_out=None, stream=None):
+    """rope_kv_cache_append into a pool of pages (fa2_rope_kv_append_paged), the pool flash_attention_2_decode_paged reads: K_pages,
+    V_pages [n_pages, H_kv, page_size, d] and block_table int32 [B, max_pages] exactly as kv_cache_append_paged takes them, the
+    capacity max_pages * page_size (the tables need that many rows).  A token whose table entry lies outside [0, n_pages) has its
+    K and V DROPPED, as there; its Q_out row is still the rotated query: Q depends on the position alone.  PAGES WRITTEN BY ONE
+    CALL MUST BELONG TO ONE SEQUENCE EACH.  Everything else is rope_kv_cache_append's: the views, the tables, the pair forms, the
+    arithmetic, seqlens_k (required, the lengths after the append), one launch, returns Q_out."""
+    B, Hkv, n_new, d, strides = _kv_new_arg(K_new, V_new)
+    Hq, q_strides = _rope_q_arg(Q, K_new)
+    for n, t in (("K_pages", K_pages), ("V_pages", V_pages)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a 4-d tensor [n_pages, H_kv, page_size, d], got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    n_pages, hk, page_size, dk = K_pages.shape
+    if hk != Hkv or dk != d or n_pages < 1 or page_size < 1:
+        raise ValueError(f"K_pages: shape {tuple(K_pages.shape)} does not match K_new {tuple(K_new.shape)}: expected "
+                         f"[n_pages, {Hkv}, page_size, {d}] with n_pages, page_size >= 1")
+    if page_size % DECODE_PAGE_GRAIN:
+        raise ValueError(f"K_pages: page_size {page_size} is not a multiple of {DECODE_PAGE_GRAIN} (the decode kernel's key tile; a page "
+                         "of 16 keys is not taken)")
+    shape = (n_pages, Hkv, page_size, d)
+    if tuple(V_pages.shape) != shape:
+        raise ValueError(f"V_pages: shape {tuple(V_pages.shape)} does not match K_pages {tuple(K_pages.shape)}")
+    fp8 = _kv_append_dtypes(K_new, K_pages, V_pages, "K_pages", "V_pages", Hkv, k_descale, v_descale)
+    _rope_tables_arg(cos, sin, d, 0)
+    flag = _rope_interleaved(interleaved)
+    if seqlens_k is None:
+        raise ValueError("seqlens_k is required: token t of sequence b has position seqlens_k[b] - n_new + t (the lengths AFTER the "
+                         "append, the decode call's tensor)")
+    max_pages = _block_table_arg(block_table, K_new, B)
+    if max_pages * page_size > 0x7fffffff - (DECODE_MAX_SPLITS + 2) * 128:
+        raise ValueError(f"block_table: {max_pages} pages of {page_size} keys is a capacity of {max_pages * page_size} keys, above what an int indexes")
+    rot_dim, n_positions = _rope_tables_arg(cos, sin, d, max_pages * page_size)
+    _seqlens_arg(seqlens_k, K_new, B)
+    _kv_append_devices(K_new, V_new, K_pages, V_pages, "K_pages", "V_pages", shape)
+    Q_out = _rope_devices(Q, Q_out, cos, sin, K_new, B, Hq, n_new, d)
+    st = _capi.lib().fa2_rope_kv_append_paged(_ptr(Q), _ptr(Q_out), K_new.data_ptr(), V_new.data_ptr(), K_pages.data_ptr(),
+                                              V_pages.data_ptr(), block_table.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                                              seqlens_k.data_ptr(), _ptr(k_descale), _ptr(v_descale), B, Hq, Hkv, n_new, n_pages, page_size,
+                                              max_pages, d, rot_dim, n_positions, flag, *q_strides, *strides, FA2_DTYPE_BF16,
+                                              FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, _stream_ptr(stream))
+    check(st, "fa2_rope_kv_append_paged")
+    return Q_out
+
+
 def _sink_pair(sink, dsink, Q, heads_dim):
     """sink= and dsink= of a backward, each checked beside Q (_sink_arg); dsink without sink is refused."""
     if sink is not None:
