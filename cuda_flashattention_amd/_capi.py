@@ -15,6 +15,7 @@ RING_LIB_PATH = os.path.join(_HERE, "lib", "libfa2_ring_mi355x.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mi355x.h")
 KVCACHE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_kvcache_mi355x.h")
 ROPE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_mi355x.h")
+EXTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -107,6 +108,15 @@ ROPE_SIGNATURES = {
     "fa2_rope_kv_append_paged": (_i, [_vp] * 12 + [_i] * 11 + [_ll] * 6 + [_i, _i, _vp]),
 }
 
+# include/fa2_extend_mi355x.h, the same library: the decode calls for any number of query rows per K/V head (the arguments of
+# fa2_forward_decode_window / _paged_window in their order).
+EXTEND_SIGNATURES = {
+    "fa2_extend_num_splits": (_i, [_i] * 7),
+    "fa2_extend_workspace_bytes": (_sz, [_i] * 8),
+    "fa2_forward_extend": SIGNATURES["fa2_forward_decode_window"],
+    "fa2_forward_extend_paged": SIGNATURES["fa2_forward_decode_paged_window"],
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -131,7 +141,8 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `make -C cuda_flashattention_amd/csrc` "
                 "(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items())
+                                  + list(EXTEND_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -25,6 +25,7 @@
 // PAGED (fa2_forward_decode_paged): the same body over a pool of pages and a block table, see decode_split_body.
 // FP8 CACHES (fa2_forward_decode_fp8kv, _paged_fp8kv): the same body over e4m3 K and V with a descale per K/V head, see there.
 // SLIDING WINDOW (fa2_forward_decode_window, _paged_window): the same body with a lower bound on the key range, see there.
+// EXTEND (fa2_forward_extend, _paged; include/fa2_extend_mi355x.h): more than 32 rows per K/V head, see extend_split_body.
 #include "fa2_common.h"
 #include "fa2_launch.h"
 
@@ -331,6 +332,282 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs& a)
     }
 }
 
+// EXTEND (fa2_forward_extend, include/fa2_extend_mi355x.h): decode_split_body with RT = 2 row tiles per wave, for any M.  The data path,
+// the loads, the page and window handling are decode_split_body's, statement for statement (a body of its own and not a parameter
+// of that one: with the parameter the ten kernels above came out of the compiler re-scheduled, tools/asm_identity.py).  A workgroup
+// is (sequence, K/V head, block of 32 RT rows, split), block j owning rows 64 j ..+64 of the group's [G][Nq] slab (row rho: head
+// rho / Nq, token rho % Nq; rows >= M are padding).  Every K fragment and every V image a wave loads feeds the products of both
+// row tiles, so the K/V head is streamed once per 64 rows.  The split ranges are decode_split_body's (shared by the blocks of a
+// sequence); a block clips its own: it stops at the largest kmax of its rows and, under a window, starts at the 32-key tile
+// that holds the smallest kmin of its rows, each wave at the first of ITS tiles (w, w + 4, ... counted from the split's first)
+// at or behind that one.  The clip only drops tiles whose every probability would be selected to 0, a row's arithmetic does
+// not depend on the tile it sits in, and the waves' states meet row tile by row tile through the same LDS image: a row's
+// result is bit for bit the one decode_split_body computes for it.
+template <int D, bool PAGED, int EB, bool WIN>
+__device__ __forceinline__ void extend_split_body(const DecodeArgs& a)
+{
+    constexpr int RT = kExtendRows / 32;      // row tiles per wave
+    static_assert(EB == 1 || EB == 2, "bf16 or e4m3 caches");
+    using kv_t = std::conditional_t<EB == 2, __bf16, uint8_t>;      // one cache element: offsets below count elements
+    constexpr int ROWB = EB * D;              // bytes per cache row
+    constexpr int KS = D / 16;                // k-steps of S^T = K Q^T
+    constexpr int KL = ROWB / 32;             // K loads per tile: 16 bytes of the lane's row each
+    constexpr int CPR = ROWB / 16;            // 16-byte chunks per row
+    constexpr int RPI = 64 / CPR;             // V rows one wave-wide load covers
+    constexpr int NV = kDecodeTile / RPI;     // V loads per tile
+    constexpr int DB = D / 32;                // 32-column tiles of O^T
+    constexpr int VIMG = kDecodeTile * 2 * D; // a wave's V image (bf16 whatever the cache holds)
+    constexpr int OP = D + 4;                 // floats per row of a wave's O image (the pad spreads 32 rows over the banks)
+    constexpr int C4 = D / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // kDecWaves x max(VIMG, 32 OP 4) | m, l: kDecWaves x 32 x 2 floats
+    float* const s_ml = reinterpret_cast<float*>(smem + kDecWaves * 32 * OP * 4);
+
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int G = a.Hq / a.Hkv, M = G * a.Nq;
+    const int bid = blockIdx.x;
+    const int RB = (M + 32 * RT - 1) / (32 * RT);      // row blocks of a group
+    const int split = bid % a.n_splits, hkv = (bid / (a.n_splits * RB)) % a.Hkv, b = bid / (a.n_splits * RB * a.Hkv);
+    const int rb0 = bid / a.n_splits % RB * (32 * RT);      // the block's first row
+    const int Mb = min(M - rb0, 32 * RT);              // its live rows
+
+    // the clamp is the contract: nothing below sees the stored value
+    int len = a.Ncap;
+    if (a.seqlens) len = min(max(__builtin_amdgcn_readfirstlane(a.seqlens[b]), 0), a.Ncap);
+    // WIN: lo without forming len - Nq - window_left (window_left may be INT_MAX, len < Nq happens); 0 otherwise
+    int lo = 0;
+    if constexpr (WIN) lo = len - a.Nq > a.window_left ? len - a.Nq - a.window_left : 0;
+    const int base0 = WIN ? lo / kDecodeKB * kDecodeKB : 0;
+    const int per = (len - base0 + a.n_splits - 1) / a.n_splits;
+    const int chunk = (per + kDecodeKB - 1) / kDecodeKB * kDecodeKB;
+    const int begin = base0 + split * chunk;              // <= len + n_splits kDecodeKB: no overflow
+    int end = min(begin + chunk, len);
+    int cstart = 0;      // WIN: the first tile with a key visible to a row of the block
+    {      // the block's clip: its rows' tokens are [tlo, thi], all of them where it crosses a head
+        const int rl = rb0 + Mb - 1;
+        const bool wrap = rb0 / a.Nq != rl / a.Nq;
+        const int tlo = wrap ? 0 : rb0 % a.Nq, thi = wrap ? a.Nq - 1 : rl % a.Nq;
+        if (a.causal) end = min(end, thi + len - a.Nq + 1);
+        if constexpr (WIN) {
+            const int pos = tlo + len - a.Nq;
+            cstart = (pos > a.window_left ? pos - a.window_left : 0) / kDecodeTile * kDecodeTile;
+        }
+    }
+
+    const size_t R = (size_t)a.B * a.Hq * a.Nq;           // rows of O, L and of one split's partials
+    const size_t row0 = ((size_t)b * a.Hq + (size_t)hkv * G) * a.Nq;      // the group's first row
+
+    // what a finished row piece becomes: a partial, or the result
+    const float vd = EB == 1 && a.v_descale ? a.v_descale[hkv] : 1.0f;
+    const auto emit = [&](int row, int c4, f32x4 o, float Lrow) {
+        const size_t gr = row0 + row;
+        if constexpr (EB == 1) o *= vd;
+        if (a.n_splits > 1) {
+            *reinterpret_cast<f32x4*>(a.wsO + ((size_t)split * R + gr) * D + 4 * c4) = o;
+            if (c4 == 0) a.wsL[(size_t)split * R + gr] = Lrow;
+        } else {
+            float w = 1.0f;
+            if (a.sink) w = decode_sink(a.sink[hkv * G + row / a.Nq], Lrow);
+            *reinterpret_cast<bf16x4*>((__bf16*)a.O + gr * D + 4 * c4) = to_bf16x4(o, w);
+            if (c4 == 0) a.L[gr] = Lrow;
+        }
+    };
+
+    if (begin >= end || (WIN && cstart >= end)) {      // an empty split (a short sequence's later splits, len = 0): no key
+        for (int idx = tid; idx < Mb * C4; idx += 256) emit(rb0 + idx / C4, idx % C4, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, -INFINITY);
+        return;
+    }
+
+    // Q^T fragments: lane (row r, half h) holds Q[r][16 t + 8 h ..+8] for k-step t (EB = 1: Q[r][32 (t / 2) + 16 h + 8 (t % 2) ..+8])
+    // (row tile i of the wave: the lane's row is rho = rb0 + 32 i + r)
+    bf16x8 q[RT][KS];
+    int kmax[RT], kmin[RT];
+#pragma unroll
+    for (int i = 0; i < RT; ++i) {
+        const int rho = rb0 + 32 * i + r;
+        const __bf16* Qg = (const __bf16*)a.Q + (row0 + (rho < M ? rho : 0)) * D + (EB == 2 ? 8 : 16) * h;
+#pragma unroll
+        for (int t = 0; t < KS; ++t) {
+            q[i][t] = *reinterpret_cast<const bf16x8*>(Qg + (EB == 2 ? 16 * t : 32 * (t / 2) + 8 * (t % 2)));
+            if (rho >= M) q[i][t] = bf16x8{};
+        }
+        // keys [0, kmax) are visible to this lane's row (bottom-right causal: j <= i + len - N_q), none to a padding row
+        kmax[i] = end;
+        if (a.causal) kmax[i] = min(end, rho % a.Nq + len - a.Nq + 1);
+        if (rho >= M) kmax[i] = 0;
+        kmin[i] = 0;      // WIN: keys [kmin, kmax); a row with pos < 0 has no key whatever kmin is
+        if constexpr (WIN) {
+            const int pos = rho % a.Nq + len - a.Nq;
+            kmin[i] = pos > a.window_left ? pos - a.window_left : 0;
+        }
+    }
+
+    const size_t slab = PAGED ? (size_t)hkv * a.page_size * D : ((size_t)b * a.Hkv + hkv) * (size_t)a.Ncap * D;
+    const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.K + slab), 0, end * ROWB, 0x00020000);
+    const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.V + slab), 0, end * ROWB, 0x00020000);
+    const uint32_t koff = (uint32_t)r * ROWB + 16 * h;                       // + 32 t per load
+    const uint32_t voff = (uint32_t)(lane / CPR) * ROWB + 16 * (lane % CPR);   // + RPI rows per load
+    // Tiles a wave keeps in flight ahead of its arithmetic.  An e4m3 tile is half the bytes (and its fragments half the registers)
+    // of a bf16 one, and with one workgroup per CU one of them in flight left the loop waiting on memory: two.
+    constexpr int PF = EB == 1 ? 2 : 1;
+    u32x4 kf[PF][KL], vf[PF][NV];
+    // PAGED.  (pg_i, pg_o): page index and row within the page of the tile whose table entry is fetched next; a wave's tiles are
+    // kDecodeKB keys apart, that is (pg_di, pg_do) further, carried without a division.  (ent, ent_o): the fetched entry and row
+    // of the tile that is LOADED next.  A tile with a key indexes the table below max_pages (kb < len <= max_pages page_size);
+    // one without reads entry 0 of its sequence, which the clamp and its resource of no rows keep from being used.
+    // The table does not change while the kernel runs: read through the constant address space, a uniform index is a scalar load
+    // whatever else the loop stores (the compiler gives up proving that for a plain global load this deep in a loop, and a
+    // vector load would leave the resource in VGPRs).
+    int pg_i = 0, pg_o = 0, pg_di = 0, pg_do = 0, ent = 0, ent_o = 0;
+    const dec_const_int* const table = (const dec_const_int*)a.block_table + (size_t)b * a.max_pages;
+    const auto fetch_entry = [&](int base) {
+        // (the outer readfirstlane costs nothing on a scalar; it keeps the compiler from merging this load with the one before
+        // the loop into a single load at the top of the iteration that uses it, which would undo the prefetch)
+        if constexpr (WIN)      // a tile wholly below lo reads entry 0 too: the entries of pages below lo are never read
+            ent = __builtin_amdgcn_readfirstlane(table[__builtin_amdgcn_readfirstlane(base < end && base + kDecodeTile > lo ? pg_i : 0)]);
+        else
+            ent = __builtin_amdgcn_readfirstlane(table[__builtin_amdgcn_readfirstlane(base < end ? pg_i : 0)]);
+        ent_o = pg_o;
+        pg_i += pg_di;
+        pg_o += pg_do;
+        if (pg_o >= a.page_size) { pg_o -= a.page_size; ++pg_i; }
+    };
+    const auto load_tile = [&](int base, int sl) {      // rows past `end` read as zeros (and cost no traffic)
+        if constexpr (WIN) {      // a resource per tile, of no rows where the tile has no key at or above lo
+            const bool live = base < end && base + kDecodeTile > lo;
+            const int page = PAGED && live ? min(max(ent, 0), a.n_pages - 1) : 0;      // the clamp is the contract
+            const int rows = __builtin_amdgcn_readfirstlane(live ? min(kDecodeTile, end - base) : 0);
+            const size_t at = slab + (PAGED ? (size_t)page * a.Hkv * a.page_size + ent_o : (size_t)(live ? base : 0)) * D;
+            const auto kp = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.K + at), 0, rows * ROWB, 0x00020000);
+            const auto vp = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.V + at), 0, rows * ROWB, 0x00020000);
+#pragma unroll
+            for (int t = 0; t < KL; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(kp, koff + 32 * t, 0, 0);
+#pragma unroll
+            for (int n = 0; n < NV; ++n) vf[sl][n] = __builtin_amdgcn_raw_buffer_load_b128(vp, voff + n * RPI * ROWB, 0, 0);
+            return;
+        }
+        if constexpr (PAGED) {
+            const int page = base < end ? min(max(ent, 0), a.n_pages - 1) : 0;      // the clamp is the contract
+            // (readfirstlane: the compiler clamps with v_med3_i32, and a resource with a VGPR word is loaded in a waterfall loop)
+            const int rows = __builtin_amdgcn_readfirstlane(max(min(kDecodeTile, end - base), 0));
+            const size_t at = slab + ((size_t)page * a.Hkv * a.page_size + ent_o) * D;      // 64-bit: a pool may exceed 4 GiB
+            const auto kp = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.K + at), 0, rows * ROWB, 0x00020000);
+            const auto vp = __builtin_amdgcn_make_buffer_rsrc((void*)((const kv_t*)a.V + at), 0, rows * ROWB, 0x00020000);
+#pragma unroll
+            for (int t = 0; t < KL; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(kp, koff + 32 * t, 0, 0);
+#pragma unroll
+            for (int n = 0; n < NV; ++n) vf[sl][n] = __builtin_amdgcn_raw_buffer_load_b128(vp, voff + n * RPI * ROWB, 0, 0);
+            return;
+        }
+        const uint32_t b0 = (uint32_t)base * ROWB;
+#pragma unroll
+        for (int t = 0; t < KL; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, b0 + koff + 32 * t, 0, 0);
+#pragma unroll
+        for (int n = 0; n < NV; ++n) vf[sl][n] = __builtin_amdgcn_raw_buffer_load_b128(v_rsrc, b0 + voff + n * RPI * ROWB, 0, 0);
+    };
+
+    char* const vimg = smem + wave * VIMG;
+    // ds_read_b64_tr_b16: lane 4 qq + p of a 16-lane group supplies row qq, columns 4 p ..+4 of a 4 x 16 block; the group's lanes
+    // get the block's columns.  Group g serves half g >> 1 and columns 16 (g & 1) ..+16 of a 32-column tile of V.
+    const int gi = lane & 15, qq = gi >> 2, pp = gi & 3, c0 = 16 * ((lane >> 4) & 1);
+
+    float m[RT], l[RT];                         // running maximum (log2 units) and this lane half's part of the running sum
+    f32x16 o[RT][DB];
+#pragma unroll
+    for (int i = 0; i < RT; ++i) {
+        m[i] = -INFINITY;
+        l[i] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < DB; ++c)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[i][c][e] = 0.0f;
+    }
+    float sc = a.scale * kLog2e;
+    if constexpr (EB == 1) sc *= a.k_descale ? a.k_descale[hkv] : 1.0f;
+
+    int kb = begin + kDecodeTile * wave;
+    if constexpr (WIN)      // the wave's first tile at or behind the block's first
+        if (cstart > kb) kb += (cstart - kb + kDecodeKB - 1) / kDecodeKB * kDecodeKB;
+    if constexpr (PAGED) {      // the two divisions of a workgroup
+        pg_i = kb / a.page_size;
+        pg_o = kb - pg_i * a.page_size;
+        pg_di = kDecodeKB / a.page_size;
+        pg_do = kDecodeKB - pg_di * a.page_size;
+        fetch_entry(kb);
+    }
+    load_tile(kb, 0);
+    if constexpr (PAGED) fetch_entry(kb + kDecodeKB);
+    if constexpr (PF == 1) {
+        for (; kb < end; kb += kDecodeKB) {
+#define DEC_KB kb
+#define DEC_SL 0
+#include "fa2_extend_tile.inc"
+        }
+    } else {      // two tiles in flight: slot 0 holds the wave's even tiles, slot 1 the odd ones
+        load_tile(kb + kDecodeKB, 1);
+        if constexpr (PAGED) fetch_entry(kb + 2 * kDecodeKB);
+        for (; kb < end; kb += 2 * kDecodeKB) {
+            {
+#define DEC_KB kb
+#define DEC_SL 0
+#include "fa2_extend_tile.inc"
+            }
+            if (kb + kDecodeKB < end) {
+#define DEC_KB (kb + kDecodeKB)
+#define DEC_SL 1
+#include "fa2_extend_tile.inc"
+            }
+        }
+    }
+
+    // the four waves' states meet, row tile by row tile: common maximum, then O and l at that maximum, summed in wave order
+#pragma unroll
+    for (int i = 0; i < RT; ++i) {
+        if (i) __syncthreads();      // the tile before is out of the images
+        l[i] = half_sum(l[i]);
+        if (h == 0) { s_ml[(wave * 32 + r) * 2] = m[i]; s_ml[(wave * 32 + r) * 2 + 1] = l[i]; }
+        __syncthreads();      // every wave is done with its V image: the O images below overlap them
+        {
+            float ms = -INFINITY;
+#pragma unroll
+            for (int w = 0; w < kDecWaves; ++w) ms = fmaxf(ms, s_ml[(w * 32 + r) * 2]);
+            const float f = __builtin_amdgcn_exp2f(m[i] - (ms == -INFINITY ? 0.0f : ms));
+            float* const oimg = reinterpret_cast<float*>(smem) + (wave * 32 + r) * OP + 4 * h;
+#pragma unroll
+            for (int c = 0; c < DB; ++c)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {      // registers 4 g4 ..+4: columns 32 c + 8 g4 + 4 h ..+4 of O's row r
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = o[i][c][4 * g4 + e] * f;
+                    *reinterpret_cast<f32x4*>(oimg + 32 * c + 8 * g4) = v;
+                }
+        }
+        __syncthreads();
+        const int Mi = min(max(Mb - 32 * i, 0), 32);      // the tile's live rows
+        for (int idx = tid; idx < Mi * C4; idx += 256) {
+            const int row = idx / C4, c4 = idx % C4;
+            float ms = -INFINITY;
+#pragma unroll
+            for (int w = 0; w < kDecWaves; ++w) ms = fmaxf(ms, s_ml[(w * 32 + row) * 2]);
+            const float ms0 = ms == -INFINITY ? 0.0f : ms;
+            float lt = 0.0f;
+            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int w = 0; w < kDecWaves; ++w) {
+                lt += s_ml[(w * 32 + row) * 2 + 1] * __builtin_amdgcn_exp2f(s_ml[(w * 32 + row) * 2] - ms0);
+                acc += *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem) + (w * 32 + row) * OP + 4 * c4);
+            }
+            const bool has = lt > 0.0f;             // a select: a row without a visible key in this split
+            const float inv = 1.0f / lt;
+            f32x4 out;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[e] = has ? acc[e] * inv : 0.0f;
+            emit(rb0 + 32 * i + row, c4, out, has ? (ms + __builtin_amdgcn_logf(lt)) * kDecLn2 : -INFINITY);      // (v_log_f32 is log2)
+        }
+    }
+}
+
 }  // namespace
 
 template <int D>
@@ -381,6 +658,13 @@ template <int D>
 __global__ void __launch_bounds__(256) fa2_decode_win_f8_paged_split_kernel(DecodeArgs a)
 {
     decode_split_body<D, true, 1, true>(a);
+}
+
+// fa2_forward_extend / _paged (include/fa2_extend_mi355x.h): extend_split_body, any M
+template <int D, bool PAGED, int EB, bool WIN>
+__global__ void __launch_bounds__(256) fa2_extend_split_kernel(DecodeArgs a)
+{
+    extend_split_body<D, PAGED, EB, WIN>(a);
 }
 
 // rows x d / 4 lanes, a lane owns four columns of one row: partials in, ascending s, fp32; the sink; one rounding
@@ -468,6 +752,43 @@ static hipError_t decode_launch(const DecodeArgs& a, hipStream_t stream)
     const size_t threads = (size_t)a.B * a.Hq * a.Nq * (D / 4);
     hipLaunchKernelGGL(fa2_decode_combine_kernel<D>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
     return hipGetLastError();
+}
+
+template <int D, bool PAGED, int EB>
+static hipError_t extend_launch(const DecodeArgs& a, hipStream_t stream)
+{
+    constexpr int lds = kDecWaves * 32 * (D + 4) * 4 + kDecWaves * 32 * 2 * 4;      // decode_launch's: the row tiles take turns
+    const int M = a.Hq / a.Hkv * a.Nq;
+    const unsigned grid = (unsigned)a.B * a.Hkv * ((M + kExtendRows - 1) / kExtendRows) * a.n_splits;
+    const hipError_t e = a.window_left >= 0 ? launch_lds<fa2_extend_split_kernel<D, PAGED, EB, true>>(dim3(grid), dim3(256), lds, stream, a)
+                                            : launch_lds<fa2_extend_split_kernel<D, PAGED, EB, false>>(dim3(grid), dim3(256), lds, stream, a);
+    if (e != hipSuccess || a.n_splits == 1) return e;
+    const size_t threads = (size_t)a.B * a.Hq * a.Nq * (D / 4);
+    hipLaunchKernelGGL(fa2_decode_combine_kernel<D>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <int D>
+static hipError_t extend_launch(const DecodeArgs& a, hipStream_t stream)
+{
+    if (a.kv_fp8) return a.block_table ? extend_launch<D, true, 1>(a, stream) : extend_launch<D, false, 1>(a, stream);
+    return a.block_table ? extend_launch<D, true, 2>(a, stream) : extend_launch<D, false, 2>(a, stream);
+}
+
+hipError_t launch_extend(const DecodeArgs& a, int d, hipStream_t stream)
+{
+    if (a.n_splits < 1 || a.n_splits > kDecodeMaxSplits || a.Hkv < 1 || a.Hq % a.Hkv || a.Nq < 1) return hipErrorInvalidValue;
+    if (a.window_left >= 0 && !a.causal) return hipErrorInvalidValue;      // the window is a causal one
+    const long long M = (long long)(a.Hq / a.Hkv) * a.Nq, rows = (long long)a.B * a.Hq * a.Nq;
+    if (M > 0x7fffffffLL - kExtendRows || rows > 0x7fffffffLL) return hipErrorInvalidValue;
+    if ((long long)a.B * a.Hkv * ((M + kExtendRows - 1) / kExtendRows) > 0x7fffffffLL / a.n_splits) return hipErrorInvalidValue;
+    if (rows * (d / 4) > 0x7fffffffLL * 256) return hipErrorInvalidValue;      // the combine's grid
+    if (a.block_table && (a.n_pages < 1 || a.max_pages < 1 || a.page_size < kDecodeTile || a.page_size % kDecodeTile ||
+                          (long long)a.max_pages * a.page_size != a.Ncap))
+        return hipErrorInvalidValue;
+    if (d == 128) return extend_launch<128>(a, stream);
+    if (d == 64) return extend_launch<64>(a, stream);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream)

@@ -102,6 +102,14 @@ struct DecodeArgs {
 int decode_num_splits(int B, int H_kv, int kv_capacity);      // pure host arithmetic: fa2_decode_num_splits
 hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream);      // d = 64 | 128; 1 <= G Nq <= 32; block_table: paged; kv_fp8: e4m3
 
+// Extend attention (fa2_forward_extend, include/fa2_extend_mi355x.h): launch_decode's arguments with any G Nq >= 1 -- the group's
+// rows go in blocks of kExtendRows, two 32-row tiles per wave, grid B Hkv ceil(G Nq / kExtendRows) n_splits -- and its partials.
+#ifndef FA2_EXTEND_ROWS      // 32: one row tile per wave, the grid-only form (an A/B build: tools/gpu_extend_ab.py)
+#define FA2_EXTEND_ROWS 64
+#endif
+constexpr int kExtendRows = FA2_EXTEND_ROWS;
+hipError_t launch_extend(const DecodeArgs& a, int d, hipStream_t stream);
+
 // fp8 (OCP e4m3) forward, d = 128: Q, K, V fp8 [BH][N][128]; O bf16; Vt: [BH][128][Npad] fp8 scratch the
 // launcher fills with V transposed (Npad = N rounded up to 64); kn: [BH][Npad / 64] fp32 scratch it fills with the largest
 // |k| of every 64 keys (fa2_fwd_fp8.hip: where the softmax needs no lane maxima).

@@ -361,16 +361,17 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _decode_shapes(Q, K_cache, V_cache):
+def _decode_shapes(Q, K_cache, V_cache, max_rows=DECODE_MAX_ROWS):
     """(B, H, H_kv, N_q, N_cap, d, fp8) of a decode problem: Q [B, H, N_q, d] bf16 against caches [B, H_kv, N_cap, d], bf16 or (fp8)
-    e4m3, H_kv dividing H.  Shapes and dtypes first (_qkv_shapes); device and contiguity are the caller's to check next."""
+    e4m3, H_kv dividing H.  Shapes and dtypes first (_qkv_shapes); device and contiguity are the caller's to check next.
+    max_rows: the most rows (H / H_kv) N_q of a K/V head the call takes (None: any, the extend calls)."""
     B, H, Hkv, Nq, Ncap, d = _qkv_shapes(Q, K_cache, V_cache, "K_cache", "V_cache", "N_cap", "decode is")
     fp8 = _kv_dtypes(Q, K_cache, V_cache, "K_cache", "V_cache")
     if d not in (64, 128):
         raise ValueError(f"Q: head_dim {d}, expected 64 or 128")
-    if (H // Hkv) * Nq > DECODE_MAX_ROWS:
+    if max_rows is not None and (H // Hkv) * Nq > max_rows:
         raise ValueError(f"Q: {H // Hkv} query heads per K/V head x {Nq} query tokens = {(H // Hkv) * Nq} rows, decode takes at most "
-                         f"{DECODE_MAX_ROWS}: that is a prefill chunk, use flash_attention_2_qk_forward")
+                         f"{max_rows}: that is a prefill chunk, use flash_attention_2_qk_forward")
     return B, H, Hkv, Nq, Ncap, d, fp8
 
 
@@ -419,8 +420,11 @@ def decode_num_splits(B, H_kv, kv_capacity, head_dim, *, q_len=1, window_left=No
     return _capi.lib().fa2_decode_window_num_splits(B, H_kv, q_len, kv_capacity, head_dim, w)
 
 
-def _decode_need(lib, B, H, Hkv, Nq, Ncap, d, n_splits, window_left):
-    """Workspace bytes of a decode call: n_splits = 0 resolved by the window's rule where there is one."""
+def _decode_need(lib, B, H, Hkv, Nq, Ncap, d, n_splits, window_left, extend=False):
+    """Workspace bytes of a decode call: n_splits = 0 resolved by the window's rule where there is one (extend: by the extend
+    calls' rule, fa2_extend_workspace_bytes)."""
+    if extend:
+        return lib.fa2_extend_workspace_bytes(B, H, Hkv, Nq, Ncap, d, n_splits, -1 if window_left is None else window_left)
     if window_left is not None and n_splits == 0:
         n_splits = lib.fa2_decode_window_num_splits(B, Hkv, Nq, Ncap, d, window_left)
     return lib.fa2_decode_workspace_bytes(B, H, Hkv, Nq, Ncap, d, n_splits)
@@ -467,7 +471,14 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     decode_num_splits(B, H_kv, N_cap, d, q_len=N_q, window_left=window_left) and the workspace decode_workspace(..., q_len=N_q,
     window_left=window_left).  bf16 and e4m3 caches, sinks, GQA and graph capture as above; a window >= N_cap - 1 is this call
     without one, bit for bit."""
-    B, H, Hkv, Nq, Ncap, d, fp8 = _decode_shapes(Q, K_cache, V_cache)
+    return _decode_call(Q, K_cache, V_cache, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace, stream, k_descale,
+                        v_descale, window_left, False)
+
+
+def _decode_call(Q, K_cache, V_cache, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace, stream, k_descale, v_descale,
+                 window_left, extend):
+    """flash_attention_2_decode (extend: flash_attention_2_extend, no row limit): one set of checks for both."""
+    B, H, Hkv, Nq, Ncap, d, fp8 = _decode_shapes(Q, K_cache, V_cache, None if extend else DECODE_MAX_ROWS)
     if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
     window_left = _window_arg(window_left, causal)
@@ -487,14 +498,19 @@ def flash_attention_2_decode(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
     L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
     lib = _capi.lib()
-    need = _decode_need(lib, B, H, Hkv, Nq, Ncap, d, n_splits, window_left)
+    need = _decode_need(lib, B, H, Hkv, Nq, Ncap, d, n_splits, window_left, extend)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
     if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
-        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (decode_workspace)")
+        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed ({'extend' if extend else 'decode'}_workspace)")
     head = (Q.data_ptr(), K_cache.data_ptr(), V_cache.data_ptr(), _ptr(seqlens_k), _ptr(sink))
     tail = (1 if causal else 0, n_splits, _ptr(workspace), 0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
-    if window_left is not None:
+    if extend:
+        st = lib.fa2_forward_extend(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d, scale,
+                                    FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, *tail,
+                                    -1 if window_left is None else window_left)
+        check(st, "fa2_forward_extend")
+    elif window_left is not None:
         st = lib.fa2_forward_decode_window(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), B, H, Hkv, Nq, Ncap, d,
                                            scale, FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, *tail, window_left)
         check(st, "fa2_forward_decode_window")
@@ -531,10 +547,10 @@ def _block_table_arg(block_table, Q, B):
     return block_table.shape[1]
 
 
-def _decode_paged_shapes(Q, K_pages, V_pages):
+def _decode_paged_shapes(Q, K_pages, V_pages, max_rows=DECODE_MAX_ROWS):
     """(B, H, H_kv, N_q, n_pages, page_size, d, fp8) of a paged decode problem: Q [B, H, N_q, d] bf16 against pools [n_pages, H_kv,
     page_size, d], bf16 or (fp8) e4m3, H_kv dividing H, page_size a multiple of 32.  Device and contiguity are the caller's to check
-    next."""
+    next.  max_rows: as _decode_shapes."""
     for n, t in (("Q", Q), ("K_pages", K_pages), ("V_pages", V_pages)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise ValueError(f"{n}: expected a 4-d tensor ({'[B, H, N_q, d]' if n == 'Q' else '[n_pages, H_kv, page_size, d]'}), got "
@@ -554,9 +570,9 @@ def _decode_paged_shapes(Q, K_pages, V_pages):
     fp8 = _kv_dtypes(Q, K_pages, V_pages, "K_pages", "V_pages")
     if d not in (64, 128):
         raise ValueError(f"Q: head_dim {d}, expected 64 or 128")
-    if (H // Hkv) * Nq > DECODE_MAX_ROWS:
+    if max_rows is not None and (H // Hkv) * Nq > max_rows:
         raise ValueError(f"Q: {H // Hkv} query heads per K/V head x {Nq} query tokens = {(H // Hkv) * Nq} rows, decode takes at most "
-                         f"{DECODE_MAX_ROWS}: that is a prefill chunk, use flash_attention_2_qk_forward")
+                         f"{max_rows}: that is a prefill chunk, use flash_attention_2_qk_forward")
     return B, H, Hkv, Nq, n_pages, page_size, d, fp8
 
 
@@ -585,7 +601,14 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     BEFORE THE WINDOW: with lo_b = max(0, len_b - N_q - window_left), every table entry of a page that lies wholly below lo_b may
     hold anything (stale, -1, out of range) and so may those pages: they are never read, prefetches included, so a server may
     free the pages behind the window and hand them to other sequences."""
-    B, H, Hkv, Nq, n_pages, page_size, d, fp8 = _decode_paged_shapes(Q, K_pages, V_pages)
+    return _decode_paged_call(Q, K_pages, V_pages, block_table, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace, stream,
+                              k_descale, v_descale, window_left, False)
+
+
+def _decode_paged_call(Q, K_pages, V_pages, block_table, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace, stream,
+                       k_descale, v_descale, window_left, extend):
+    """flash_attention_2_decode_paged (extend: flash_attention_2_extend_paged, no row limit): one set of checks for both."""
+    B, H, Hkv, Nq, n_pages, page_size, d, fp8 = _decode_paged_shapes(Q, K_pages, V_pages, None if extend else DECODE_MAX_ROWS)
     if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
     window_left = _window_arg(window_left, causal)
@@ -609,15 +632,19 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     O = torch.empty_like(Q) if O is None else _like(O, "O", Q, (B, H, Nq, d), Q.dtype)
     L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
     lib = _capi.lib()
-    need = _decode_need(lib, B, H, Hkv, Nq, kv_capacity, d, n_splits, window_left)
+    need = _decode_need(lib, B, H, Hkv, Nq, kv_capacity, d, n_splits, window_left, extend)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
     if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
-        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (decode_workspace)")
+        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed ({'extend' if extend else 'decode'}_workspace)")
     head = (Q.data_ptr(), K_pages.data_ptr(), V_pages.data_ptr(), block_table.data_ptr(), _ptr(seqlens_k), _ptr(sink))
     dims = (B, H, Hkv, Nq, n_pages, page_size, max_pages, d, scale)
     tail = (1 if causal else 0, n_splits, _ptr(workspace), 0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
-    if window_left is not None:
+    if extend:
+        st = lib.fa2_forward_extend_paged(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), *dims, FA2_DTYPE_BF16,
+                                          FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, *tail, -1 if window_left is None else window_left)
+        check(st, "fa2_forward_extend_paged")
+    elif window_left is not None:
         st = lib.fa2_forward_decode_paged_window(*head, _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr(), *dims,
                                                  FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, *tail, window_left)
         check(st, "fa2_forward_decode_paged_window")
@@ -629,6 +656,48 @@ def flash_attention_2_decode_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
         st = lib.fa2_forward_decode_paged(*head, O.data_ptr(), L.data_ptr(), *dims, FA2_DTYPE_BF16, *tail)
         check(st, "fa2_forward_decode_paged")
     return O, L
+
+
+def extend_num_splits(B, H, H_kv, q_len, kv_capacity, head_dim, *, window_left=None):
+    """The split count n_splits=0 stands for in the extend calls (fa2_extend_num_splits): host arithmetic, never on a length.  With
+    M = (H / H_kv) q_len <= 32 it is decode_num_splits(B, H_kv, kv_capacity, head_dim, q_len=q_len, window_left=window_left); above, the
+    same rule with B H_kv ceil(M / 64) workgroups to fill the GPU -- a prefill chunk resolves to one split."""
+    w = _window_arg(window_left, True)
+    return _capi.lib().fa2_extend_num_splits(B, H, H_kv, q_len, kv_capacity, head_dim, -1 if w is None else w)
+
+
+def extend_workspace(B, H, H_kv, N_q, kv_capacity, d, n_splits=0, device="cuda", *, window_left=None):
+    """Scratch for flash_attention_2_extend / _paged (the splits' fp32 partials; empty for one split): allocate once, pass as
+    workspace= (graph capture).  n_splits=0 is extend_num_splits(B, H, H_kv, N_q, kv_capacity, d, window_left=window_left)."""
+    w = _window_arg(window_left, True)
+    return torch.empty(_decode_need(_capi.lib(), B, H, H_kv, N_q, kv_capacity, d, n_splits, w, True), dtype=torch.uint8, device=device)
+
+
+def flash_attention_2_extend(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=None, causal=True, sink=None, n_splits=0,
+                             O=None, L=None, workspace=None, stream=None, k_descale=None, v_descale=None, window_left=None):
+    """O, L = flash_attention_2_decode for ANY number of query rows per K/V head (fa2_forward_extend, include/fa2_extend_mi355x.h):
+    extend attention -- speculative-decoding verification, MQA and wide groups at N_q = 1, a prefill chunk or a prefix-cache hit
+    against a cache that is bf16 or e4m3.  Every argument, check and promise is flash_attention_2_decode's (seqlens_k, block of
+    the sequence's LAST N_q tokens already in the cache, bottom-right causal mask, sink, descales, window_left, rows without a key,
+    garbage past a length and before the window, graph capture, (O, L) for merge_states_forward); only (H / H_kv) N_q <= 32 is
+    gone.  With at most 32 rows per K/V head the call IS flash_attention_2_decode, bit for bit; above, a workgroup takes 64 rows
+    of a K/V head's [H / H_kv][N_q] slab and a row's result is bit for bit what flash_attention_2_decode gives for it on a slice
+    of at most 32 rows with the same n_splits.  n_splits=0 is extend_num_splits(...), the workspace extend_workspace(...).
+    On a contiguous bf16 cache with equal lengths flash_attention_2_qk_forward computes the same; measured (profiles/extend_times.json,
+    d = 128) it takes 1.35 - 1.41 times this call's time at N_q = 512 and 8 - 40 times at N_q 8 and 1: no measured N_q favours it.
+    INFERENCE ONLY.  Not covered: a q_len per sequence, tree masks, token-major layouts."""
+    return _decode_call(Q, K_cache, V_cache, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace, stream, k_descale,
+                        v_descale, window_left, True)
+
+
+def flash_attention_2_extend_paged(Q, K_pages, V_pages, block_table, seqlens_k=None, softmax_scale=None, causal=True, sink=None,
+                                   n_splits=0, O=None, L=None, workspace=None, stream=None, k_descale=None, v_descale=None,
+                                   window_left=None):
+    """flash_attention_2_extend over a pool of pages (fa2_forward_extend_paged): flash_attention_2_decode_paged's arguments, checks
+    and promises (block table read on the device, entries past a length and behind the window never read, the clamp of an entry
+    in use, shared pages) without the row limit; with the same n_splits bit for bit flash_attention_2_extend on the gathered cache."""
+    return _decode_paged_call(Q, K_pages, V_pages, block_table, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace,
+                              stream, k_descale, v_descale, window_left, True)
 
 
 def _kv_new_arg(K_new, V_new):
