@@ -8,6 +8,8 @@ from .ops import flash_attention_2_qk_forward, flash_attention_2_qk_backward, at
 from .ops import flash_attention_2_decode, decode_num_splits, decode_workspace  # noqa: F401
 from .ops import flash_attention_2_decode_paged  # noqa: F401
 from .ops import flash_attention_2_extend, flash_attention_2_extend_paged, extend_num_splits, extend_workspace  # noqa: F401
+from .ops import flash_attention_2_extend_ragged, flash_attention_2_extend_ragged_paged  # noqa: F401
+from .ops import ExtendRaggedPlan, extend_ragged_plan, extend_ragged_num_splits, extend_ragged_workspace  # noqa: F401
 from .ops import kv_cache_append, kv_cache_append_paged  # noqa: F401
 from .ops import rope_kv_cache_append, rope_kv_cache_append_paged  # noqa: F401
 from .ops import merge_states_forward,merge_states_backward, merge_attention_states, attention_segments  # noqa: F401

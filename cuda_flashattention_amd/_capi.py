@@ -16,6 +16,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mi355x.h")
 KVCACHE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_kvcache_mi355x.h")
 ROPE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_mi355x.h")
 EXTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend_mi355x.h")
+EXTEND_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend_ragged_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -117,6 +118,19 @@ EXTEND_SIGNATURES = {
     "fa2_forward_extend_paged": SIGNATURES["fa2_forward_decode_paged_window"],
 }
 
+# include/fa2_extend_ragged_mi355x.h, the same library: the extend calls with a q_len per sequence and token-major rows (the
+# siblings' argument lists with total_q for q_len, q_token_stride behind Q, and plan, plan_bytes behind the caches or the table).
+EXTEND_RAGGED_SIGNATURES = {
+    "fa2_extend_ragged_max_blocks": (_ll, [_i] * 4),
+    "fa2_extend_ragged_plan_bytes": (_sz, [_i] * 4),
+    "fa2_extend_ragged_plan": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "fa2_extend_ragged_num_splits": (_i, [_i] * 7),
+    "fa2_extend_ragged_workspace_bytes": (_sz, [_i] * 8),
+    "fa2_forward_extend_ragged": (_i, [_vp, _ll, _vp, _vp, _vp, _sz] + [_vp] * 6 + [_i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
+    "fa2_forward_extend_ragged_paged": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _sz] + [_vp] * 6
+                                        + [_i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -142,7 +156,7 @@ def lib():
                 "(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items())
-                                  + list(EXTEND_SIGNATURES.items())):
+                                  + list(EXTEND_SIGNATURES.items()) + list(EXTEND_RAGGED_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -110,6 +110,25 @@ hipError_t launch_decode(const DecodeArgs& a, int d, hipStream_t stream);      /
 constexpr int kExtendRows = FA2_EXTEND_ROWS;
 hipError_t launch_extend(const DecodeArgs& a, int d, hipStream_t stream);
 
+// Ragged extend attention (fa2_forward_extend_ragged, include/fa2_extend_ragged_mi355x.h): a q_len per sequence, token-major rows.
+// a: launch_extend's with B sequences, Nq unused (every sequence brings its own), Q [T][Hq][d] with q_stride elements between
+// tokens, O [T][Hq][d], L [T][Hq], partials [n_splits][T Hq].  The PLAN (DEVICE, ints, written by launch_extend_ragged_plan
+// from cu_seqlens_q alone) is where a workgroup learns its sequence and row block:
+//   header [kRaggedPlanHeader]: B, G = Hq / Hkv, T, the number of work items, the first owned token, one past the last, 0, 0
+//   seq [B][2]: (start_b, q_b), 0 <= start_b, start_b + q_b <= T, the sequences tiling [first token, last) in order of b
+//   items [max_blocks][2]: (b, row block j of the [G][q_b] slab), in order of b; (-1, 0) from the header's count on.
+// A workgroup whose header does not name the call's B, G and T leaves at once, and so does one whose entries are out of range.
+constexpr int kRaggedPlanHeader = 8;
+struct ExtendRaggedArgs {
+    DecodeArgs a;
+    const int* plan;
+    int T, max_blocks;
+    long long q_stride;
+};
+long long extend_ragged_max_blocks(int B, int H_q, int H_kv, int total_q);      // floor(G T / 64) + min(B, T); host arithmetic
+hipError_t launch_extend_ragged_plan(const int* cu_seqlens_q, int B, int G, int T, int* plan, hipStream_t stream);
+hipError_t launch_extend_ragged(const ExtendRaggedArgs& x, int d, hipStream_t stream);
+
 // fp8 (OCP e4m3) forward, d = 128: Q, K, V fp8 [BH][N][128]; O bf16; Vt: [BH][128][Npad] fp8 scratch the
 // launcher fills with V transposed (Npad = N rounded up to 64); kn: [BH][Npad / 64] fp32 scratch it fills with the largest
 // |k| of every 64 keys (fa2_fwd_fp8.hip: where the softmax needs no lane maxima).

@@ -685,7 +685,7 @@ def flash_attention_2_extend(Q, K_cache, V_cache, seqlens_k=None, softmax_scale=
     of at most 32 rows with the same n_splits.  n_splits=0 is extend_num_splits(...), the workspace extend_workspace(...).
     On a contiguous bf16 cache with equal lengths flash_attention_2_qk_forward computes the same; measured (profiles/extend_times.json,
     d = 128) it takes 1.35 - 1.41 times this call's time at N_q = 512 and 8 - 40 times at N_q 8 and 1: no measured N_q favours it.
-    INFERENCE ONLY.  Not covered: a q_len per sequence, tree masks, token-major layouts."""
+    INFERENCE ONLY.  A q_len per sequence and token-major Q / O: flash_attention_2_extend_ragged.  Not covered: tree masks."""
     return _decode_call(Q, K_cache, V_cache, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace, stream, k_descale,
                         v_descale, window_left, True)
 
@@ -698,6 +698,228 @@ def flash_attention_2_extend_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
     in use, shared pages) without the row limit; with the same n_splits bit for bit flash_attention_2_extend on the gathered cache."""
     return _decode_paged_call(Q, K_pages, V_pages, block_table, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace,
                               stream, k_descale, v_descale, window_left, True)
+
+
+class ExtendRaggedPlan:
+    """What extend_ragged_plan returns and the ragged extend calls take: the device buffer the plan kernel filled (`tensor`,
+    int32) and the (B, H_q, H_kv, total_q) it was built for.  It depends on cu_seqlens_q and H_q / H_kv only: build it once per
+    step, pass it to every layer's call."""
+    __slots__ = ("tensor", "B", "H_q", "H_kv", "total_q")
+
+    def __init__(self, tensor, B, H_q, H_kv, total_q):
+        self.tensor, self.B, self.H_q, self.H_kv, self.total_q = tensor, B, H_q, H_kv, total_q
+
+
+def _ragged_dims(H_q, H_kv, total_q):
+    for n, v in (("H_q", H_q), ("H_kv", H_kv), ("total_q", total_q)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{n}: {v!r}, expected an int >= 1")
+    if H_q % H_kv:
+        raise ValueError(f"H_kv: {H_kv} does not divide H_q = {H_q}")
+    if total_q * H_q > 0x7fffffff - 64:
+        raise ValueError(f"total_q: {total_q} tokens x {H_q} heads is more rows than an int indexes")
+
+
+def _cu_seqlens_q_arg(cu):
+    """cu_seqlens_q of a ragged extend step: like seqlens_k it is read ON THE DEVICE (by the plan kernel), never by the host.
+    Returns B."""
+    if not isinstance(cu, torch.Tensor):
+        raise ValueError(f"cu_seqlens_q must be an int32 device tensor of B + 1 offsets (or an ExtendRaggedPlan), got {type(cu).__name__}: "
+                         "the plan kernel reads it on the device, the host never does")
+    if cu.dtype != torch.int32:
+        raise ValueError(f"cu_seqlens_q: dtype {cu.dtype}, expected torch.int32")
+    if cu.dim() != 1 or cu.numel() < 2:
+        raise ValueError(f"cu_seqlens_q: shape {tuple(cu.shape)}, expected (B + 1,) with B >= 1")
+    if not cu.is_contiguous():
+        raise ValueError(f"cu_seqlens_q must be contiguous (got stride {tuple(cu.stride())}; call .contiguous())")
+    if not cu.is_cuda:
+        raise ValueError("cu_seqlens_q is a CPU tensor: the plan kernel reads it on the device (the host never reads it)")
+    return cu.numel() - 1
+
+
+def extend_ragged_plan(cu_seqlens_q, H_q, H_kv, total_q, plan=None, stream=None):
+    """The plan of a ragged extend step (fa2_extend_ragged_plan, include/fa2_extend_ragged_mi355x.h): ONE small launch that turns
+    cu_seqlens_q (int32 [B + 1] DEVICE tensor: sequence b owns tokens cu[b] .. cu[b + 1] - 1 of the total_q packed ones, q_b = 0
+    allowed) into the sanitised (start_b, q_b) and the list of 64-row work items the attention kernels read.  It depends on
+    cu_seqlens_q and H_q / H_kv only: every layer of the step reuses it.  The host never reads cu_seqlens_q; a tensor that is not
+    non-decreasing within [0, total_q] is the caller's error with a defined outcome (the running maximum, clamped).
+    plan: None (a buffer is allocated), a device tensor of at least fa2_extend_ragged_plan_bytes bytes, 16-byte aligned, or an
+    ExtendRaggedPlan to refill in place -- PASS ONE FOR GRAPH CAPTURE and rewrite cu_seqlens_q in place between replays.
+    Returns an ExtendRaggedPlan."""
+    _ragged_dims(H_q, H_kv, total_q)
+    B = _cu_seqlens_q_arg(cu_seqlens_q)
+    lib = _capi.lib()
+    need = lib.fa2_extend_ragged_plan_bytes(B, H_q, H_kv, total_q)
+    if not need:
+        raise ValueError(f"extend_ragged_plan: no plan for B = {B}, H_q = {H_q}, H_kv = {H_kv}, total_q = {total_q}")
+    if isinstance(plan, ExtendRaggedPlan):
+        if (plan.B, plan.H_q // plan.H_kv, plan.total_q) != (B, H_q // H_kv, total_q):
+            raise ValueError(f"plan: built for B = {plan.B}, H_q / H_kv = {plan.H_q // plan.H_kv}, total_q = {plan.total_q}; "
+                             f"this step has B = {B}, H_q / H_kv = {H_q // H_kv}, total_q = {total_q}")
+        buf = plan.tensor
+    elif plan is None:
+        buf = torch.empty(need // 4, dtype=torch.int32, device=cu_seqlens_q.device)
+    else:
+        buf = plan
+    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or not buf.is_contiguous() or buf.device != cu_seqlens_q.device:
+        raise ValueError("plan must be a contiguous device tensor on cu_seqlens_q's device")
+    if _nbytes(buf) < need or buf.data_ptr() % 16:
+        raise ValueError(f"plan: {_nbytes(buf)} bytes at an address % 16 = {buf.data_ptr() % 16}, {need} needed, 16-byte aligned")
+    st = lib.fa2_extend_ragged_plan(cu_seqlens_q.data_ptr(), B, H_q, H_kv, total_q, buf.data_ptr(), _nbytes(buf), _stream_ptr(stream))
+    check(st, "fa2_extend_ragged_plan")
+    return ExtendRaggedPlan(buf, B, H_q, H_kv, total_q)
+
+
+def extend_ragged_num_splits(B, H, H_kv, total_q, kv_capacity, head_dim, *, window_left=None):
+    """The split count n_splits=0 stands for in the ragged extend calls (fa2_extend_ragged_num_splits): host arithmetic on B,
+    total_q and the capacity, never on a q_b or a length: min(ceil(256 / workgroups), max(1, span / 256), 256) with
+    workgroups = H_kv max(min(B, total_q), ceil((H / H_kv) total_q / 64))."""
+    w = _window_arg(window_left, True)
+    return _capi.lib().fa2_extend_ragged_num_splits(B, H, H_kv, total_q, kv_capacity, head_dim, -1 if w is None else w)
+
+
+def extend_ragged_workspace(B, H, H_kv, total_q, kv_capacity, d, n_splits=0, device="cuda", *, window_left=None):
+    """Scratch for flash_attention_2_extend_ragged / _paged (the splits' fp32 partials; empty for one split): allocate once, pass
+    as workspace= (graph capture).  n_splits=0 is extend_ragged_num_splits(...)."""
+    w = _window_arg(window_left, True)
+    need = _capi.lib().fa2_extend_ragged_workspace_bytes(B, H, H_kv, total_q, kv_capacity, d, n_splits, -1 if w is None else w)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _extend_ragged_call(Q, K, V, block_table, cu_or_plan, seqlens_k, softmax_scale, causal, sink, n_splits, O, L, workspace, stream,
+                        k_descale, v_descale, window_left):
+    """flash_attention_2_extend_ragged (block_table None) and _paged: one set of checks for both, the siblings' in their order."""
+    paged = block_table is not None
+    kname, vname = ("K_pages", "V_pages") if paged else ("K_cache", "V_cache")
+    want = "[n_pages, H_kv, page_size, d]" if paged else "[B, H_kv, N_cap, d]"
+    if not isinstance(Q, torch.Tensor) or Q.dim() != 3:
+        raise ValueError(f"Q: expected a 3-d tensor [T, H_q, d] (token-major), got {tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
+    for n, t in ((kname, K), (vname, V)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a 4-d tensor {want}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    T, H, d = Q.shape
+    n0, Hkv, n2, dk = K.shape
+    if dk != d or Hkv < 1 or H % Hkv != 0 or T < 1 or n0 < 1 or n2 < 1:
+        raise ValueError(f"{kname}: shape {tuple(K.shape)} does not match Q {tuple(Q.shape)}: expected {want} with d = {d} and H_kv dividing H_q = {H}")
+    if tuple(V.shape) != tuple(K.shape):
+        raise ValueError(f"{vname}: shape {tuple(V.shape)} does not match {kname} {tuple(K.shape)}")
+    if paged and n2 % DECODE_PAGE_GRAIN:
+        raise ValueError(f"K_pages: page_size {n2} is not a multiple of {DECODE_PAGE_GRAIN} (the kernel's key tile)")
+    if Q.dtype != torch.bfloat16:
+        raise ValueError(f"Q: dtype {Q.dtype}, expected torch.bfloat16")
+    fp8 = _kv_dtypes(Q, K, V, kname, vname)
+    if d not in (64, 128):
+        raise ValueError(f"Q: head_dim {d}, expected 64 or 128")
+    if Q.stride(2) != 1 or Q.stride(1) != d:
+        raise ValueError(f"Q: strides {tuple(Q.stride())}, the last two dimensions must be contiguous ([T, H_q, d] with strides (s, d, 1))")
+    if T > 1 and (Q.stride(0) < H * d or Q.stride(0) % 8):
+        raise ValueError(f"Q: token stride {Q.stride(0)}, expected at least H_q x d = {H * d} and a multiple of 8 elements (a lane loads 16 bytes)")
+    if Q.storage_offset() % 8:
+        raise ValueError(f"Q: storage offset {Q.storage_offset()} elements is not 16-byte aligned (a multiple of 8): a lane loads 16 bytes")
+    q_stride = Q.stride(0) if T > 1 else H * d
+    if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
+        raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
+    window_left = _window_arg(window_left, causal)
+    if isinstance(cu_or_plan, ExtendRaggedPlan):
+        plan = cu_or_plan
+        if (plan.H_q // plan.H_kv, plan.total_q) != (H // Hkv, T):
+            raise ValueError(f"plan: built for H_q / H_kv = {plan.H_q // plan.H_kv} and total_q = {plan.total_q}; Q {tuple(Q.shape)} against "
+                             f"{Hkv} K/V heads has H_q / H_kv = {H // Hkv} and total_q = {T}")
+        B = plan.B
+    else:
+        plan = None
+        B = _cu_seqlens_q_arg(cu_or_plan)
+    if paged:
+        Q4 = Q.new_empty((B, H, 0, d))      # (the shared helpers describe their tensors beside a [B, H, N, d] Q)
+        for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+            if t is not None:
+                _descale_arg(t, Q4, Hkv, name, fp8, kname)
+        max_pages = _block_table_arg(block_table, Q4, B)
+        kv_capacity = max_pages * n2
+        if kv_capacity > 0x7fffffff - (DECODE_MAX_SPLITS + 2) * 128:
+            raise ValueError(f"block_table: {max_pages} pages of {n2} keys is a capacity of {kv_capacity} keys, above what an int indexes")
+    else:
+        Q4 = Q.new_empty((B, H, 0, d))
+        if n0 != B:
+            raise ValueError(f"K_cache: {n0} sequences, cu_seqlens_q (the plan) has {B}")
+        kv_capacity = n2
+    if seqlens_k is not None:
+        _seqlens_arg(seqlens_k, Q4, B)
+    if sink is not None:
+        _sink_arg(sink, Q4, 1)
+    if not paged:
+        for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+            if t is not None:
+                _descale_arg(t, Q4, Hkv, name, fp8, kname)
+    if not Q.is_cuda:
+        raise ValueError("Q must be a device tensor")
+    _like(K, kname, Q, tuple(K.shape), K.dtype)
+    _like(V, vname, Q, tuple(K.shape), K.dtype)
+    scale = _scale(softmax_scale, d)
+    if not scale > 0.0:
+        raise ValueError(f"softmax_scale: {scale}, expected a positive number")
+    if plan is None:
+        if cu_or_plan.device != Q.device:
+            raise ValueError(f"cu_seqlens_q is on {cu_or_plan.device}, expected {Q.device}")
+        plan = extend_ragged_plan(cu_or_plan, H, Hkv, T, stream=stream)
+    elif plan.tensor.device != Q.device:
+        raise ValueError(f"plan is on {plan.tensor.device}, expected {Q.device}")
+    if O is None:
+        O = torch.empty(T, H, d, dtype=Q.dtype, device=Q.device)
+    elif not isinstance(O, torch.Tensor) or tuple(O.shape) != (T, H, d) or O.dtype != Q.dtype or not O.is_contiguous() or O.device != Q.device:
+        raise ValueError(f"O: expected a contiguous {Q.dtype} tensor {(T, H, d)} on {Q.device}")
+    L = torch.empty(T, H, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, T, H, 1)
+    lib = _capi.lib()
+    need = lib.fa2_extend_ragged_workspace_bytes(B, H, Hkv, T, kv_capacity, d, n_splits, -1 if window_left is None else window_left)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+    if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
+        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (extend_ragged_workspace)")
+    mid = (plan.tensor.data_ptr(), _nbytes(plan.tensor), _ptr(seqlens_k), _ptr(sink), _ptr(k_descale), _ptr(v_descale), O.data_ptr(), L.data_ptr())
+    tail = (d, scale, FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, 1 if causal else 0, n_splits, _ptr(workspace),
+            0 if workspace is None else _nbytes(workspace), _stream_ptr(stream), -1 if window_left is None else window_left)
+    if paged:
+        st = lib.fa2_forward_extend_ragged_paged(Q.data_ptr(), q_stride, K.data_ptr(), V.data_ptr(), block_table.data_ptr(), *mid,
+                                                 B, H, Hkv, T, n0, n2, max_pages, *tail)
+        check(st, "fa2_forward_extend_ragged_paged")
+    else:
+        st = lib.fa2_forward_extend_ragged(Q.data_ptr(), q_stride, K.data_ptr(), V.data_ptr(), *mid, B, H, Hkv, T, kv_capacity, *tail)
+        check(st, "fa2_forward_extend_ragged")
+    return O, L
+
+
+def flash_attention_2_extend_ragged(Q, K_cache, V_cache, cu_seqlens_q_or_plan, seqlens_k=None, softmax_scale=None, causal=True,
+                                    sink=None, n_splits=0, O=None, L=None, workspace=None, stream=None, k_descale=None,
+                                    v_descale=None, window_left=None):
+    """O, L = flash_attention_2_extend with a q_len PER SEQUENCE and TOKEN-MAJOR rows (fa2_forward_extend_ragged,
+    include/fa2_extend_ragged_mi355x.h): one call for a continuous-batching step that mixes prompt chunks, speculative
+    verification and plain decodes.  Q: bf16 [T, H_q, d], any view with contiguous last two dimensions and a token stride that is
+    a multiple of 8 (the Q slice of a fused QKV output goes in as it is); K_cache, V_cache [B, H_kv, N_cap, d], bf16 or e4m3;
+    returns O [T, H_q, d] and L [T, H_q] -- flattened, the rows merge_states_forward takes.
+    cu_seqlens_q_or_plan: an int32 [B + 1] DEVICE tensor (sequence b owns tokens cu[b] .. cu[b + 1] - 1, q_b = cu[b + 1] - cu[b],
+    0 allowed; the plan is then built inside this call, one more small launch), or the ExtendRaggedPlan extend_ragged_plan
+    built from it -- once per step, shared by every layer.  The host never reads cu_seqlens_q.  Everything
+    flash_attention_2_extend defines with N_q holds with q_b: the q_b queries are the sequence's last q_b cached tokens, key j is
+    visible to token i iff j <= i + len_b - q_b, window_left counts from pos_i = i + len_b - q_b, rows with pos_i < 0 have O = 0
+    and L = -inf (or the sink).  Tokens of no sequence keep what O and L held.  seqlens_k, sink, descales, window_left,
+    n_splits (0 = extend_ragged_num_splits), workspace (extend_ragged_workspace), graph capture: flash_attention_2_extend's.  With
+    the same n_splits a sequence's rows are bit for bit flash_attention_2_extend's on that sequence alone.  INFERENCE ONLY.
+    Not covered: a ragged append, tree masks, token-major pools."""
+    return _extend_ragged_call(Q, K_cache, V_cache, None, cu_seqlens_q_or_plan, seqlens_k, softmax_scale, causal, sink, n_splits, O, L,
+                               workspace, stream, k_descale, v_descale, window_left)
+
+
+def flash_attention_2_extend_ragged_paged(Q, K_pages, V_pages, block_table, cu_seqlens_q_or_plan, seqlens_k=None, softmax_scale=None,
+                                          causal=True, sink=None, n_splits=0, O=None, L=None, workspace=None, stream=None,
+                                          k_descale=None, v_descale=None, window_left=None):
+    """flash_attention_2_extend_ragged over a pool of pages (fa2_forward_extend_ragged_paged): K_pages, V_pages [n_pages, H_kv,
+    page_size, d] and block_table int32 [B, max_pages] as flash_attention_2_extend_paged takes them (read on the device, entries
+    past a length and behind the window never read, an entry in use clamped, shared pages); with the same n_splits bit for bit
+    flash_attention_2_extend_ragged on the gathered cache."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
+    return _extend_ragged_call(Q, K_pages, V_pages, block_table, cu_seqlens_q_or_plan, seqlens_k, softmax_scale, causal, sink, n_splits,
+                               O, L, workspace, stream, k_descale, v_descale, window_left)
 
 
 def _kv_new_arg(K_new, V_new):

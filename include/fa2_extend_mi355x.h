@@ -47,9 +47,10 @@
  * AGAINST fa2_forward_qk.  A caller whose cache is contiguous bf16 with equal lengths could also call fa2_forward_qk on it.  Measured
  * on one MI355X (profiles/extend_times.json, d = 128): that call takes 1.35 - 1.41 times this one's time at q_len = 512 (32 heads on 8,
  * 8192 and 32768 keys) and 8 - 40 times at q_len 8 and 1; no measured q_len favours it.
- * NOT COVERED: a q_len per sequence (ragged batches, cu_seqlens), tree masks for speculative decoding, a backward, token-major
- * Q / O or pools, and what the siblings leave out: per-token or per-page scales, e5m2, pages that are no multiple of 32 keys,
- * head dims other than 64 and 128, fp8 queries.
+ * A q_len PER SEQUENCE (ragged batches, cu_seqlens_q) and token-major Q / O are fa2_forward_extend_ragged / _paged
+ * (fa2_extend_ragged_mi355x.h): these calls give all B sequences one q_len and take Q, O as [B][H_q][q_len][d].
+ * NOT COVERED: tree masks for speculative decoding, a backward, token-major pools, and what the siblings leave out: per-token
+ * or per-page scales, e5m2, pages that are no multiple of 32 keys, head dims other than 64 and 128, fp8 queries.
  */
 #ifndef FA2_EXTEND_MI355X_H
 #define FA2_EXTEND_MI355X_H
