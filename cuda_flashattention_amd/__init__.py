@@ -12,4 +12,6 @@ from .ops import flash_attention_2_extend_ragged, flash_attention_2_extend_ragge
 from .ops import ExtendRaggedPlan, extend_ragged_plan, extend_ragged_num_splits, extend_ragged_workspace  # noqa: F401
 from .ops import kv_cache_append, kv_cache_append_paged  # noqa: F401
 from .ops import rope_kv_cache_append, rope_kv_cache_append_paged  # noqa: F401
+from .ops import rope_kv_cache_append_ragged, rope_kv_cache_append_ragged_paged  # noqa: F401
+from .ops import kv_cache_append_ragged, kv_cache_append_ragged_paged  # noqa: F401
 from .ops import merge_states_forward,merge_states_backward, merge_attention_states, attention_segments  # noqa: F401

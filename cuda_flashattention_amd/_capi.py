@@ -17,6 +17,7 @@ KVCACHE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_kvcac
 ROPE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_mi355x.h")
 EXTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend_mi355x.h")
 EXTEND_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend_ragged_mi355x.h")
+ROPE_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_ragged_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -131,6 +132,13 @@ EXTEND_RAGGED_SIGNATURES = {
                                         + [_i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, _vp, _i]),
 }
 
+# include/fa2_rope_ragged_mi355x.h, the same library: the rotary append with an n_new per sequence and token-major tensors (the
+# siblings' argument lists with plan, plan_bytes before seqlens_k, total_q for n_new, and two strides per source for three).
+ROPE_RAGGED_SIGNATURES = {
+    "fa2_rope_kv_append_ragged": (_i, [_vp] * 9 + [_sz] + [_vp] * 3 + [_i] * 9 + [_ll] * 4 + [_i, _i, _vp]),
+    "fa2_rope_kv_append_ragged_paged": (_i, [_vp] * 10 + [_sz] + [_vp] * 3 + [_i] * 11 + [_ll] * 4 + [_i, _i, _vp]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -156,7 +164,8 @@ def lib():
                 "(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items())
-                                  + list(EXTEND_SIGNATURES.items()) + list(EXTEND_RAGGED_SIGNATURES.items())):
+                                  + list(EXTEND_SIGNATURES.items()) + list(EXTEND_RAGGED_SIGNATURES.items())
+                                  + list(ROPE_RAGGED_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

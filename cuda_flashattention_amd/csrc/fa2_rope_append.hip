@@ -12,16 +12,15 @@
 // ADDRESSES.  A cache destination is formed by fa2_kv_append_addr.h and nothing else, exactly as the append forms it.  A table
 // row is read only for a position that passed 0 <= pos < capacity, and the host has checked capacity <= n_positions.  A Q_out
 // row is a function of (b, head, t) alone, t < n_new.  No loop bound comes from device memory.
-// ROTATION.  Each product and each sum is one fp32 rounding: `#pragma clang fp contract(off)` in the two rotation functions
-// (hipcc contracts a*b + c*d into a fused multiply-add by default, which rounds once less and changes bits).  The partner of a
-// rotate-half lane's chunk is the whole chunk of lane c +- rot_dim / 16, fetched with a SECOND 16-byte load;
-// an interleaved lane holds its four pairs itself.  x1*c - x2*s is formed as x1*c + (-x2)*s: the negation is exact, so the bits
-// are the same, and one function serves both halves of a rotate-half row.
+// ROTATION.  fa2_rope_rotate.h, shared with the ragged call (fa2_rope_append_ragged.hip): each product and each sum is one fp32
+// rounding.  The partner of a rotate-half lane's chunk is the whole chunk of lane c +- rot_dim / 16, fetched with a SECOND
+// 16-byte load; an interleaved lane holds its four pairs itself.
 #include "fa2_common.h"
 #include "fa2_kv_append_addr.h"
 #include "fa2_kv_quantise.h"
 #include "fa2_launch.h"
 #include "fa2_rope_mi355x.h"
+#include "fa2_rope_rotate.h"
 
 #include <algorithm>
 
@@ -34,7 +33,6 @@ constexpr int kRopeMaxBlocks = 2048;     // 256 CUs x 8 workgroups of 4 waves: a
 // what a wave reads once per unit, at a wave-uniform address: the constant address space makes these scalar loads
 typedef __attribute__((address_space(4))) int rope_const_int;
 typedef __attribute__((address_space(4))) float rope_const_float;
-typedef __attribute__((ext_vector_type(2))) __bf16 rope_bf16x2;
 
 struct RopeAppendArgs {
     const void* Q; void* Qout; const void* Knew; const void* Vnew; void* K; void* V;
@@ -47,49 +45,6 @@ struct RopeAppendArgs {
     long long qb, qh, qt;                        // Q's element strides: batch, head, token
     long long sb, sh, st;                        // K_new's and V_new's
 };
-
-__device__ __forceinline__ float rope_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float rope_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-
-// two fp32 -> two bf16 in one word, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ uint32_t rope_pack(float lo, float hi)
-{
-    const rope_bf16x2 v{(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
-
-// Rotate-half: eight elements x of one half of a row, their partners p in the other half WITH THE SIGN ALREADY SET (negated for
-// the first half), the eight table columns they share: y = bf16(fl(fl(x*cos) + fl(p*sin))).
-__device__ __forceinline__ u32x4 rope_rotate_half8(const u32x4& x, const u32x4& p, const f32x4& c0, const f32x4& c1,
-                                                   const f32x4& s0, const f32x4& s1)
-{
-#pragma clang fp contract(off)
-    const float cs[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-    const float sn[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
-    u32x4 y;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float a0 = rope_lo(x[i]) * cs[2 * i], b0 = rope_lo(p[i]) * sn[2 * i];
-        const float a1 = rope_hi(x[i]) * cs[2 * i + 1], b1 = rope_hi(p[i]) * sn[2 * i + 1];
-        y[i] = rope_pack(a0 + b0, a1 + b1);
-    }
-    return y;
-}
-
-// Interleaved: word i of the chunk is the pair (x1, x2) of table column 4 c + i: y1 = x1*cos - x2*sin, y2 = x2*cos + x1*sin.
-__device__ __forceinline__ u32x4 rope_rotate_pairs8(const u32x4& x, const f32x4& cs, const f32x4& sn)
-{
-#pragma clang fp contract(off)
-    u32x4 y;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float x1 = rope_lo(x[i]), x2 = rope_hi(x[i]);
-        const float a1 = x1 * cs[i], b1 = x2 * sn[i];
-        const float a2 = x2 * cs[i], b2 = x1 * sn[i];
-        y[i] = rope_pack(a1 - b1, a2 + b2);
-    }
-    return y;
-}
 
 template <int D, bool FP8, bool PAGED, bool INTERLEAVED>
 __global__ __launch_bounds__(256) void fa2_rope_append_kernel(const RopeAppendArgs a)

@@ -904,7 +904,7 @@ def flash_attention_2_extend_ragged(Q, K_cache, V_cache, cu_seqlens_q_or_plan, s
     and L = -inf (or the sink).  Tokens of no sequence keep what O and L held.  seqlens_k, sink, descales, window_left,
     n_splits (0 = extend_ragged_num_splits), workspace (extend_ragged_workspace), graph capture: flash_attention_2_extend's.  With
     the same n_splits a sequence's rows are bit for bit flash_attention_2_extend's on that sequence alone.  INFERENCE ONLY.
-    Not covered: a ragged append, tree masks, token-major pools."""
+    The step's ragged append is rope_kv_cache_append_ragged (the same plan).  Not covered: tree masks, token-major pools."""
     return _extend_ragged_call(Q, K_cache, V_cache, None, cu_seqlens_q_or_plan, seqlens_k, softmax_scale, causal, sink, n_splits, O, L,
                                workspace, stream, k_descale, v_descale, window_left)
 
@@ -1222,6 +1222,194 @@ def rope_kv_cache_append_paged(Q, K_new, V_new, K_pages, V_pages, block_table, c
                                               FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16, _stream_ptr(stream))
     check(st, "fa2_rope_kv_append_paged")
     return Q_out
+
+
+def _ragged_rows_arg(x, name, H_name, how):
+    """(H, (stride_t, stride_h)) of a token-major source of a ragged append: a bf16 [T, H, d] VIEW with the last dimension
+    contiguous, strides non-negative multiples of 8 elements, 16-byte aligned -- a lane loads 16 bytes (_kv_new_arg's rules)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError(f"{name}: expected a 3-d tensor [T, {H_name}, d] (token-major), got "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}; {how}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: dtype {x.dtype}, expected torch.bfloat16 (the source of an append is bf16; the cache may be e4m3)")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{name}: shape {tuple(x.shape)}, expected [T, {H_name}, d] with T, {H_name} >= 1")
+    if x.stride(-1) != 1:
+        raise ValueError(f"{name}: stride {tuple(x.stride())}, the last dimension must be contiguous (stride(-1) == 1); {how}")
+    strides = tuple(x.stride()[:2])
+    if any(s < 0 or s % 8 for s in strides):
+        raise ValueError(f"{name}: strides {strides} (token, head) must be non-negative multiples of 8 elements: a lane loads 16 bytes")
+    if x.storage_offset() % 8:
+        raise ValueError(f"{name}: storage offset {x.storage_offset()} elements is not 16-byte aligned (a multiple of 8): a lane loads 16 bytes")
+    return x.shape[1], strides
+
+
+def _rope_ragged_call(Q, K_new, V_new, K, V, block_table, cos, sin, cu_or_plan, seqlens_k, interleaved, k_descale, v_descale, Q_out,
+                      stream):
+    """rope_kv_cache_append_ragged (block_table None) and _paged, kv_cache_append_ragged (cos, sin, Q None) and _paged: one set of
+    checks for the four, the uniform calls' in their order.  Nothing here reads a device value."""
+    paged = block_table is not None
+    kname, vname = ("K_pages", "V_pages") if paged else ("K_cache", "V_cache")
+    want = "[n_pages, H_kv, page_size, d]" if paged else "[B, H_kv, N_cap, d]"
+    how = "pass token-major [T, H, d] views, e.g. the Q, K and V slices of one fused [T, H_q + 2 H_kv, d] projection output"
+    Hkv, strides = _ragged_rows_arg(K_new, "K_new", "H_kv", how)
+    _ragged_rows_arg(V_new, "V_new", "H_kv", how)
+    T, _, d = K_new.shape
+    if tuple(V_new.shape) != tuple(K_new.shape):
+        raise ValueError(f"V_new: shape {tuple(V_new.shape)} does not match K_new {tuple(K_new.shape)}")
+    if d not in (64, 128):
+        raise ValueError(f"K_new: head_dim {d}, expected 64 or 128")
+    if tuple(V_new.stride()) != tuple(K_new.stride()):
+        raise ValueError(f"V_new: strides {tuple(V_new.stride())} differ from K_new's {tuple(K_new.stride())}: one (token, head) "
+                         f"stride pair serves both; {how}")
+    Hq, q_strides = 0, (0, 0)
+    if Q is not None:
+        Hq, q_strides = _ragged_rows_arg(Q, "Q", "H_q", how)
+        if Q.shape[0] != T or Q.shape[2] != d or Hq % Hkv:
+            raise ValueError(f"Q: shape {tuple(Q.shape)} does not match K_new {tuple(K_new.shape)}: expected [{T}, H_q, {d}] with "
+                             f"H_kv = {Hkv} dividing H_q")
+    elif Q_out is not None:
+        raise ValueError("Q_out: given without Q (a K/V-only call has neither)")
+    if (Hq + Hkv) * T > 0x7fffffff:
+        raise ValueError(f"K_new: {T} tokens x {Hq + Hkv} heads is more rows than an int indexes")
+    for n, t in ((kname, K), (vname, V)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{n}: expected a 4-d tensor {want}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    n0, hk, n2, dk = K.shape
+    if hk != Hkv or dk != d or n0 < 1 or n2 < 1:
+        raise ValueError(f"{kname}: shape {tuple(K.shape)} does not match K_new {tuple(K_new.shape)}: expected {want} with H_kv = {Hkv}, d = {d}")
+    if paged and n2 % DECODE_PAGE_GRAIN:
+        raise ValueError(f"K_pages: page_size {n2} is not a multiple of {DECODE_PAGE_GRAIN} (the decode kernel's key tile; a page "
+                         "of 16 keys is not taken)")
+    if tuple(V.shape) != tuple(K.shape):
+        raise ValueError(f"{vname}: shape {tuple(V.shape)} does not match {kname} {tuple(K.shape)}")
+    fp8 = _kv_dtypes(K_new, K, V, kname, vname)
+    for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if t is not None:
+            _descale_arg(t, K_new, Hkv, name, fp8, kname)
+    if (cos is None) != (sin is None):
+        raise ValueError("cos and sin come as a pair: both tensors, or both None for an append without rotation")
+    if cos is not None:
+        _rope_tables_arg(cos, sin, d, 0)
+    flag = _rope_interleaved(interleaved)
+    G = Hq // Hkv if Hq else 1      # a K/V-only call takes a plan of any G; one built here is built for G = 1
+    if isinstance(cu_or_plan, ExtendRaggedPlan):
+        plan = cu_or_plan
+        if plan.total_q != T or (Hq and plan.H_q // plan.H_kv != G):
+            raise ValueError(f"plan: built for H_q / H_kv = {plan.H_q // plan.H_kv} and total_q = {plan.total_q}; this step has "
+                             + (f"H_q / H_kv = {G} and " if Hq else "") + f"total_q = {T} (K_new {tuple(K_new.shape)})")
+        B = plan.B
+    else:
+        plan = None
+        B = _cu_seqlens_q_arg(cu_or_plan)
+    if seqlens_k is None:
+        raise ValueError("seqlens_k is required: token t of sequence b has position seqlens_k[b] - q_b + (t - start_b) (the lengths "
+                         "AFTER the append, the ragged extend call's tensor)")
+    if paged:
+        max_pages = _block_table_arg(block_table, K_new, B)
+        capacity = max_pages * n2
+        if capacity > 0x7fffffff - (DECODE_MAX_SPLITS + 2) * 128:
+            raise ValueError(f"block_table: {max_pages} pages of {n2} keys is a capacity of {capacity} keys, above what an int indexes")
+    else:
+        if n0 != B:
+            raise ValueError(f"K_cache: {n0} sequences, cu_seqlens_q (the plan) has {B}")
+        capacity = n2
+    rot_dim, n_positions = (0, 0) if cos is None else _rope_tables_arg(cos, sin, d, capacity)
+    _seqlens_arg(seqlens_k, K_new, B)
+    _kv_append_devices(K_new, V_new, K, V, kname, vname, tuple(K.shape))
+    for n, t in ((kname, K), (vname, V)):
+        if not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous (got stride {tuple(t.stride())})")
+    if Q is not None and (not Q.is_cuda or Q.device != K_new.device):
+        raise ValueError(f"Q is on {Q.device}, expected {K_new.device}")
+    for n, t in (("cos", cos), ("sin", sin)):
+        if t is None:
+            continue
+        if not t.is_cuda or t.device != K_new.device:
+            raise ValueError(f"{n} is on {t.device}, expected {K_new.device}: the kernel reads the tables on the device when it runs")
+        if not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous (got stride {tuple(t.stride())}; call .contiguous())")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{n}: not 16-byte aligned (storage offset {t.storage_offset()} elements): a lane loads 16 bytes")
+    if Q is None:
+        pass
+    elif Q_out is None:
+        Q_out = torch.empty(T, Hq, d, dtype=torch.bfloat16, device=K_new.device)
+    elif (not isinstance(Q_out, torch.Tensor) or tuple(Q_out.shape) != (T, Hq, d) or Q_out.dtype != torch.bfloat16
+          or not Q_out.is_contiguous() or Q_out.device != K_new.device):
+        raise ValueError(f"Q_out: expected a contiguous torch.bfloat16 tensor {(T, Hq, d)} on {K_new.device}")
+    if plan is None:
+        if cu_or_plan.device != K_new.device:
+            raise ValueError(f"cu_seqlens_q is on {cu_or_plan.device}, expected {K_new.device}")
+        plan = extend_ragged_plan(cu_or_plan, Hq if Hq else Hkv, Hkv, T, stream=stream)
+    elif plan.tensor.device != K_new.device:
+        raise ValueError(f"plan is on {plan.tensor.device}, expected {K_new.device}")
+    lib = _capi.lib()
+    head = (_ptr(Q), _ptr(Q_out), K_new.data_ptr(), V_new.data_ptr(), K.data_ptr(), V.data_ptr())
+    mid = (_ptr(cos), _ptr(sin), plan.tensor.data_ptr(), _nbytes(plan.tensor), seqlens_k.data_ptr(), _ptr(k_descale), _ptr(v_descale))
+    tail = (d, rot_dim, n_positions, flag, *q_strides, *strides, FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16,
+            _stream_ptr(stream))
+    if paged:
+        st = lib.fa2_rope_kv_append_ragged_paged(*head, block_table.data_ptr(), *mid, B, Hq, Hkv, T, n0, n2, max_pages, *tail)
+        check(st, "fa2_rope_kv_append_ragged_paged")
+    else:
+        st = lib.fa2_rope_kv_append_ragged(*head, *mid, B, Hq, Hkv, T, capacity, *tail)
+        check(st, "fa2_rope_kv_append_ragged")
+    return Q_out
+
+
+def rope_kv_cache_append_ragged(Q, K_new, V_new, K_cache, V_cache, cos, sin, cu_seqlens_q_or_plan, seqlens_k, *, interleaved=False,
+                                k_descale=None, v_descale=None, Q_out=None, stream=None):
+    """rope_kv_cache_append with an n_new PER SEQUENCE and TOKEN-MAJOR tensors (fa2_rope_kv_append_ragged,
+    include/fa2_rope_ragged_mi355x.h): the cache-writing half of a continuous-batching step, beside
+    flash_attention_2_extend_ragged.  ONE launch rotates and appends the K of the step's T packed tokens, appends their V, and
+    writes the rotated queries; returns Q_out, bf16 [T, H_q, d] contiguous, what flash_attention_2_extend_ragged takes.  A step is:
+    seqlens_k[b] += q_b (in place), extend_ragged_plan (once), then per layer rope_kv_cache_append_ragged(..., plan, seqlens_k) and
+    flash_attention_2_extend_ragged(Q_out, ..., plan, seqlens_k); one captured graph serves every step while the mix changes.
+    Q [T, H_q, d], K_new, V_new [T, H_kv, d]: bf16 VIEWS (d = 64 | 128) with stride(-1) == 1 and strides that are non-negative
+    multiples of 8; K_new and V_new share theirs, Q has its own: the three slices of a fused [T, H_q + 2 H_kv, d] projection
+    output are passed as they are.  Q=None is a K/V-only call (returns None).  K_cache, V_cache [B, H_kv, N_cap, d], bf16 or e4m3.
+    cu_seqlens_q_or_plan: an int32 [B + 1] DEVICE tensor (sequence b owns tokens cu[b] .. cu[b + 1] - 1, q_b = 0 allowed; the plan
+    is then built inside this call, one more small launch), or the ExtendRaggedPlan extend_ragged_plan built from it -- the one
+    the attention call of the step takes.  The host never reads cu_seqlens_q, seqlens_k, a descale or a table.
+    POSITION: token t of sequence b has position seqlens_k[b] - q_b + (t - cu[b]) -- its cache row, its table row, and the position
+    the ragged extend's mask gives that query.  cos, sin, interleaved, the arithmetic, the e4m3 store and the write-or-drop rule are
+    rope_kv_cache_append's; cos = sin = None appends without rotating.  A sequence's rows are bit for bit what
+    rope_kv_cache_append writes when called on that sequence alone.
+    Q_out: EVERY row t < T is written: rotated where the token is owned and 0 <= position < capacity, +0.0 throughout elsewhere
+    (a dropped position, a token no sequence owns); such a token's K and V are dropped.  Allocated when not given -- pass one for
+    graph capture.  A plan built for another B, H_q / H_kv or T makes the kernel leave without a store."""
+    return _rope_ragged_call(Q, K_new, V_new, K_cache, V_cache, None, cos, sin, cu_seqlens_q_or_plan, seqlens_k, interleaved, k_descale,
+                             v_descale, Q_out, stream)
+
+
+def rope_kv_cache_append_ragged_paged(Q, K_new, V_new, K_pages, V_pages, block_table, cos, sin, cu_seqlens_q_or_plan, seqlens_k, *,
+                                      interleaved=False, k_descale=None, v_descale=None, Q_out=None, stream=None):
+    """rope_kv_cache_append_ragged into a pool of pages (fa2_rope_kv_append_ragged_paged), the pool
+    flash_attention_2_extend_ragged_paged reads: K_pages, V_pages [n_pages, H_kv, page_size, d] and block_table int32 [B, max_pages]
+    exactly as rope_kv_cache_append_paged takes them.  A token whose table entry lies outside [0, n_pages) has its K and V
+    DROPPED; its Q_out row is still the rotated query.  PAGES WRITTEN BY ONE CALL MUST BELONG TO ONE SEQUENCE EACH."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
+    return _rope_ragged_call(Q, K_new, V_new, K_pages, V_pages, block_table, cos, sin, cu_seqlens_q_or_plan, seqlens_k, interleaved,
+                             k_descale, v_descale, Q_out, stream)
+
+
+def kv_cache_append_ragged(K_new, V_new, K_cache, V_cache, cu_seqlens_q_or_plan, seqlens_k, k_descale=None, v_descale=None, stream=None):
+    """kv_cache_append with an n_new PER SEQUENCE and token-major sources: rope_kv_cache_append_ragged without rotation and without
+    queries (fa2_rope_kv_append_ragged with rot_dim = 0, H_q = 0), byte for byte kv_cache_append on every sequence.  K_new, V_new:
+    bf16 [T, H_kv, d] views; a plan built for any H_q / H_kv serves (one built here is built for 1).  Returns None."""
+    _rope_ragged_call(None, K_new, V_new, K_cache, V_cache, None, None, None, cu_seqlens_q_or_plan, seqlens_k, False, k_descale, v_descale,
+                      None, stream)
+
+
+def kv_cache_append_ragged_paged(K_new, V_new, K_pages, V_pages, block_table, cu_seqlens_q_or_plan, seqlens_k, k_descale=None,
+                                 v_descale=None, stream=None):
+    """kv_cache_append_ragged into a pool of pages: kv_cache_append_paged's pool, table and drop rule.  Returns None."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
+    _rope_ragged_call(None, K_new, V_new, K_pages, V_pages, block_table, None, None, cu_seqlens_q_or_plan, seqlens_k, False, k_descale,
+                      v_descale, None, stream)
 
 
 def _sink_pair(sink, dsink, Q, heads_dim):

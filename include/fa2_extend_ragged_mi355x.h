@@ -59,7 +59,8 @@
  * workspace size that overflows -> FA2_ERR_INVALID_SHAPE; plan_bytes below fa2_extend_ragged_plan_bytes or a plan that is not
  * 16-byte aligned -> FA2_ERR_WORKSPACE; n_splits > 1 with a workspace that is NULL, too small or not 16-byte aligned ->
  * FA2_ERR_WORKSPACE; window_left >= 0 without causal -> FA2_ERR_UNSUPPORTED.
- * NOT COVERED: a ragged KV append or a ragged rotary append (n_new per sequence), tree masks for speculative decoding, a
+ * NOT COVERED: in THIS header a ragged KV append or a ragged rotary append (n_new per sequence): the step's other half, driven by
+ * the same plan, is fa2_rope_kv_append_ragged (fa2_rope_ragged_mi355x.h); tree masks for speculative decoding, a
  * backward, token-major pools, a longest-first order of the work items, a one-tile instantiation for sequences of at most 32
  * rows, and what the siblings leave out.
  */

@@ -43,7 +43,8 @@
  * bytes, x 1 for e4m3), B x H_kv x n_new above INT_MAX, a negative stride or one that is no multiple of 8, a pointer that is not
  * 16-byte aligned -> FA2_ERR_INVALID_SHAPE; head_dim other than 64 or 128 -> FA2_ERR_UNSUPPORTED_HEAD_DIM; dtype not bf16,
  * kv_dtype neither bf16 nor e4m3 -> FA2_ERR_UNSUPPORTED_DTYPE; a non-NULL descale beside a bf16 cache -> FA2_ERR_UNSUPPORTED.
- * NOT COVERED: ragged n_new per sequence and packed [T][H][d] sources with cu_seqlens, token-major pools (rotary embedding fused
+ * NOT COVERED: in THESE calls ragged n_new per sequence and packed [T][H][d] sources with cu_seqlens (that is
+ * fa2_rope_kv_append_ragged with rot_dim = 0 and H_q = 0, fa2_rope_ragged_mi355x.h), token-major pools (rotary embedding fused
  * into the append is fa2_rope_kv_append, fa2_rope_mi355x.h), per-token or per-page scales, e5m2, a dequantising gather from pages into contiguous keys, page allocation
  * and copy-on-write.
  */

@@ -49,8 +49,8 @@
  * FA2_ERR_UNSUPPORTED_HEAD_DIM; dtype not bf16, kv_dtype neither bf16 nor e4m3 -> FA2_ERR_UNSUPPORTED_DTYPE; a non-NULL descale
  * beside a bf16 cache -> FA2_ERR_UNSUPPORTED.
  * NOT COVERED: a position other than the cache row (explicit position_ids, multimodal 3-D RoPE), cos/sin computed in the kernel
- * from a base frequency, HF's bf16 arithmetic, a backward, RoPE for the training forward, ragged n_new, head_dim other than 64
- * or 128.
+ * from a base frequency, HF's bf16 arithmetic, a backward, RoPE for the training forward, ragged n_new (an n_new per sequence and
+ * token-major tensors are fa2_rope_kv_append_ragged, fa2_rope_ragged_mi355x.h), head_dim other than 64 or 128.
  */
 #ifndef FA2_ROPE_MI355X_H
 #define FA2_ROPE_MI355X_H
