@@ -13,5 +13,6 @@ from .ops import ExtendRaggedPlan, extend_ragged_plan, extend_ragged_num_splits,
 from .ops import kv_cache_append, kv_cache_append_paged  # noqa: F401
 from .ops import rope_kv_cache_append, rope_kv_cache_append_paged  # noqa: F401
 from .ops import rope_kv_cache_append_ragged, rope_kv_cache_append_ragged_paged  # noqa: F401
+from .ops import norm_rope_kv_cache_append_ragged, norm_rope_kv_cache_append_ragged_paged  # noqa: F401
 from .ops import kv_cache_append_ragged, kv_cache_append_ragged_paged  # noqa: F401
 from .ops import merge_states_forward,merge_states_backward, merge_attention_states, attention_segments  # noqa: F401

@@ -18,6 +18,7 @@ ROPE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_mi3
 EXTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend_mi355x.h")
 EXTEND_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend_ragged_mi355x.h")
 ROPE_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_ragged_mi355x.h")
+ROPE_NORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_norm_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -139,6 +140,13 @@ ROPE_RAGGED_SIGNATURES = {
     "fa2_rope_kv_append_ragged_paged": (_i, [_vp] * 10 + [_sz] + [_vp] * 3 + [_i] * 11 + [_ll] * 4 + [_i, _i, _vp]),
 }
 
+# include/fa2_rope_norm_mi355x.h, the same library: the ragged rotary append with a per-head RMSNorm of Q and K in front of the
+# rotation (the siblings' argument lists with q_weight, k_weight, eps behind sin_table).
+ROPE_NORM_SIGNATURES = {
+    "fa2_norm_rope_kv_append_ragged": (_i, [_vp] * 10 + [_f, _vp, _sz] + [_vp] * 3 + [_i] * 9 + [_ll] * 4 + [_i, _i, _vp]),
+    "fa2_norm_rope_kv_append_ragged_paged": (_i, [_vp] * 11 + [_f, _vp, _sz] + [_vp] * 3 + [_i] * 11 + [_ll] * 4 + [_i, _i, _vp]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -165,7 +173,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items())
                                   + list(EXTEND_SIGNATURES.items()) + list(EXTEND_RAGGED_SIGNATURES.items())
-                                  + list(ROPE_RAGGED_SIGNATURES.items())):
+                                  + list(ROPE_RAGGED_SIGNATURES.items()) + list(ROPE_NORM_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -4,174 +4,27 @@
 // step's packed tokens, appends their V and writes the rotated queries as fa2_forward_extend_ragged reads them.  rot_dim = 0
 // turns the rotation off and H_q = 0 leaves the queries out: together that is the plain ragged append.
 //
-// WORK SPLIT.  fa2_rope_append_kernel's: a row of d elements is d / 8 lanes of 16 bytes, a wave holds 64 / (d / 8) rows per pass
-// and makes kRopePasses passes per unit, all loads of a unit issued before its first store.  A unit is (head j, a group of TPU
-// consecutive PACKED tokens); j < H_kv is a K/V head, the others are Q heads.  j is WAVE-UNIFORM: the branch between the two kinds
-// of head is a scalar one and the descales are scalar loads.  The owning sequence is NOT: a group may straddle several sequences
-// and tokens no sequence owns, so each lane finds its token's owner itself (fa2_rope_ragged_owner.h: a search of ceil(log2 B)
-// steps over the plan's pairs, the count a host value) and loads seqlens_k[b] with a vector load.  The grid depends on host
-// values only and is capped; a wave strides over the rest.  Plain compiler code: no LDS, no atomics, no inline assembly.
-// THE PLAN IS THE SAFETY CONTRACT.  A header that does not name the call's B and T (and G, with Q heads) ends every wave before
-// its first store.  Ownership comes from ragged_owner and nothing else: whatever the pairs hold, an owner has 0 <= b < B and
-// 0 <= i < q_b <= T, and only the B pairs are read.  A cache destination is formed by fa2_kv_append_addr.h and nothing else; a
-// table row is read only for a position that passed 0 <= pos < capacity (the host has checked capacity <= n_positions); a Q_out
-// row is a function of (t, head) alone, t < T.  No loop bound comes from device memory.
-// ROTATION.  fa2_rope_rotate.h, the uniform call's, so a row's bits are that call's.
-#include "fa2_common.h"
-#include "fa2_kv_append_addr.h"
-#include "fa2_kv_quantise.h"
-#include "fa2_launch.h"
+// The unit loop, its work split and the argument checks live in fa2_rope_ragged_unit.h, which this file instantiates WITHOUT the
+// per-head RMSNorm (fa2_norm_rope_append_ragged.hip instantiates it with): plain compiler code, no LDS, no atomics, no inline
+// assembly.  THE PLAN IS THE SAFETY CONTRACT, ownership comes from fa2_rope_ragged_owner.h and cache addresses from
+// fa2_kv_append_addr.h alone, and the rotation is fa2_rope_rotate.h, the uniform call's, so a row's bits are that call's.
 #include "fa2_rope_ragged_mi355x.h"
-#include "fa2_rope_ragged_owner.h"
-#include "fa2_rope_rotate.h"
-
-#include <algorithm>
+#include "fa2_rope_ragged_unit.h"
 
 namespace fa2 {
 
 namespace {
 
-constexpr int kRopePasses = 2;           // rows of a lane per unit: both passes' loads are issued before the first store
-constexpr int kRopeMaxBlocks = 2048;     // 256 CUs x 8 workgroups of 4 waves: a memory-bound grid is capped and strides
-// what a wave reads once per unit, at a wave-uniform address: the constant address space makes these scalar loads
-typedef __attribute__((address_space(4))) int rope_const_int;
-typedef __attribute__((address_space(4))) float rope_const_float;
-
-struct RopeRaggedArgs {
-    const void* Q; void* Qout; const void* Knew; const void* Vnew; void* K; void* V;
-    const float* cos; const float* sin;
-    const int* plan; const int* seqlens; const int* block_table; const float* k_descale; const float* v_descale;
-    int B, Hq, Hkv, T, Ncap;                     // Ncap: kv_capacity, or max_pages x page_size
-    int n_pages, page_size, max_pages;           // paged only
-    int half;                                    // rot_dim / 2: the tables' row length, a multiple of 8; 0: no rotation
-    int iters;                                   // the owner search's steps: ragged_owner_iters(B)
-    unsigned groups, units;                      // token groups of a head; (H_kv + H_q) x groups (rope_ragged_launch)
-    long long qt, qh;                            // Q's element strides: token, head
-    long long st, sh;                            // K_new's and V_new's
-};
-
 template <int D, bool FP8, bool PAGED, bool INTERLEAVED>
 __global__ __launch_bounds__(256) void fa2_rope_append_ragged_kernel(const RopeRaggedArgs a)
 {
-    constexpr int LPR = D / 8;                  // lanes of a row
-    constexpr int ROWS = 64 / LPR;              // rows of a wave's pass
-    constexpr int TPU = ROWS * kRopePasses;     // tokens of a unit
-    // the plan is the contract: a header built for another batch ends the wave before it touches anything
-    const rope_const_int* const head = (const rope_const_int*)a.plan;
-    if (head[0] != a.B || head[2] != a.T) return;
-    if (a.Hq > 0 && head[1] != a.Hq / a.Hkv) return;
-    const int* const pseq = a.plan + kRaggedPlanHeader;      // B pairs (start_b, q_b): the host checked plan_bytes
-    const int lane = threadIdx.x & 63;
-    const int r = lane / LPR, c = lane % LPR;
-    const bool rotates = 4 * c < a.half;        // this lane's chunk lies inside rot_dim (8 c < rot_dim)
-    const bool first = 8 * c < a.half;          // rotate-half: inside the first half, the x1 of its pairs
-    // the lane's eight table columns (rotate-half) or four (interleaved), and its partner's chunk
-    const int col = INTERLEAVED ? 4 * c : (first ? 8 * c : 8 * c - a.half);
-    const int partner = first ? a.half : -a.half;
-    // host values: (H_kv + H_q) x T is below 2^31 (rope_ragged_check) and the grid is capped, so u + step stays below 2^32
-    const unsigned groups = a.groups, units = a.units;
-    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-    const unsigned step = gridDim.x * 4u;
-    for (unsigned u = wave; u < units; u += step) {
-        const int g = (int)(u % groups), j = (int)(u / groups);
-        const bool is_q = j >= a.Hkv;                                                // wave-uniform
-        const int h = is_q ? j - a.Hkv : j;
-        float kd = 1.0f, vd = 1.0f;
-        if constexpr (FP8) {
-            if (!is_q) {
-                if (a.k_descale) kd = ((const rope_const_float*)a.k_descale)[h];
-                if (a.v_descale) vd = ((const rope_const_float*)a.v_descale)[h];
-            }
-        }
-        const __bf16* xsrc = (const __bf16*)(is_q ? a.Q : a.Knew);
-        const long long row0 = (long long)h * (is_q ? a.qh : a.sh);
-        const long long tstride = is_q ? a.qt : a.st;
-        long long dst[kRopePasses];               // where the row goes (a cache, or Q_out), or dropped
-        bool live[kRopePasses];                   // its position has a table row: it was loaded and is rotated
-        u32x4 x[kRopePasses], xp[kRopePasses], v[kRopePasses];
-        f32x4 c0[kRopePasses], c1[kRopePasses], s0[kRopePasses], s1[kRopePasses];
-#pragma unroll
-        for (int p = 0; p < kRopePasses; ++p) {
-            const unsigned t = (unsigned)g * TPU + p * ROWS + r;      // unsigned: the last group may pass T, up to INT_MAX, by TPU - 1
-            const bool in = t < (unsigned)a.T;
-            int pos = -1, b = 0;
-            if (in) {
-                const RaggedOwner own = ragged_owner(pseq, a.B, a.iters, a.T, (int)t);
-                if (own.b >= 0) {
-                    b = own.b;
-                    pos = kv_append_pos(a.seqlens[own.b], own.q, own.i, a.Ncap);
-                }
-            }
-            long long to = kKvAppendDropped;
-            if (is_q) {
-                if (in) to = ((long long)t * a.Hq + h) * D;      // every row of Q_out is written
-            } else if constexpr (PAGED) {
-                if (pos >= 0) {
-                    const int entry = a.block_table[(long long)b * a.max_pages + kv_append_table_index(pos, a.page_size)];
-                    to = kv_append_offset_paged(pos, entry, a.n_pages, h, a.Hkv, a.page_size, D);
-                }
-            } else {
-                to = kv_append_offset(pos, b, h, a.Hkv, a.Ncap, D);      // dropped for pos = -1
-            }
-            dst[p] = to;
-            live[p] = to >= 0 && pos >= 0;
-            const long long src = row0 + (long long)t * tstride + 8 * c;
-            if (live[p]) {
-                x[p] = *reinterpret_cast<const u32x4*>(xsrc + src);
-                if (!is_q) v[p] = *reinterpret_cast<const u32x4*>((const __bf16*)a.Vnew + src);      // K_new's strides are V_new's
-            }
-            if (live[p] && rotates) {
-                const long long at = (long long)pos * a.half + col;      // pos < capacity <= n_positions (host-checked)
-                c0[p] = *reinterpret_cast<const f32x4*>(a.cos + at);
-                s0[p] = *reinterpret_cast<const f32x4*>(a.sin + at);
-                if constexpr (!INTERLEAVED) {
-                    c1[p] = *reinterpret_cast<const f32x4*>(a.cos + at + 4);
-                    s1[p] = *reinterpret_cast<const f32x4*>(a.sin + at + 4);
-                    xp[p] = *reinterpret_cast<const u32x4*>(xsrc + src + partner);
-                }
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < kRopePasses; ++p) {
-            if (dst[p] < 0) continue;
-            u32x4 y = u32x4{0u, 0u, 0u, 0u};      // a Q row no sequence owns, or whose position has no table row: +0.0 throughout
-            if (live[p]) {
-                y = x[p];                          // past rot_dim: the source bits
-                if (rotates) {
-                    if constexpr (INTERLEAVED) {
-                        y = rope_rotate_pairs8(x[p], c0[p], s0[p]);
-                    } else {
-                        const uint32_t sign = first ? 0x80008000u : 0u;
-                        const u32x4 q = u32x4{xp[p][0] ^ sign, xp[p][1] ^ sign, xp[p][2] ^ sign, xp[p][3] ^ sign};
-                        y = rope_rotate_half8(x[p], q, c0[p], c1[p], s0[p], s1[p]);
-                    }
-                }
-            }
-            const long long at = dst[p] + 8 * c;
-            if (is_q) {
-                *reinterpret_cast<u32x4*>((__bf16*)a.Qout + at) = y;
-            } else if constexpr (FP8) {
-                *reinterpret_cast<u32x2*>((uint8_t*)a.K + at) = kv_quantise8(y, kd);
-                *reinterpret_cast<u32x2*>((uint8_t*)a.V + at) = kv_quantise8(v[p], vd);
-            } else {
-                *reinterpret_cast<u32x4*>((__bf16*)a.K + at) = y;
-                *reinterpret_cast<u32x4*>((__bf16*)a.V + at) = v[p];
-            }
-        }
-    }
+    rope_ragged_units<D, FP8, PAGED, INTERLEAVED, false>(a);
 }
 
 template <int D, bool FP8, bool PAGED, bool INTERLEAVED>
-hipError_t rope_ragged_launch(RopeRaggedArgs a, hipStream_t stream)
+hipError_t rope_ragged_launch(const RopeRaggedArgs& a, hipStream_t stream)
 {
-    constexpr int TPU = 64 / (D / 8) * kRopePasses;
-    a.groups = (unsigned)(((long long)a.T + TPU - 1) / TPU);
-    const long long units = (long long)(a.Hkv + a.Hq) * a.groups;
-    a.units = (unsigned)units;
-    a.iters = ragged_owner_iters(a.B);
-    const unsigned grid = (unsigned)std::min<long long>((units + 3) / 4, kRopeMaxBlocks);
-    hipLaunchKernelGGL((fa2_rope_append_ragged_kernel<D, FP8, PAGED, INTERLEAVED>), dim3(grid), dim3(256), 0, stream, a);
-    return hipGetLastError();
+    return rope_ragged_launch_units<D>(a, fa2_rope_append_ragged_kernel<D, FP8, PAGED, INTERLEAVED>, stream);
 }
 
 template <int D, bool PAGED>
@@ -187,44 +40,6 @@ hipError_t rope_ragged_dispatch(const RopeRaggedArgs& a, int d, bool fp8, bool i
     if (d == 128) return rope_ragged_pick<128, PAGED>(a, fp8, interleaved, stream);
     if (d == 64) return rope_ragged_pick<64, PAGED>(a, fp8, interleaved, stream);
     return hipErrorInvalidValue;
-}
-
-inline int rope_ragged_hip_status(hipError_t e) { return e == hipSuccess ? FA2_OK : FA2_ERR_HIP_BASE - (int)e; }
-
-inline bool rope_ragged_misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
-
-inline bool rope_ragged_bad_stride(long long s) { return s < 0 || s % 8 != 0; }
-
-// Everything both entry points check after their NULL pointers and their own capacity rules, in the header's order; capacity is
-// kv_capacity or max_pages_per_seq x page_size.  The plan comes last, as the ragged extend's does.
-int rope_ragged_check(const RopeRaggedArgs& a, long long capacity, int head_dim, int rot_dim, int n_positions, int interleaved, int dtype,
-                      int kv_dtype, size_t plan_bytes)
-{
-    if (rot_dim != 0 && (rot_dim < 16 || rot_dim % 16 || rot_dim > head_dim)) return FA2_ERR_INVALID_SHAPE;
-    if (rot_dim != 0 && n_positions < capacity) return FA2_ERR_INVALID_SHAPE;
-    if (interleaved != 0 && interleaved != 1) return FA2_ERR_INVALID_SHAPE;
-    if (((long long)a.Hq + a.Hkv) * a.T > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;      // the units are counted in 32 bits
-    if (rope_ragged_bad_stride(a.qt) || rope_ragged_bad_stride(a.qh)) return FA2_ERR_INVALID_SHAPE;
-    if (rope_ragged_bad_stride(a.st) || rope_ragged_bad_stride(a.sh)) return FA2_ERR_INVALID_SHAPE;
-    if (rope_ragged_misaligned(a.Q) || rope_ragged_misaligned(a.Qout) || rope_ragged_misaligned(a.Knew) || rope_ragged_misaligned(a.Vnew) ||
-        rope_ragged_misaligned(a.K) || rope_ragged_misaligned(a.V) || rope_ragged_misaligned(a.cos) || rope_ragged_misaligned(a.sin))
-        return FA2_ERR_INVALID_SHAPE;
-    if (head_dim != 64 && head_dim != 128) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
-    if (dtype != FA2_DTYPE_BF16) return FA2_ERR_UNSUPPORTED_DTYPE;
-    if (kv_dtype != FA2_DTYPE_BF16 && kv_dtype != FA2_DTYPE_FP8_E4M3) return FA2_ERR_UNSUPPORTED_DTYPE;
-    if (kv_dtype == FA2_DTYPE_BF16 && (a.k_descale || a.v_descale)) return FA2_ERR_UNSUPPORTED;
-    if (plan_bytes < (kRaggedPlanHeader + 2 * (size_t)a.B) * sizeof(int) || rope_ragged_misaligned(a.plan)) return FA2_ERR_WORKSPACE;
-    return FA2_OK;
-}
-
-// The pointers of both entry points: the tables are needed by a rotation only, Q and Q_out come as a pair, and only a call
-// without Q heads may leave them out.
-inline bool rope_ragged_null(const void* Q, const void* Q_out, int H_q, const void* K_new, const void* V_new, const void* K, const void* V,
-                             const float* cos_table, const float* sin_table, int rot_dim, const void* plan, const int* seqlens_k)
-{
-    if (!K_new || !V_new || !K || !V || !seqlens_k || !plan) return true;
-    if (rot_dim != 0 && (!cos_table || !sin_table)) return true;
-    return (!Q != !Q_out) || (!Q && H_q != 0);
 }
 
 }  // namespace
@@ -243,9 +58,7 @@ int fa2_rope_kv_append_ragged(const void* Q, void* Q_out, const void* K_new, con
 {
     if (fa2::rope_ragged_null(Q, Q_out, H_q, K_new, V_new, K_cache, V_cache, cos_table, sin_table, rot_dim, plan, seqlens_k))
         return FA2_ERR_NULL_POINTER;
-    if (B <= 0 || H_kv <= 0 || total_q <= 0 || kv_capacity <= 0 || head_dim <= 0 || H_q < 0 || H_q % H_kv) return FA2_ERR_INVALID_SHAPE;
-    // the decode calls' (b, head) slab limit: 2 bytes per element, 1 in an e4m3 cache
-    if ((long long)kv_capacity * head_dim * (kv_dtype == FA2_DTYPE_FP8_E4M3 ? 1 : 2) > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;
+    if (fa2::rope_ragged_bad_contiguous(B, H_q, H_kv, total_q, kv_capacity, head_dim, kv_dtype)) return FA2_ERR_INVALID_SHAPE;
     fa2::RopeRaggedArgs a{};
     a.Q = Q; a.Qout = Q_out; a.Knew = K_new; a.Vnew = V_new; a.K = K_cache; a.V = V_cache;
     a.cos = rot_dim ? cos_table : nullptr; a.sin = rot_dim ? sin_table : nullptr;
@@ -270,12 +83,7 @@ int fa2_rope_kv_append_ragged_paged(const void* Q, void* Q_out, const void* K_ne
 {
     if (fa2::rope_ragged_null(Q, Q_out, H_q, K_new, V_new, K_pages, V_pages, cos_table, sin_table, rot_dim, plan, seqlens_k) || !block_table)
         return FA2_ERR_NULL_POINTER;
-    if (B <= 0 || H_kv <= 0 || total_q <= 0 || n_pages <= 0 || page_size <= 0 || max_pages_per_seq <= 0 || head_dim <= 0 || H_q < 0 ||
-        H_q % H_kv)
-        return FA2_ERR_INVALID_SHAPE;
-    if (page_size % fa2::kDecodeTile) return FA2_ERR_INVALID_SHAPE;
-    // the paged decode's capacity limit: what this call writes, that call must be able to read
-    if ((long long)max_pages_per_seq * page_size > 0x7fffffffLL - (fa2::kDecodeMaxSplits + 2) * fa2::kDecodeKB) return FA2_ERR_INVALID_SHAPE;
+    if (fa2::rope_ragged_bad_paged(B, H_q, H_kv, total_q, n_pages, page_size, max_pages_per_seq, head_dim)) return FA2_ERR_INVALID_SHAPE;
     fa2::RopeRaggedArgs a{};
     a.Q = Q; a.Qout = Q_out; a.Knew = K_new; a.Vnew = V_new; a.K = K_pages; a.V = V_pages;
     a.cos = rot_dim ? cos_table : nullptr; a.sin = rot_dim ? sin_table : nullptr;

@@ -1244,10 +1244,35 @@ def _ragged_rows_arg(x, name, H_name, how):
     return x.shape[1], strides
 
 
+def _f32(x):
+    """x rounded to float32, as a Python float (inf where it overflows)."""
+    try:
+        with np.errstate(over="ignore"):
+            return float(np.float32(float(x)))
+    except OverflowError:      # an int too large for a double
+        return math.inf
+
+
+def _norm_weight_arg(w, name, d):
+    """A weight of the per-head RMSNorm: an fp32 [d] contiguous tensor, 16-byte aligned -- a lane loads its eight in two 16-byte
+    loads.  (Its device is checked with the other tensors'.)"""
+    if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.shape[0] != d:
+        raise ValueError(f"{name}: expected a 1-d tensor [{d}] (one weight per element of head_dim), got "
+                         f"{tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
+    if w.dtype != torch.float32:
+        raise ValueError(f"{name}: dtype {w.dtype}, expected torch.float32 (convert a checkpoint's bf16 weight, and fold Gemma's "
+                         "1 + w, once: the caller builds the weights as it builds cos and sin)")
+    if not w.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (got stride {tuple(w.stride())}; call .contiguous())")
+    if w.storage_offset() % 4:
+        raise ValueError(f"{name}: storage offset {w.storage_offset()} elements is not 16-byte aligned (a multiple of 4): a lane loads 16 bytes")
+
+
 def _rope_ragged_call(Q, K_new, V_new, K, V, block_table, cos, sin, cu_or_plan, seqlens_k, interleaved, k_descale, v_descale, Q_out,
-                      stream):
-    """rope_kv_cache_append_ragged (block_table None) and _paged, kv_cache_append_ragged (cos, sin, Q None) and _paged: one set of
-    checks for the four, the uniform calls' in their order.  Nothing here reads a device value."""
+                      stream, norm=None):
+    """rope_kv_cache_append_ragged (block_table None) and _paged, kv_cache_append_ragged (cos, sin, Q None) and _paged, and
+    norm_rope_kv_cache_append_ragged (norm = (q_weight, k_weight, eps)) and _paged: one set of checks for the six, the uniform
+    calls' in their order.  Nothing here reads a device value."""
     paged = block_table is not None
     kname, vname = ("K_pages", "V_pages") if paged else ("K_cache", "V_cache")
     want = "[n_pages, H_kv, page_size, d]" if paged else "[B, H_kv, N_cap, d]"
@@ -1292,6 +1317,16 @@ def _rope_ragged_call(Q, K_new, V_new, K, V, block_table, cos, sin, cu_or_plan, 
     if cos is not None:
         _rope_tables_arg(cos, sin, d, 0)
     flag = _rope_interleaved(interleaved)
+    if norm is not None:
+        q_weight, k_weight, eps = norm
+        if Q is not None:
+            _norm_weight_arg(q_weight, "q_weight", d)
+        elif q_weight is not None:
+            raise ValueError("q_weight: given without Q (a K/V-only call normalises K alone)")
+        _norm_weight_arg(k_weight, "k_weight", d)
+        # as the kernel gets it: a C float (1e-46 is 0.0f there and 1e39 is inf)
+        if isinstance(eps, bool) or not isinstance(eps, (int, float, np.floating)) or not math.isfinite(_f32(eps)) or _f32(eps) <= 0:
+            raise ValueError(f"eps: {eps!r}, expected a finite float > 0 (as a float32)")
     G = Hq // Hkv if Hq else 1      # a K/V-only call takes a plan of any G; one built here is built for G = 1
     if isinstance(cu_or_plan, ExtendRaggedPlan):
         plan = cu_or_plan
@@ -1331,6 +1366,10 @@ def _rope_ragged_call(Q, K_new, V_new, K, V, block_table, cos, sin, cu_or_plan, 
             raise ValueError(f"{n} must be contiguous (got stride {tuple(t.stride())}; call .contiguous())")
         if t.data_ptr() % 16:
             raise ValueError(f"{n}: not 16-byte aligned (storage offset {t.storage_offset()} elements): a lane loads 16 bytes")
+    if norm is not None:
+        for n, t in (("q_weight", q_weight), ("k_weight", k_weight)):
+            if t is not None and (not t.is_cuda or t.device != K_new.device):
+                raise ValueError(f"{n} is on {t.device}, expected {K_new.device}: the kernel reads the weights on the device when it runs")
     if Q is None:
         pass
     elif Q_out is None:
@@ -1349,12 +1388,14 @@ def _rope_ragged_call(Q, K_new, V_new, K, V, block_table, cos, sin, cu_or_plan, 
     mid = (_ptr(cos), _ptr(sin), plan.tensor.data_ptr(), _nbytes(plan.tensor), seqlens_k.data_ptr(), _ptr(k_descale), _ptr(v_descale))
     tail = (d, rot_dim, n_positions, flag, *q_strides, *strides, FA2_DTYPE_BF16, FA2_DTYPE_FP8_E4M3 if fp8 else FA2_DTYPE_BF16,
             _stream_ptr(stream))
+    if norm is not None:
+        mid = mid[:2] + (_ptr(q_weight), k_weight.data_ptr(), float(eps)) + mid[2:]
+    name = ("fa2_norm_rope_kv_append_ragged" if norm is not None else "fa2_rope_kv_append_ragged") + ("_paged" if paged else "")
     if paged:
-        st = lib.fa2_rope_kv_append_ragged_paged(*head, block_table.data_ptr(), *mid, B, Hq, Hkv, T, n0, n2, max_pages, *tail)
-        check(st, "fa2_rope_kv_append_ragged_paged")
+        st = getattr(lib, name)(*head, block_table.data_ptr(), *mid, B, Hq, Hkv, T, n0, n2, max_pages, *tail)
     else:
-        st = lib.fa2_rope_kv_append_ragged(*head, *mid, B, Hq, Hkv, T, capacity, *tail)
-        check(st, "fa2_rope_kv_append_ragged")
+        st = getattr(lib, name)(*head, *mid, B, Hq, Hkv, T, capacity, *tail)
+    check(st, name)
     return Q_out
 
 
@@ -1393,6 +1434,39 @@ def rope_kv_cache_append_ragged_paged(Q, K_new, V_new, K_pages, V_pages, block_t
         raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
     return _rope_ragged_call(Q, K_new, V_new, K_pages, V_pages, block_table, cos, sin, cu_seqlens_q_or_plan, seqlens_k, interleaved,
                              k_descale, v_descale, Q_out, stream)
+
+
+def norm_rope_kv_cache_append_ragged(Q, K_new, V_new, K_cache, V_cache, cos, sin, q_weight, k_weight, eps, cu_seqlens_q_or_plan,
+                                     seqlens_k, *, interleaved=False, k_descale=None, v_descale=None, Q_out=None, stream=None):
+    """rope_kv_cache_append_ragged with a PER-HEAD RMSNorm of every new Q row and K row in front of the rotation
+    (fa2_norm_rope_kv_append_ragged, include/fa2_rope_norm_mi355x.h): the cache-writing half of a step for models that normalise
+    queries and keys over head_dim before they rotate them (Qwen3, Gemma 3).  ONE launch; the Q, K and V slices of the fused
+    projection output go in as they are, no framework norm and no normalised copy in between.  Every argument but three is
+    rope_kv_cache_append_ragged's, with its rules, its Q_out (every row written, +0.0 throughout for dropped and un-owned
+    tokens), its plan contract and its write-or-drop rule; V is copied untouched.
+    q_weight, k_weight: fp32 [d] contiguous DEVICE tensors, read on the device; q_weight is None exactly when Q is None.  The caller
+    builds them as it builds cos and sin: Gemma's 1 + w and a checkpoint's bf16 weight are folded or converted once.  eps: a
+    finite float > 0.
+    ARITHMETIC, all fp32 with one rounding per operation and no fused multiply-add: the squares are summed in a fixed order
+    (eight per 16-byte chunk left to right, then a butterfly over the row's chunks), r = 1 / sqrt(sum / d + eps) with a correctly
+    rounded sqrt and division, n = ((x * r) * w).bfloat16() -- ONE rounding to bf16, Gemma 3's form; HF Qwen3's extra bf16 rounding
+    before the weight is a different, less exact expression and is not reproduced.  The call is bit for bit
+    rope_kv_cache_append_ragged applied to the normalised bf16 tensors; cos = sin = None stores n itself."""
+    return _rope_ragged_call(Q, K_new, V_new, K_cache, V_cache, None, cos, sin, cu_seqlens_q_or_plan, seqlens_k, interleaved, k_descale,
+                             v_descale, Q_out, stream, norm=(q_weight, k_weight, eps))
+
+
+def norm_rope_kv_cache_append_ragged_paged(Q, K_new, V_new, K_pages, V_pages, block_table, cos, sin, q_weight, k_weight, eps,
+                                           cu_seqlens_q_or_plan, seqlens_k, *, interleaved=False, k_descale=None, v_descale=None,
+                                           Q_out=None, stream=None):
+    """norm_rope_kv_cache_append_ragged into a pool of pages (fa2_norm_rope_kv_append_ragged_paged): K_pages, V_pages, block_table
+    and the drop rule exactly as rope_kv_cache_append_ragged_paged takes them.  A token whose table entry lies outside
+    [0, n_pages) has its K and V DROPPED; its Q_out row is still the normalised, rotated query.  PAGES WRITTEN BY ONE CALL MUST
+    BELONG TO ONE SEQUENCE EACH."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
+    return _rope_ragged_call(Q, K_new, V_new, K_pages, V_pages, block_table, cos, sin, cu_seqlens_q_or_plan, seqlens_k, interleaved,
+                             k_descale, v_descale, Q_out, stream, norm=(q_weight, k_weight, eps))
 
 
 def kv_cache_append_ragged(K_new, V_new, K_cache, V_cache, cu_seqlens_q_or_plan, seqlens_k, k_descale=None, v_descale=None, stream=None):

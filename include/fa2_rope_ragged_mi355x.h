@@ -55,7 +55,8 @@
  * beside a bf16 cache -> FA2_ERR_UNSUPPORTED; plan_bytes below (8 + 2 B) x 4 or a plan that is not 16-byte aligned ->
  * FA2_ERR_WORKSPACE.
  * NOT COVERED: explicit position_ids, tree masks for speculative decoding, token-major pools, per-token scales, a backward,
- * reordering the work items, and what the siblings leave out.
+ * reordering the work items, a norm of the rows (a per-head RMSNorm of Q and K in front of the rotation is
+ * fa2_norm_rope_kv_append_ragged, fa2_rope_norm_mi355x.h), and what the siblings leave out.
  */
 #ifndef FA2_ROPE_RAGGED_MI355X_H
 #define FA2_ROPE_RAGGED_MI355X_H
