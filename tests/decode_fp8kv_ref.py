@@ -9,7 +9,7 @@ quantise(X): the descale of head h is amax_h / 448 (448: the largest e4m3 value)
 +-448 -- torch's cast does not saturate -- and cast.  dequantise: X8.float() * descale, in fp32.
 
 REFERENCE AND GATES.  decode_paged_ref.reference64 and decode_ref.emulate ON THE DEQUANTISED TENSORS, gated by decode_ref's own
-gates (within_gates): quantisation error is the caller's choice of format and no part of any gate -- what is gated is what the
+gates (within_gates) and the row gate of O of tests/decode_rows_ref.py on the same tensors: quantisation error is the caller's choice of format and no part of any gate -- what is gated is what the
 kernels do with the values the cache holds."""
 import functools
 

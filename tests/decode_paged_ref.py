@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 import decode_ref as dr
+import decode_rows_ref as rows
 import regimes
 from sink_ref import ref_attention_sink
 
@@ -101,7 +102,8 @@ def paged_inputs(i, page_size, fill="nan", zero_unused=False):
 
 
 def reference64(Q, K, V, lens, scale, causal, sink):
-    """float64 O [B, hq, nq, d] and L [B, hq, nq] on contiguous host caches: decode_ref.reference's rule for any batch."""
+    """float64 O [B, hq, nq, d] and L [B, hq, nq] on contiguous host caches: decode_ref.reference's rule for any batch, with the
+    row gate's .quad beside them (decode_rows_ref.Ref)."""
     G = Q.shape[1] // K.shape[1]
     O, L = np.zeros(tuple(Q.shape)), np.zeros(tuple(Q.shape[:3]))
     for b, n in enumerate(lens):
@@ -111,7 +113,7 @@ def reference64(Q, K, V, lens, scale, causal, sink):
             O[b], L[b] = regimes.ref_attention(q, k, v, np.zeros_like(q), scale, causal)[:2]
         else:
             O[b], L[b] = ref_attention_sink(q, k, v, np.zeros_like(q), scale, causal, sink.double().numpy())[:2]
-    return O, L
+    return rows.Ref(O, L, rows.quad64(Q, K, V, lens, scale, causal, sink))
 
 
 @functools.lru_cache(maxsize=None)

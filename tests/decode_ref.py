@@ -16,13 +16,16 @@ leaves a normalised fp32 O_s and L_s; the combine folds them in ascending order 
 It follows the kernels' order of operations, not their bits (a NumPy fp32 product sums in another order than an MFMA).
 
 GATES: the project's bf16 ones (tests/test_gpu_qk.py): O rel-L2 <= 5e-3 over the whole tensor; max |dL| <= 1e-4 over rows with a
-finite reference L of magnitude <= 25, <= 1e-3 above; the rows with L = -inf are exactly the reference's and O is exactly 0 there."""
+finite reference L of magnitude <= 25, <= 1e-3 above; the rows with L = -inf are exactly the reference's and O is exactly 0 there.
+The tensor gate alone lets a fault on the long sequences' P V side pass (they hold 0.1 % of the norm): O is also gated PER ROW by
+tests/decode_rows_ref.py, whose quadrature term reference() carries beside (O, L)."""
 import functools
 import itertools
 
 import numpy as np
 import torch
 
+import decode_rows_ref as rows
 import regimes
 from sink_ref import ref_attention_sink
 
@@ -100,7 +103,7 @@ def inputs(i):
 
 @functools.lru_cache(maxsize=None)
 def reference(i):
-    """float64 O [B, hq, nq, d] and L [B, hq, nq] of CASES[i]."""
+    """float64 O [B, hq, nq, d] and L [B, hq, nq] of CASES[i], with the row gate's .quad beside them (decode_rows_ref.Ref)."""
     c = CASES[i]
     Q, K, V, scale, lens, sink = inputs(i)
     G = c["hq"] // c["hkv"]
@@ -112,7 +115,7 @@ def reference(i):
             O[b], L[b] = regimes.ref_attention(q, k, v, np.zeros_like(q), scale, c["causal"])[:2]
         else:
             O[b], L[b] = ref_attention_sink(q, k, v, np.zeros_like(q), scale, c["causal"], sink.double().numpy())[:2]
-    return O, L
+    return rows.Ref(O, L, rows.quad64(Q, K, V, c["lens"], scale, c["causal"], sink))
 
 
 def split_range(n, n_splits, s):
@@ -227,7 +230,7 @@ MIN_SPLIT_KEYS = 256      # kDecodeMinSplitKeys
 
 def errors(O, L, ref):
     """(O rel-L2, max |dL| where |L_ref| <= 25, max |dL| above, whether the -inf rows are the reference's and O is 0 on them)."""
-    rO, rL = ref
+    rO, rL = ref[:2]
     O, L = np.asarray(O, dtype=np.float64), np.asarray(L, dtype=np.float64)
     none = np.isneginf(rL)
     same = bool(np.array_equal(np.isneginf(L), none) and np.isfinite(L[~none]).all() and np.isfinite(O).all() and (O[none] == 0).all())

@@ -18,7 +18,7 @@ V rows below lo_b zeroed: it never multiplies what lies there).  With kmin = 0 i
 (tests/test_decode_window_reference.py asserts it), and the combine and the sink step are decode_ref's own code paths, copied
 where they are not functions.
 
-GATES: decode_ref.errors / within_gates, unchanged."""
+GATES: decode_ref.errors / within_gates, unchanged, and the row gate of O of tests/decode_rows_ref.py (reference64 carries its term)."""
 import functools
 import itertools
 
@@ -28,6 +28,7 @@ import torch
 import decode_fp8kv_ref as fr
 import decode_paged_ref as pr
 import decode_ref as dr
+import decode_rows_ref as rows
 import regimes
 
 KB, TILE, WAVES = dr.KB, dr.TILE, dr.WAVES
@@ -105,7 +106,8 @@ def dequantised(i):
 
 def reference64(Q, K, V, lens, scale, sink, wl):
     """float64 O [B, hq, nq, d] and L [B, hq, nq] on contiguous host caches under the causal mask with the window; wl = None: no
-    window.  Written out here, not through regimes.ref_attention: that function has no lower bound."""
+    window.  Written out here, not through regimes.ref_attention: that function has no lower bound.  With the row gate's .quad
+    (decode_rows_ref.Ref)."""
     B, hq, nq, d = Q.shape
     G = hq // K.shape[1]
     O, L = np.zeros((B, hq, nq, d)), np.zeros((B, hq, nq))
@@ -132,7 +134,7 @@ def reference64(Q, K, V, lens, scale, sink, wl):
                 Ob = Ob * np.where(np.isneginf(sk), 1.0, np.where(seen, np.exp(Lb - Ln), 0.0))[..., None]
                 Lb = Ln
             O[b], L[b] = Ob, Lb
-    return O, L
+    return rows.Ref(O, L, rows.quad64(Q, K, V, lens, scale, True, sink, wl))
 
 
 @functools.lru_cache(maxsize=None)

@@ -18,7 +18,8 @@ causal mask, no mask, the causal mask with each window); the sink alternates ove
 their first 192 keys, so their first pages can be shared in a pool.
 
 REFERENCE: per sequence, extend_ref.reference64 (decode_paged_ref.reference64 / decode_window_ref.reference64) on the transposed
-slice [1, H_q, q_b, d].  GATES: decode_ref.errors / within_gates, unchanged, over all T H_q rows at once."""
+slice [1, H_q, q_b, d].  GATES: decode_ref.errors / within_gates, unchanged, over all T H_q rows at once, and the row gate of O of
+tests/decode_rows_ref.py on each of them."""
 import functools
 
 import numpy as np
@@ -27,6 +28,7 @@ import torch
 import decode_fp8kv_ref as fr
 import decode_paged_ref as pr
 import decode_ref as dr
+import decode_rows_ref as rows
 import extend_ref as er
 
 ROWS, KB, TILE, WAVES = er.ROWS, er.KB, er.TILE, er.WAVES
@@ -117,17 +119,18 @@ def dequantised(i):
 
 def reference64(Q, K, V, qs, lens, scale, causal, sink, wl):
     """float64 O [T, hq, d] and L [T, hq] of a packed batch on contiguous host caches: extend_ref.reference64 per sequence on the
-    transposed slice; tokens past the last sequence (T > sum q_b) stay NaN -- no sequence owns them."""
+    transposed slice; tokens past the last sequence (T > sum q_b) stay NaN -- no sequence owns them.  The row gate's .quad [T, hq]
+    comes with them (decode_rows_ref.Ref)."""
     T, hq, d = Q.shape
-    O, L = np.full((T, hq, d), np.nan), np.full((T, hq), np.nan)
+    O, L, quad = np.full((T, hq, d), np.nan), np.full((T, hq), np.nan), np.full((T, hq), np.nan)
     t = 0
     for b, q in enumerate(qs):
         if q:
             Qb = Q[t:t + q].transpose(0, 1)[None]
-            Ob, Lb = er.reference64(Qb, K[b:b + 1], V[b:b + 1], [int(lens[b])], scale, causal, sink, wl)
-            O[t:t + q], L[t:t + q] = np.swapaxes(Ob[0], 0, 1), np.swapaxes(Lb[0], 0, 1)
+            rb = er.reference64(Qb, K[b:b + 1], V[b:b + 1], [int(lens[b])], scale, causal, sink, wl)
+            O[t:t + q], L[t:t + q], quad[t:t + q] = (np.swapaxes(x[0], 0, 1) for x in (*rb, rb.quad))
         t += q
-    return O, L
+    return rows.Ref(O, L, quad)
 
 
 @functools.lru_cache(maxsize=8)

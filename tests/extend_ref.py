@@ -14,7 +14,8 @@ SHARED in a pool (shared_pages).
 
 REFERENCE (reference64): decode_paged_ref.reference64 -- regimes.ref_attention, sink_ref.ref_attention_sink per sequence -- without
 a window, decode_window_ref.reference64 with one; e4m3 caches through decode_fp8kv_ref's quantise / dequantise.
-GATES: decode_ref.errors / within_gates, unchanged, for bf16 and e4m3 caches alike (as tests/test_gpu_decode_window.py uses them)."""
+GATES: decode_ref.errors / within_gates, unchanged, for bf16 and e4m3 caches alike (as tests/test_gpu_decode_window.py uses them),
+and the row gate of O of tests/decode_rows_ref.py (the references carry its term)."""
 import functools
 
 import torch

@@ -11,7 +11,8 @@ a key); 3 heads on 3, 8 on 2, 8 on 1 (N_q = 4: M = 32 rows) and 32 on 1; both he
 scale-one and low-level regimes of tests/regimes.py at 300 and 1100 keys (a late large key inside a later split, L < -88).
 
 GATES: O rel-L2 <= 5e-3 over the whole tensor; max |dL| <= 1e-4 over rows with finite |L_ref| <= 25, <= 1e-3 above; the rows with
-L = -inf are exactly the reference's, O is exactly 0 on them and on every row without a visible key; no NaN, no Inf."""
+L = -inf are exactly the reference's, O is exactly 0 on them and on every row without a visible key; no NaN, no Inf; and PER ROW |O_i - O_ref,i| <= KAPPA u sqrt(sum_j P_ij^2 |v_j|^2) + u |O_i| (tests/decode_rows_ref.py: the tensor gate
+alone lets a fault on the long sequences' P V side pass), the worst ratio printed with its (sequence, head, token)."""
 import ctypes
 import functools
 
@@ -19,7 +20,9 @@ import numpy as np
 import pytest
 import torch
 
+import decode_paged_ref as pr
 import decode_ref as dr
+import decode_rows_ref as rows
 
 pytestmark = pytest.mark.gpu
 
@@ -41,13 +44,14 @@ def _keyless(c):
     return np.array([[[n == 0 or (c["causal"] and q + n - c["nq"] < 0) for q in range(c["nq"])]] for n in c["lens"]])
 
 
-def _check(where, c, O, L, ref):
+def _check(where, c, O, L, ref, extra=None):
     O, L = O.float().cpu().numpy(), L.cpu().numpy()
     e = dr.errors(O, L, ref)
     print(where, f"O {e[0]:.3e} dL {e[1]:.3e} dL(|L| > 25) {e[2]:.3e} rows {e[3]}")
     assert dr.within_gates(e), (where, e)
     keyless = np.broadcast_to(_keyless(c), L.shape)
     assert (O[keyless] == 0).all(), (where, "O of a row without a key")
+    rows.check(where, O, ref, extra=extra)
 
 
 @pytest.mark.parametrize("i", range(len(dr.CASES)), ids=[dr.case_id(c) for c in dr.CASES])
@@ -187,6 +191,12 @@ def test_a_cache_in_two_allocations_is_two_calls_and_a_merge(d):
     for b, n in enumerate(lens):
         k, v = (np.repeat(t[b, :, :n].double().numpy(), hq // hkv, axis=0) for t in (K, V))
         rO[b], rL[b] = ref_attention_sink(Q[b].double().numpy(), k, v, np.zeros((hq, nq, d)), scale, True, sink.double().numpy())[:2]
+    ref = rows.Ref(rO, rL, rows.quad64(Q, K, V, lens, scale, True, sink))
+    # the two partial O's are rounded to bf16 before the merge weighs them: u (w_a |O_a,i| + w_b |O_b,i|) on top of the row gate,
+    # from the reference partials (the first without the mask and the sink, the last with both) and their weights exp(L_part - L)
+    parts = [pr.reference64(Q, K[:, :, :cut], V[:, :, :cut], [min(n, cut) for n in lens], scale, False, None),
+             pr.reference64(Q, K[:, :, cut:], V[:, :, cut:], [n - cut for n in lens], scale, True, sink)]
+    extra = rows.merged_extra(parts, rL)
     Qd, sd = Q.cuda(), sink.cuda()
     first = (K[:, :, :cut].contiguous().cuda(), V[:, :, :cut].contiguous().cuda())
     last = (K[:, :, cut:].contiguous().cuda(), V[:, :, cut:].contiguous().cuda())
@@ -196,7 +206,7 @@ def test_a_cache_in_two_allocations_is_two_calls_and_a_merge(d):
         a = fa.flash_attention_2_decode(Qd, *first, la, scale, causal=False, n_splits=n_splits)
         b = fa.flash_attention_2_decode(Qd, *last, lb, scale, causal=True, sink=sd, n_splits=n_splits)
         O, L = fa.merge_states_forward([a[0], b[0]], [a[1], b[1]])
-        _check(f"two allocations d{d} splits {n_splits}", c, O, L, (rO, rL))
+        _check(f"two allocations d{d} splits {n_splits}", c, O, L, ref, extra=extra)
 
 
 def test_more_than_32_rows_is_refused_and_writes_nothing():

@@ -4,7 +4,8 @@ per-head descales).
 
 Inputs, references and gates are tests/decode_fp8kv_ref.py's: decode_ref's cases with the caches quantised per K/V head, the
 float64 reference ON THE DEQUANTISED VALUES, decode_ref's own gates (O rel-L2 <= 5e-3; |dL| <= 1e-4 up to |L| = 25, <= 1e-3 above;
-the -inf rows exact).  Quantisation error is in no gate; tests/test_decode_fp8kv_reference.py certifies on the CPU that the
+the -inf rows exact) and, PER ROW, |O_i - O_ref,i| <= KAPPA u sqrt(sum_j P_ij^2 |v_j|^2) + u |O_i| on the dequantised values
+(tests/decode_rows_ref.py; the worst ratio is printed with its (sequence, head, token)).  Quantisation error is in no gate; tests/test_decode_fp8kv_reference.py certifies on the CPU that the
 kernels' data flow on these values stays inside the gates.  Everything else is bit equality: paged against contiguous, garbage
 against zeros, descales against a folded scale, a replayed graph against an eager call, and every e4m3 code against its value."""
 import ctypes
@@ -17,6 +18,7 @@ import torch
 import decode_fp8kv_ref as fr
 import decode_paged_ref as pr
 import decode_ref as dr
+import decode_rows_ref as rows
 
 pytestmark = pytest.mark.gpu
 
@@ -54,6 +56,7 @@ def _check(where, lens, nq, causal, O, L, ref):
     print(where, f"O {e[0]:.3e} dL {e[1]:.3e} dL(|L| > 25) {e[2]:.3e} rows {e[3]}")
     assert dr.within_gates(e), (where, e)
     assert (O[np.broadcast_to(_keyless(lens, nq, causal), L.shape)] == 0).all(), (where, "O of a row without a key")
+    rows.check(where, O, ref)
 
 
 # ---- 1. against the float64 reference on the dequantised caches

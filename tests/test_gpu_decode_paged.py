@@ -4,8 +4,9 @@ N_q, d] against page pools [n_pages, H_kv, page_size, d] and a block table in de
 THE GATE IS BIT EQUALITY with flash_attention_2_decode on the GATHERED contiguous cache of capacity max_pages * page_size and the
 same n_splits: the 32-key tiles, their order and every sum are the same in both kernels, only where a tile's rows are found
 differs, so O and L are compared as integers and need no tolerance.  Beside it decode_ref's gates against the float64 reference
-(tests/test_decode_paged_reference.py certifies on the CPU that the reference alone stays inside them), and O == 0 on every row
-without a visible key.
+(tests/test_decode_paged_reference.py certifies on the CPU that the reference alone stays inside them), O == 0 on every row
+without a visible key, and PER ROW |O_i - O_ref,i| <= KAPPA u sqrt(sum_j P_ij^2 |v_j|^2) + u |O_i| (tests/decode_rows_ref.py; the
+worst ratio is printed with its (sequence, head, token)).
 
 Pools and tables are tests/decode_paged_ref.py's: pages assigned by a seeded permutation, the pool NaN wherever no key was copied
 (the tail of each last page, every spare page), unused table entries -1 and 0x7fffffff.  Page sizes 32, 64, 96, 128, 256; splits 0
@@ -20,6 +21,7 @@ import torch
 
 import decode_paged_ref as pr
 import decode_ref as dr
+import decode_rows_ref as rows
 
 pytestmark = pytest.mark.gpu
 
@@ -62,6 +64,7 @@ def _check(where, lens, nq, causal, O, L, ref):
     print(where, f"O {e[0]:.3e} dL {e[1]:.3e} dL(|L| > 25) {e[2]:.3e} rows {e[3]}")
     assert dr.within_gates(e), (where, e)
     assert (O[np.broadcast_to(_keyless(lens, nq, causal), L.shape)] == 0).all(), (where, "O of a row without a key")
+    rows.check(where, O, ref)
 
 
 # ---- 1. bit for bit against the contiguous kernel

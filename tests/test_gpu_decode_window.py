@@ -5,7 +5,9 @@ Cases, inputs and the float64 reference are tests/decode_window_ref.py's (tests/
 CPU that the reference alone stays inside the gates): N_cap = 1024, heads (8, 2) and (3, 3), d in {64, 128}, q_len in {1, 4},
 window_left in {0, 1, 31, 127, 128, 200}, n_splits in {0, 1, 2, 5}; every case is one batch of the lengths 0, 1, q_len - 1,
 window_left, window_left + 1, window_left + 2, the two that put lo_b at 256 and 257, and 1024.  Gates: decode_ref.within_gates
-against the float64 reference (5e-3 on O rel-L2, 1e-4 / 1e-3 on |dL|), and bit equalities without a tolerance.
+against the float64 reference (5e-3 on O rel-L2, 1e-4 / 1e-3 on |dL|), PER ROW |O_i - O_ref,i| <= KAPPA u sqrt(sum_j P_ij^2 |v_j|^2)
++ u |O_i| (tests/decode_rows_ref.py; the worst ratio is printed with its (sequence, head, token)), and bit equalities without a
+tolerance.
 e4m3 caches carry a distinct descale per head that is no power of two; their reference is the float64 one on the dequantised cache."""
 import ctypes
 import functools
@@ -17,6 +19,7 @@ import torch
 import decode_fp8kv_ref as fr
 import decode_paged_ref as pr
 import decode_ref as dr
+import decode_rows_ref as rows
 import decode_window_ref as wr
 
 pytestmark = pytest.mark.gpu
@@ -70,6 +73,7 @@ def _check(where, lens, nq, O, L, ref):
     print(where, f"O {e[0]:.3e} dL {e[1]:.3e} dL(|L| > 25) {e[2]:.3e} rows {e[3]}")
     assert dr.within_gates(e), (where, e)
     assert (O[np.broadcast_to(_keyless(lens, nq), L.shape)] == 0).all(), (where, "O of a row without a key")
+    rows.check(where, O, ref)
 
 
 def _contiguous(i, fp8, n_splits, wl="case", K=None, V=None, **kw):

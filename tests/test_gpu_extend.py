@@ -6,7 +6,8 @@ eight shapes M = 33 .. 160 at d = 64 and 128, one batch of the lengths 0, 1, q_l
 capacity of 2560 (and seqlens_k = None), n_splits in {0, 1, 2, 7, 64}, the causal mask, no mask, the causal mask under each window
 of (0, 1, 31, 127, 128, 200, capacity - 1), with and without a sink, pages of 32 and 96 keys with shared pages.
 Gates: decode_ref.within_gates against the float64 reference (5e-3 on O rel-L2, 1e-4 / 1e-3 on |dL|, the -inf rows exactly the
-reference's with O exactly 0), and bit equalities without a tolerance."""
+reference's with O exactly 0); PER ROW |O_i - O_ref,i| <= KAPPA u sqrt(sum_j P_ij^2 |v_j|^2) + u |O_i| (tests/decode_rows_ref.py;
+the worst ratio is printed with its (sequence, head, token)); and bit equalities without a tolerance."""
 import functools
 
 import numpy as np
@@ -16,6 +17,7 @@ import torch
 import decode_fp8kv_ref as fr
 import decode_paged_ref as pr
 import decode_ref as dr
+import decode_rows_ref as rows
 import decode_window_ref as wr
 import extend_ref as er
 
@@ -61,9 +63,11 @@ def _same_bits(got, want, where):
 
 
 def _check(where, O, L, ref):
-    e = dr.errors(O.float().cpu().numpy(), L.cpu().numpy(), ref)
+    O = O.float().cpu().numpy()
+    e = dr.errors(O, L.cpu().numpy(), ref)
     print(where, f"O {e[0]:.3e} dL {e[1]:.3e} dL(|L| > 25) {e[2]:.3e} rows {e[3]}")
     assert dr.within_gates(e), (where, e)
+    rows.check(where, O, ref)
 
 
 def _contiguous(i, k, fp8, n_splits, K=None, V=None, wl="variant", **kw):

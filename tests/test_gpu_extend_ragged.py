@@ -5,7 +5,9 @@ Cases, inputs, the float64 reference and the plan's model are tests/extend_ragge
 certifies them on the CPU): mixed, mqa, g1, decode and nolens at d = 64 and 128, n_splits in {0, 1, 2, 7, 64}, the causal mask, no
 mask, the causal mask under each window, with and without a sink, pages of 32 and 96 keys with shared pages.
 Gates: decode_ref.within_gates against the float64 reference (5e-3 on O rel-L2, 1e-4 / 1e-3 on |dL|, the -inf rows exactly the
-reference's with O exactly 0), over every row of a batch at once, and bit equalities without a tolerance."""
+reference's with O exactly 0), over every row of a batch at once; PER ROW |O_i - O_ref,i| <= KAPPA u sqrt(sum_j P_ij^2 |v_j|^2) +
+u |O_i| (tests/decode_rows_ref.py; the worst ratio is printed with its place; the merge of two bf16 partial results gets their
+roundings on top); and bit equalities without a tolerance."""
 import functools
 
 import pytest
@@ -14,6 +16,7 @@ import torch
 import decode_fp8kv_ref as fr
 import decode_paged_ref as pr
 import decode_ref as dr
+import decode_rows_ref as rows
 import extend_ragged_ref as rr
 
 pytestmark = pytest.mark.gpu
@@ -63,10 +66,12 @@ def _same_bits(got, want, where):
     assert torch.equal(got[1].view(torch.int32), want[1].view(torch.int32)), (where, "L")
 
 
-def _check(where, O, L, ref):
-    e = dr.errors(O.float().cpu().numpy(), L.cpu().numpy(), ref)
+def _check(where, O, L, ref, extra=None, cu=None):
+    O = O.float().cpu().numpy()
+    e = dr.errors(O, L.cpu().numpy(), ref)
     print(where, f"O {e[0]:.3e} dL {e[1]:.3e} dL(|L| > 25) {e[2]:.3e} rows {e[3]}")
     assert dr.within_gates(e), (where, e)
+    rows.check(where, O, ref, extra=extra, cu=cu)      # (cu: the place as (sequence, head, token), else as (token, head))
 
 
 def _kw(i, k, fp8):
@@ -96,10 +101,10 @@ def test_parity_with_the_reference(i, k):
         ref = rr.reference(i, k, fp8)
         for n_splits in c["splits"]:
             where = f"{rr.RUN_IDS[rr.RUNS.index((i, k))]} {'e4m3' if fp8 else 'bf16'} splits {n_splits}"
-            _check(where, *_contiguous(i, k, fp8, n_splits), ref)
+            _check(where, *_contiguous(i, k, fp8, n_splits), ref, cu=rr.cu_of(c["qs"]))
             if c["seqlens"]:      # (seqlens_k = None behind pages has the pages' capacity: test 2 ties it to the contiguous call)
                 for P in rr.PAGE_SIZES:
-                    _check(f"{where} page {P}", *_paged(i, k, fp8, P, n_splits), ref)
+                    _check(f"{where} page {P}", *_paged(i, k, fp8, P, n_splits), ref, cu=rr.cu_of(c["qs"]))
 
 
 # ---- 2. bit identity: a sequence's rows are the uniform call's on that sequence alone; n_splits = 0; paged with contiguous
@@ -251,7 +256,7 @@ def test_a_malformed_cu_seqlens_gives_the_sanitised_plan_and_stays_inside(name):
         assert (Oi[~owned] == SENT16).all() and (Li[~owned] == SENT32).all(), (name, n_splits)
         assert not (Oi[owned] == SENT16).any() and not (Li[owned] == SENT32).any(), (name, n_splits)
         if last > first:
-            _check(f"{name} splits {n_splits}", got[0][first:last], got[1][first:last], (ref[0][:last - first], ref[1][:last - first]))
+            _check(f"{name} splits {n_splits}", got[0][first:last], got[1][first:last], ref.head(last - first))
 
 
 # ---- 4. strides: the Q slice of a fused QKV output
@@ -445,6 +450,10 @@ def test_two_calls_over_two_halves_of_the_keys_merge_into_one():
     Qd, Kd, Vd = Q.cuda(), K.cuda(), V.cuda()
     lens = torch.tensor(ls, dtype=torch.int32, device="cuda")
     ref = rr.reference64(Q, K, V, qs, ls, 1.0 / d ** 0.5, True, sink, None)
+    # the two partial O's are rounded to bf16 before the merge weighs them: u (w_a |O_a,i| + w_b |O_b,i|) on top of the row gate
+    parts = [rr.reference64(Q, K[:, :, :h], V[:, :, :h], qs, [h] * B, 1.0 / d ** 0.5, False, None, None),
+             rr.reference64(Q, K[:, :, h:], V[:, :, h:], qs, [n - h for n in ls], 1.0 / d ** 0.5, True, sink, None)]
+    extra = rows.merged_extra(parts, ref[1])
     for n_splits in (1, 2):
         O1, L1 = fa.flash_attention_2_extend_ragged(Qd, Kd[:, :, :h].contiguous(), Vd[:, :, :h].contiguous(), plan, None, causal=False,
                                                     n_splits=n_splits)
@@ -453,4 +462,4 @@ def test_two_calls_over_two_halves_of_the_keys_merge_into_one():
         Om, Lm = fa.merge_states_forward([O1.flatten(0, 1), O2.flatten(0, 1)], [L1.flatten(), L2.flatten()])
         one = fa.flash_attention_2_extend_ragged(Qd, Kd, Vd, plan, lens, sink=sink.cuda(), n_splits=n_splits)
         _check(f"one call splits {n_splits}", *one, ref)
-        _check(f"merged splits {n_splits}", Om.view(T, hq, d), Lm.view(T, hq), ref)
+        _check(f"merged splits {n_splits}", Om.view(T, hq, d), Lm.view(T, hq), ref, extra=extra)
