@@ -60,6 +60,7 @@ import functools
 import numpy as np
 import torch
 
+import lse_ref as LR
 import regimes as R
 
 U = 2.0 ** -9                                 # bf16's unit round-off
@@ -111,17 +112,34 @@ def visible(nq, nk, causal, shift=0):
 # ------------------------------------------------------------------------------------------------ a problem and its gates
 class Case:
     """One sequence: host bf16 Q, dO [hq, nq, d] and K, V [hkv, nk, d] (.t), their float64 values (.q .k .v .g), the reference
-    (.ref: O, L of ref_grouped; dQ, dK, dV of ref_flow fed .O16 and .L32) and the two parts of every row gate."""
+    (.ref: O, L of ref_grouped; dQ, dK, dV of ref_flow fed .O16 and .L32) and the two parts of every row gate.
+    sink (fp32 [hq], -inf = none) and dL (fp32 [hq, nq]), both optional: with either present O and L come
+    from lse_ref.forward(..., sink), the gradients and .dsink from lse_ref.flow fed bf16(O_ref), fp32(L_ref), dL and the sink;
+    P = exp(S - L) with the sink-inclusive L (a row's P sums to less than 1), the row constant is D' = D - dL (dL dropped where
+    L = -inf) and e_ij gains phi P_ij |dL_i|, the one more fp32 operation on the row constant.  A row without a visible key
+    (.keyless): O = 0 and dQ = 0 exactly, L = its head's sink bit for bit (-inf without one).  With both absent every array is
+    what it was without these two arguments."""
 
-    def __init__(self, regime, Q, K, V, dO, s, causal):
+    def __init__(self, regime, Q, K, V, dO, s, causal, sink=None, dL=None):
         self.regime, self.s, self.causal, self.t = regime, s, causal, (Q, K, V, dO)
         self.q, self.k, self.v, self.g = (f64(t) for t in self.t)
         (self.hq, self.nq, self.d), (self.hkv, self.nk, _) = self.q.shape, self.k.shape
         self.G = self.hq // self.hkv
-        O, L, *_ = R.ref_grouped(Q, K, V, dO, s, causal)
-        self.O16, self.L32 = R.kernel_feed(O, L)
-        self.ref = dict(zip(OUTPUTS, (O, L) + tuple(R.ref_flow(Q, K, V, dO, s, causal, self.O16, self.L32))))
+        self.sink, self.dL, self.dsink = sink, dL, None
+        self.shift = self.nk - self.nq if causal else None              # lse_ref's name for the mask
+        if sink is None and dL is None:
+            O, L, *_ = R.ref_grouped(Q, K, V, dO, s, causal)
+            self.O16, self.L32 = R.kernel_feed(O, L)
+            grads = tuple(R.ref_flow(Q, K, V, dO, s, causal, self.O16, self.L32))
+        else:
+            O, L = LR.forward(Q, K, V, s, self.shift, sink)
+            self.O16, self.L32 = R.kernel_feed(O, L)
+            grads = LR.flow(Q, K, V, dO, dL, s, self.shift, self.O16, self.L32, sink)
+            if sink is not None:
+                grads, self.dsink = grads[:3], grads[3]
+        self.ref = dict(zip(OUTPUTS, (O, L) + tuple(grads)))
         self.key_seen = np.full((self.hkv, self.nk), self.nq > 0)       # the last row sees every key under either mask
+        self.keyless = np.broadcast_to(~visible(self.nq, self.nk, causal).any(axis=1), (self.hq, self.nq)).copy()
         self._gates()
 
     def scores(self, causal=None, shift=0):
@@ -143,8 +161,12 @@ class Case:
             S = np.where(vis, s * (q[h] @ k[hk].T), -np.inf)
             P = np.where(seen[:, None], np.exp(S - np.where(seen, L32[h], 0.0)[:, None]), 0.0)
             D = (g[h] * O16[h]).sum(axis=-1)
+            row = (np.abs(g[h]) * np.abs(O16[h])).sum(axis=-1)
+            if self.dL is not None:                                      # D' = D - dL, dropped where L = -inf
+                gl = np.where(seen, f64(self.dL)[h], 0.0)
+                D, row = D - gl, row + np.abs(gl)
             dS = P * (g[h] @ v[hk].T - D[:, None])
-            E = PHI * P * (np.abs(g[h]) @ np.abs(v[hk]).T + (np.abs(g[h]) * np.abs(O16[h])).sum(axis=-1)[:, None])
+            E = PHI * P * (np.abs(g[h]) @ np.abs(v[hk]).T + row[:, None])
             quad["O"][h] = np.sqrt((P * P) @ (vn[hk] ** 2))
             quad["dQ"][h] = s * np.sqrt((dS * dS) @ (kn[hk] ** 2))
             lin["dQ"][h] = s * (E @ kn[hk])
@@ -171,18 +193,28 @@ class Case:
     # ---- the data flow
     @one_thread
     def emulate_forward(self, offset):
-        return forward_flow(self.scores(), np.repeat(self.v, self.G, axis=0), offset)
+        return forward_flow(self.scores(), np.repeat(self.v, self.G, axis=0), offset, sink=self.sink_rows())
+
+    def sink_rows(self):
+        """The sink as forward_flow takes it: float64 [hq, 1] (None without one)."""
+        return None if self.sink is None else f64(self.sink)[:, None]
+
+    def _emulate(self, K, V):
+        """The backward's data flow: regimes.emulate, or with a sink or dL lse_ref.flow(kernel_formats=True)."""
+        if self.sink is None and self.dL is None:
+            return R.emulate(self.t[0], K, V, self.t[3], self.s, self.causal, self.O16, self.L32)
+        return LR.flow(self.t[0], K, V, self.t[3], self.dL, self.s, self.shift, self.O16, self.L32, self.sink, kernel_formats=True)[:3]
 
     @one_thread
     def emulate_backward_exact(self):
         """regimes.emulate as it stands: float64 sums of the bf16-rounded P and dS (what the mutants splice)."""
-        return dict(zip(GRADS, R.emulate(*self.t, self.s, self.causal, self.O16, self.L32)))
+        return dict(zip(GRADS, self._emulate(*self.t[1:3])))
 
     @one_thread
     def emulate_backward(self, partials=False):
         if partials and self.G > 1:
             K, V = (t.repeat_interleave(self.G, dim=0) for t in self.t[1:3])
-            dQ, dK, dV = R.emulate(self.t[0], K, V, self.t[3], self.s, self.causal, self.O16, self.L32)
+            dQ, dK, dV = self._emulate(K, V)
             dK, dV = (R._group_sum(_bf16(x), self.hkv) for x in (dK, dV))
             return dict(dQ=_bf16(dQ), dK=_bf16(dK), dV=_bf16(dV))
         return {n: _bf16(x) for n, x in self.emulate_backward_exact().items()}
@@ -201,6 +233,10 @@ class Packed(Case):
         for field in ("ref", "quad", "rest", "part"):
             setattr(self, field, {n: cat([getattr(p, field)[n] for p in parts]) for n in getattr(p0, field)})
         self.l_gate, self.key_seen = cat([p.l_gate for p in parts]), cat([p.key_seen for p in parts])
+        self.keyless = cat([p.keyless for p in parts])
+        self.sink = p0.sink
+        self.dL = None if p0.dL is None else cat([p.dL for p in parts])
+        self.dsink = None if p0.dsink is None else sum(p.dsink for p in parts)
         self.nq, self.nk = self.t[0].shape[1], self.t[1].shape[1]
 
     def emulate_forward(self, offset):
@@ -213,10 +249,12 @@ class Packed(Case):
 
 
 @one_thread
-def forward_flow(S, v, offset, edit=None):
+def forward_flow(S, v, offset, edit=None, sink=None, sink_times=1):
     """The forward's arithmetic at the reference row maximum - offset: p = exp(S - r), l = sum p (unrounded), p in bf16 for the
     second product, O = bf16((p16 v) / l), L = r + log l.  S [..., nq, nk] with -inf on hidden keys, v [..., nk, d];
-    edit(p16) -> p16: where a mutant alters the second product alone.  A row without a visible key: O = 0, L = -inf."""
+    edit(p16) -> p16: where a mutant alters the second product alone.  A row without a visible key: O = 0, L = -inf.
+    sink (broadcastable to [..., nq], -inf = none): the epilogue of DESIGN.md section 3e -- L' = logaddexp(L, sink) and the
+    accumulator times f = exp(L - L') before the one bf16 rounding; a sink of -inf skips it."""
     m = S.max(axis=-1, initial=-np.inf)
     seen = np.isfinite(m)
     r = np.where(seen, m - offset, 0.0)
@@ -227,22 +265,30 @@ def forward_flow(S, v, offset, edit=None):
         p16 = edit(p16)
     with np.errstate(divide="ignore"):
         L = np.where(seen, r + np.log(l), -np.inf)
-    return dict(O=_bf16((p16 @ v) / l[..., None]), L=L)
+    acc = (p16 @ v) / l[..., None]
+    if sink is not None:
+        sink = np.broadcast_to(sink, L.shape)
+        has = np.isfinite(sink)
+        with np.errstate(invalid="ignore"):
+            Lp = np.where(has, np.logaddexp(L, np.where(has, sink, 0.0)), L)
+            f = np.where(has, np.exp(L - np.where(has, Lp, 0.0)), 1.0)
+        acc, L = acc * (f ** sink_times)[..., None], Lp      # (sink_times = 2: what mutant k1 of tests/sink_rows_ref.py writes)
+    return dict(O=_bf16(acc), L=L)
 
 
 # ------------------------------------------------------------------------------------------------ errors, ratios, the verdict
 def row_errors(got, case):
     """{tensor: error per row [heads, rows]} of a result {tensor: array}: 2-norms over d, |dL| for L.  Where the rule is exact
-    -- a row without a visible key (O = 0, L = -inf, dQ = 0), a key without query rows (dK = dV = 0) -- the error is 0 if the
-    rule holds and +inf if not."""
+    -- a row without a visible key (O = 0, dQ = 0, L = -inf or, bit for bit, the head's sink), a key without query rows
+    (dK = dV = 0) -- the error is 0 if the rule holds and +inf if not."""
     ref, out = case.ref, {}
-    none = np.isneginf(ref["L"])
+    none = case.keyless
     for name, x in got.items():
         x = f64(x)
         if name == "L":
             with np.errstate(invalid="ignore"):
                 e = np.abs(x - ref["L"])
-            out[name] = np.where(none, np.where(np.isneginf(x), 0.0, np.inf), e)
+            out[name] = np.where(none, np.where(x == ref["L"], 0.0, np.inf), e)
             continue
         e, zero = _norm(x - ref[name]), np.abs(x).max(axis=-1, initial=0.0) == 0.0
         exact = none if name in ("O", "dQ") else ~case.key_seen

@@ -52,10 +52,17 @@ def _nan(shape, dtype):
 
 # ------------------------------------------------------------------------------------------------ the calls
 class Dense:
-    """A Case on the device as [batch, H, N, d] tensors (batch > 1: the Case's heads are batch x H, multi-head only)."""
+    """A Case on the device as [batch, H, N, d] tensors (batch > 1: the Case's heads are batch x H, multi-head only).
+    A Case with a sink or a dL (tests/test_gpu_sink_rows.py; batch = 1) goes through the _qk calls whatever its shape, with
+    sink=, dsink= and dL= passed on; .dsink holds the last backward's."""
 
     def __init__(self, case, batch=1):
         self.case, self.batch = case, batch
+        self.extra = case.sink is not None or case.dL is not None
+        assert batch == 1 or not self.extra
+        self.sink = None if case.sink is None else case.sink.cuda()
+        self.dL = None if case.dL is None else case.dL[None].contiguous().cuda()
+        self.dsink = None
         hq, hkv = case.hq // batch, case.hkv // batch
         shape = lambda t, h: t.reshape(batch, h, t.shape[1], *t.shape[2:]).contiguous().cuda()
         Q, K, V, dO = case.t
@@ -71,8 +78,9 @@ class Dense:
         fa, c = _fa(), self.case
         O = _nan(self.Q.shape, torch.bfloat16) if O is None else O
         L = _nan(self.Q.shape[:3], torch.float32) if L is None else L
-        call = fa.flash_attention_2_forward if self.square else fa.flash_attention_2_qk_forward
-        O2, L2 = call(self.Q, self.K, self.V, c.s, causal=c.causal, O=O, L=L)
+        call = fa.flash_attention_2_forward if self.square and not self.extra else fa.flash_attention_2_qk_forward
+        more = {} if self.sink is None else {"sink": self.sink}
+        O2, L2 = call(self.Q, self.K, self.V, c.s, causal=c.causal, O=O, L=L, **more)
         torch.cuda.synchronize()
         assert O2 is O and L2 is L
         return {"O": self.flat(O), "L": self.flat(L)}
@@ -80,7 +88,7 @@ class Dense:
     def workspace(self):
         lib, c = _fa()._capi.lib(), self.case
         hq, hkv = c.hq // self.batch, c.hkv // self.batch
-        if self.square:
+        if self.square and not self.extra:
             return lib.fa2_backward_gqa_workspace_bytes(self.batch, hq, hkv, c.nq, c.d, 0)
         return lib.fa2_backward_qk_workspace_bytes(self.batch, hq, hkv, c.nq, c.nk, c.d, 0)
 
@@ -88,9 +96,15 @@ class Dense:
         fa, c = _fa(), self.case
         dQ, dK, dV = out or (_nan(self.Q.shape, torch.bfloat16), _nan(self.K.shape, torch.bfloat16), _nan(self.V.shape, torch.bfloat16))
         ws = torch.empty(self.workspace(), dtype=torch.uint8, device="cuda") if workspace is None else workspace
-        call = fa.flash_attention_2_backward if self.square else fa.flash_attention_2_qk_backward
+        call = fa.flash_attention_2_backward if self.square and not self.extra else fa.flash_attention_2_qk_backward
+        more = {}
+        if self.sink is not None:
+            self.dsink = _nan((c.hq,), torch.float32)
+            more.update(sink=self.sink, dsink=self.dsink)
+        if self.dL is not None:
+            more["dL"] = self.dL
         for ph in phases:
-            call(self.Q, self.K, self.V, self.O16, self.L32, self.dO, c.s, causal=c.causal, dQ=dQ, dK=dK, dV=dV, workspace=ws, phases=ph)
+            call(self.Q, self.K, self.V, self.O16, self.L32, self.dO, c.s, causal=c.causal, dQ=dQ, dK=dK, dV=dV, workspace=ws, phases=ph, **more)
         torch.cuda.synchronize()
         return {"dQ": self.flat(dQ), "dK": self.flat(dK), "dV": self.flat(dV)}
 
@@ -100,7 +114,10 @@ class Dense:
         if not self.square:
             return [((7,), False), ((1, 6), False)]
         single = B.single_kernel(c.nq, c.d)
-        says = _plan_says(self.batch, c.hq // self.batch, c.nq, c.d, c.causal)
+        if self.extra:
+            says = _fa()._capi.lib().fa2_backward_gqa_plan(1, c.hq, c.hkv, c.nq, c.d, 0, int(c.causal), None)
+        else:
+            says = _plan_says(self.batch, c.hq // self.batch, c.nq, c.d, c.causal)
         assert says == (1 if single else 2), f"fa2_backward_plan says {says} at N = {c.nq}, d = {c.d}: rule (a) has changed"
         return [((7,), single), ((1, 6), False)] + ([((9,), True)] if single else [])
 
