@@ -19,6 +19,7 @@ EXTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend
 EXTEND_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_extend_ragged_mi355x.h")
 ROPE_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_ragged_mi355x.h")
 ROPE_NORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_norm_mi355x.h")
+MLA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -147,6 +148,14 @@ ROPE_NORM_SIGNATURES = {
     "fa2_norm_rope_kv_append_ragged_paged": (_i, [_vp] * 11 + [_f, _vp, _sz] + [_vp] * 3 + [_i] * 11 + [_ll] * 4 + [_i, _i, _vp]),
 }
 
+# include/fa2_mla_mi355x.h, the same library: MLA decode attention over a 576-wide latent KV cache (one cache tensor, O 512 wide).
+MLA_SIGNATURES = {
+    "fa2_mla_decode_num_splits": (_i, [_i] * 6),
+    "fa2_mla_decode_workspace_bytes": (_sz, [_i] * 7),
+    "fa2_forward_mla_decode": (_i, [_vp] * 5 + [_i] * 6 + [_f, _i, _i, _vp, _sz, _vp]),
+    "fa2_forward_mla_decode_paged": (_i, [_vp] * 6 + [_i] * 8 + [_f, _i, _i, _vp, _sz, _vp]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -173,7 +182,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items())
                                   + list(EXTEND_SIGNATURES.items()) + list(EXTEND_RAGGED_SIGNATURES.items())
-                                  + list(ROPE_RAGGED_SIGNATURES.items()) + list(ROPE_NORM_SIGNATURES.items())):
+                                  + list(ROPE_RAGGED_SIGNATURES.items()) + list(ROPE_NORM_SIGNATURES.items())
+                                  + list(MLA_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

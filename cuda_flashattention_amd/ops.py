@@ -700,6 +700,99 @@ def flash_attention_2_extend_paged(Q, K_pages, V_pages, block_table, seqlens_k=N
                               stream, k_descale, v_descale, window_left, True)
 
 
+MLA_KV_LORA_RANK, MLA_ROPE_DIM = 512, 64      # the one latent layout the MLA kernels take: a cache row is 576 wide
+
+
+def mla_decode_num_splits(B, H, q_len, kv_capacity):
+    """The split count n_splits=0 stands for in the MLA decode calls (fa2_mla_decode_num_splits): host arithmetic on the capacity,
+    never on a length -- B ceil(H q_len / 32) workgroups to fill 256 CUs, a split of a full cache keeping at least 256 keys."""
+    return _capi.lib().fa2_mla_decode_num_splits(B, H, q_len, kv_capacity, MLA_KV_LORA_RANK, MLA_ROPE_DIM)
+
+
+def mla_decode_workspace(B, H, q_len, kv_capacity, n_splits=0, device="cuda"):
+    """Scratch for flash_attention_2_mla_decode / _paged (the splits' fp32 partials; empty for one split): allocate once, pass as
+    workspace= (graph capture).  n_splits=0 is mla_decode_num_splits(B, H, q_len, kv_capacity)."""
+    need = _capi.lib().fa2_mla_decode_workspace_bytes(B, H, q_len, kv_capacity, MLA_KV_LORA_RANK, MLA_ROPE_DIM, n_splits)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream):
+    """flash_attention_2_mla_decode (block_table None) and _paged: one set of checks for both."""
+    row, name = MLA_KV_LORA_RANK + MLA_ROPE_DIM, "ckv_cache" if block_table is None else "ckv_pages"
+    for n, t, dims in (("Q", Q, 4), (name, cache, 3)):
+        if not isinstance(t, torch.Tensor) or t.dim() != dims or t.shape[-1] != row or t.dtype != torch.bfloat16:
+            raise ValueError(f"{n}: expected a bf16 {dims}-d tensor whose last dimension is {row} ({MLA_KV_LORA_RANK} latent columns "
+                             f"followed by {MLA_ROPE_DIM} rotary ones), got "
+                             f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    B, H, Nq, _ = Q.shape
+    if min(B, H, Nq) < 1 or cache.shape[0] < 1 or cache.shape[1] < 1:
+        raise ValueError(f"Q {tuple(Q.shape)}, {name} {tuple(cache.shape)}: every dimension must be at least 1")
+    if isinstance(n_splits, bool) or not isinstance(n_splits, int) or not 0 <= n_splits <= DECODE_MAX_SPLITS:
+        raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
+    if block_table is None:
+        if cache.shape[0] != B:
+            raise ValueError(f"{name}: shape {tuple(cache.shape)}, expected ({B}, N_cap, {row}): one slab per sequence of Q")
+        kv_capacity = cache.shape[1]
+    else:
+        if cache.shape[1] % DECODE_PAGE_GRAIN:
+            raise ValueError(f"{name}: page_size {cache.shape[1]} is not a multiple of {DECODE_PAGE_GRAIN} (the kernel's key tile)")
+        kv_capacity = _block_table_arg(block_table, Q, B) * cache.shape[1]
+        if kv_capacity > 0x7fffffff - (DECODE_MAX_SPLITS + 2) * 128:
+            raise ValueError(f"block_table: a capacity of {kv_capacity} keys, above what an int indexes")
+    if seqlens_k is not None:
+        _seqlens_arg(seqlens_k, Q, B)
+    _bhnd(Q, "Q")
+    if not cache.is_cuda or not cache.is_contiguous() or cache.device != Q.device:
+        raise ValueError(f"{name} must be a contiguous device tensor on Q's device (got {cache.device}, strides {tuple(cache.stride())})")
+    if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)) or not softmax_scale > 0.0:
+        raise ValueError(f"softmax_scale: {softmax_scale!r}, expected a positive number (the model's scale: 576 does not tell it)")
+    O = torch.empty(B, H, Nq, MLA_KV_LORA_RANK, dtype=Q.dtype, device=Q.device) if O is None else \
+        _like(O, "O", Q, (B, H, Nq, MLA_KV_LORA_RANK), Q.dtype)
+    L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
+    lib = _capi.lib()
+    need = lib.fa2_mla_decode_workspace_bytes(B, H, Nq, kv_capacity, MLA_KV_LORA_RANK, MLA_ROPE_DIM, n_splits)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+    if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
+        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (mla_decode_workspace)")
+    tail = (MLA_KV_LORA_RANK, MLA_ROPE_DIM, float(softmax_scale), 1 if causal else 0, n_splits, _ptr(workspace),
+            0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
+    if block_table is None:
+        st = lib.fa2_forward_mla_decode(Q.data_ptr(), cache.data_ptr(), _ptr(seqlens_k), O.data_ptr(), L.data_ptr(), B, H, Nq, kv_capacity, *tail)
+        check(st, "fa2_forward_mla_decode")
+    else:
+        st = lib.fa2_forward_mla_decode_paged(Q.data_ptr(), cache.data_ptr(), block_table.data_ptr(), _ptr(seqlens_k), O.data_ptr(),
+                                              L.data_ptr(), B, H, Nq, cache.shape[0], cache.shape[1], block_table.shape[1], *tail)
+        check(st, "fa2_forward_mla_decode_paged")
+    return O, L
+
+
+def flash_attention_2_mla_decode(Q, ckv_cache, seqlens_k=None, *, softmax_scale, causal=True, n_splits=0, O=None, L=None,
+                                 workspace=None, stream=None):
+    """O, L = a decode step of multi-head latent attention in absorbed form (fa2_forward_mla_decode, include/fa2_mla_mi355x.h):
+    multi-query attention over ONE latent cache row per token.  Q [B, H, N_q, 576] bf16 (per head q_nope W_UK, 512 columns, then
+    q_rope, 64 columns), ckv_cache [B, N_cap, 576] bf16 (the 512-wide compressed KV followed by the 64-wide rotary key).  The score
+    uses all 576 columns, the value is the first 512 of the same row: O [B, H, N_q, 512] bf16 (W_UV is the caller's next matmul),
+    L [B, H, N_q] fp32.  Any H N_q >= 1.  INFERENCE ONLY.
+    softmax_scale is REQUIRED: the model's scale belongs to its un-absorbed head width (times a YaRN factor), which 576 does not tell.
+    seqlens_k, causal (bottom-right), rows without a key (O = 0, L = -inf), rows past a length (anything, NaN included), n_splits,
+    workspace and graph capture are flash_attention_2_decode's: n_splits=0 is mla_decode_num_splits(B, H, N_q, N_cap), the workspace
+    mla_decode_workspace(B, H, N_q, N_cap, n_splits).  The cache is written with torch (there is no latent append kernel).
+    Not covered: e4m3 caches, sinks, windows, ragged Q, merge_states_forward on the 512-wide O, a backward, other latent widths."""
+    return _mla_call(Q, ckv_cache, None, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream)
+
+
+def flash_attention_2_mla_decode_paged(Q, ckv_pages, block_table, seqlens_k=None, *, softmax_scale, causal=True, n_splits=0, O=None,
+                                       L=None, workspace=None, stream=None):
+    """flash_attention_2_mla_decode over a pool of pages (fa2_forward_mla_decode_paged): ckv_pages [n_pages, page_size, 576] bf16,
+    page_size a multiple of 32, block_table int32 [B, max_pages] on the device as flash_attention_2_decode_paged describes it
+    (shared pages, entries past a length never read, an entry in use clamped to [0, n_pages)).  The capacity is max_pages x
+    page_size; with the same n_splits the result is bit for bit flash_attention_2_mla_decode's on the gathered cache."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
+    return _mla_call(Q, ckv_pages, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream)
+
+
 class ExtendRaggedPlan:
     """What extend_ragged_plan returns and the ragged extend calls take: the device buffer the plan kernel filled (`tensor`,
     int32) and the (B, H_q, H_kv, total_q) it was built for.  It depends on cu_seqlens_q and H_q / H_kv only: build it once per
