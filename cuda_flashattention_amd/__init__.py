@@ -15,5 +15,6 @@ from .ops import kv_cache_append, kv_cache_append_paged  # noqa: F401
 from .ops import rope_kv_cache_append, rope_kv_cache_append_paged  # noqa: F401
 from .ops import rope_kv_cache_append_ragged, rope_kv_cache_append_ragged_paged  # noqa: F401
 from .ops import norm_rope_kv_cache_append_ragged, norm_rope_kv_cache_append_ragged_paged  # noqa: F401
+from .ops import mla_kv_cache_append, mla_kv_cache_append_paged  # noqa: F401
 from .ops import kv_cache_append_ragged, kv_cache_append_ragged_paged  # noqa: F401
 from .ops import merge_states_forward,merge_states_backward, merge_attention_states, attention_segments  # noqa: F401

@@ -20,6 +20,7 @@ EXTEND_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2
 ROPE_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_ragged_mi355x.h")
 ROPE_NORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_norm_mi355x.h")
 MLA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_mi355x.h")
+MLA_APPEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_append_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -156,6 +157,13 @@ MLA_SIGNATURES = {
     "fa2_forward_mla_decode_paged": (_i, [_vp] * 6 + [_i] * 8 + [_f, _i, _i, _vp, _sz, _vp]),
 }
 
+# include/fa2_mla_append_mi355x.h, the same library: the producer of that latent cache and of the decode's Q (RMSNorm of the 512
+# latent columns, rotation of the 64 rotary ones, q_nope and the rotated q_pe side by side); MLA_SIGNATURES is pinned to its header.
+MLA_APPEND_SIGNATURES = {
+    "fa2_mla_kv_append": (_i, [_vp] * 8 + [_f, _vp] + [_i] * 8 + [_ll] * 8 + [_vp]),
+    "fa2_mla_kv_append_paged": (_i, [_vp] * 9 + [_f, _vp] + [_i] * 10 + [_ll] * 8 + [_vp]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -183,7 +191,7 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items())
                                   + list(EXTEND_SIGNATURES.items()) + list(EXTEND_RAGGED_SIGNATURES.items())
                                   + list(ROPE_RAGGED_SIGNATURES.items()) + list(ROPE_NORM_SIGNATURES.items())
-                                  + list(MLA_SIGNATURES.items())):
+                                  + list(MLA_SIGNATURES.items()) + list(MLA_APPEND_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -777,7 +777,7 @@ def flash_attention_2_mla_decode(Q, ckv_cache, seqlens_k=None, *, softmax_scale,
     softmax_scale is REQUIRED: the model's scale belongs to its un-absorbed head width (times a YaRN factor), which 576 does not tell.
     seqlens_k, causal (bottom-right), rows without a key (O = 0, L = -inf), rows past a length (anything, NaN included), n_splits,
     workspace and graph capture are flash_attention_2_decode's: n_splits=0 is mla_decode_num_splits(B, H, N_q, N_cap), the workspace
-    mla_decode_workspace(B, H, N_q, N_cap, n_splits).  The cache is written with torch (there is no latent append kernel).
+    mla_decode_workspace(B, H, N_q, N_cap, n_splits).  The cache and Q are produced by mla_kv_cache_append.
     Not covered: e4m3 caches, sinks, windows, ragged Q, merge_states_forward on the 512-wide O, a backward, other latent widths."""
     return _mla_call(Q, ckv_cache, None, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream)
 
@@ -1560,6 +1560,118 @@ def norm_rope_kv_cache_append_ragged_paged(Q, K_new, V_new, K_pages, V_pages, bl
         raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
     return _rope_ragged_call(Q, K_new, V_new, K_pages, V_pages, block_table, cos, sin, cu_seqlens_q_or_plan, seqlens_k, interleaved,
                              k_descale, v_descale, Q_out, stream, norm=(q_weight, k_weight, eps))
+
+
+def _mla_source_arg(x, name, shape, how):
+    """The strides of a source of the MLA append: a bf16 VIEW of `shape` with the last dimension contiguous, strides non-negative
+    multiples of 8 elements, 16-byte aligned -- a lane loads 16 bytes (_kv_new_arg's rules)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != len(shape):
+        raise ValueError(f"{name}: expected a {len(shape)}-d tensor {how}, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: dtype {x.dtype}, expected torch.bfloat16")
+    if any(got != want for got, want in zip(x.shape, shape) if want is not None) or min(x.shape) < 1:
+        raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {how} with every dimension at least 1")
+    if x.stride(-1) != 1:
+        raise ValueError(f"{name}: stride {tuple(x.stride())}, the last dimension must be contiguous (stride(-1) == 1)")
+    strides = tuple(x.stride()[:-1])
+    if any(s < 0 or s % 8 for s in strides):
+        raise ValueError(f"{name}: strides {strides} must be non-negative multiples of 8 elements: a lane loads 16 bytes")
+    if x.storage_offset() % 8:
+        raise ValueError(f"{name}: storage offset {x.storage_offset()} elements is not 16-byte aligned (a multiple of 8): a lane loads 16 bytes")
+    return strides
+
+
+def _mla_append_call(q_nope, q_pe, kv_new, cache, block_table, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream):
+    """mla_kv_cache_append (block_table None) and _paged: one set of checks for both."""
+    rank, rope, row = MLA_KV_LORA_RANK, MLA_ROPE_DIM, MLA_KV_LORA_RANK + MLA_ROPE_DIM
+    name = "ckv_cache" if block_table is None else "ckv_pages"
+    kv_strides = _mla_source_arg(kv_new, "kv_new", (None, None, row), f"[B, n_new, {row}] ({rank} latent columns, then {rope} rotary ones)")
+    B, n_new, _ = kv_new.shape
+    if (q_nope is None) != (q_pe is None):
+        raise ValueError("q_nope and q_pe come together: both tensors, or both None for a cache-only call")
+    H, nope_strides, pe_strides = 0, (0, 0, 0), (0, 0, 0)
+    if q_nope is not None:
+        nope_strides = _mla_source_arg(q_nope, "q_nope", (B, None, n_new, rank), f"[{B}, H, {n_new}, {rank}] (the absorbed q_nope W_UK; a view)")
+        H = q_nope.shape[1]
+        pe_strides = _mla_source_arg(q_pe, "q_pe", (B, H, n_new, rope), f"[{B}, {H}, {n_new}, {rope}] (a view, e.g. x[..., 128:].permute(0, 2, 1, 3))")
+    if not isinstance(cache, torch.Tensor) or cache.dim() != 3 or cache.shape[-1] != row or cache.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: expected a bf16 3-d tensor whose last dimension is {row}, got "
+                         f"{(tuple(cache.shape), cache.dtype) if isinstance(cache, torch.Tensor) else type(cache).__name__}")
+    if cache.shape[0] < 1 or cache.shape[1] < 1:
+        raise ValueError(f"{name}: shape {tuple(cache.shape)}, every dimension must be at least 1")
+    if block_table is None:
+        if cache.shape[0] != B:
+            raise ValueError(f"{name}: shape {tuple(cache.shape)}, expected ({B}, N_cap, {row}): one slab per sequence of kv_new")
+        capacity = cache.shape[1]
+    else:
+        if cache.shape[1] % DECODE_PAGE_GRAIN:
+            raise ValueError(f"{name}: page_size {cache.shape[1]} is not a multiple of {DECODE_PAGE_GRAIN} (the decode kernel's key tile)")
+        capacity = _block_table_arg(block_table, kv_new, B) * cache.shape[1]
+        if capacity > 0x7fffffff - (DECODE_MAX_SPLITS + 2) * 128:
+            raise ValueError(f"block_table: a capacity of {capacity} keys, above what an int indexes")
+    rot_dim, n_positions = _rope_tables_arg(cos, sin, rope, capacity)
+    if rot_dim != rope:
+        raise ValueError(f"cos: shape {tuple(cos.shape)} is a rot_dim of {rot_dim}, expected [n_positions, {rope // 2}]: all {rope} rotary columns rotate")
+    flag = _rope_interleaved(interleaved)
+    _norm_weight_arg(kv_weight, "kv_weight", rank)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.floating)) or not math.isfinite(_f32(eps)) or _f32(eps) <= 0:
+        raise ValueError(f"eps: {eps!r}, expected a finite float > 0 (as a float32)")
+    if seqlens_k is None:
+        raise ValueError("seqlens_k is required: token t of sequence b has position seqlens_k[b] - n_new + t (the lengths AFTER the "
+                         "append, the decode call's tensor)")
+    _seqlens_arg(seqlens_k, kv_new, B)
+    if not kv_new.is_cuda:
+        raise ValueError("kv_new must be a device tensor")
+    for n, t in (("q_nope", q_nope), ("q_pe", q_pe), ("kv_weight", kv_weight)):
+        if t is not None and t.device != kv_new.device:
+            raise ValueError(f"{n} is on {t.device}, expected {kv_new.device}")
+    if not cache.is_contiguous() or cache.device != kv_new.device:
+        raise ValueError(f"{name} must be a contiguous device tensor on kv_new's device (got {cache.device}, strides {tuple(cache.stride())})")
+    Q_out = _rope_devices(q_nope, Q_out, cos, sin, kv_new, B, H, n_new, row)
+    lib = _capi.lib()
+    head = (_ptr(q_nope), _ptr(q_pe), _ptr(Q_out), kv_new.data_ptr(), cache.data_ptr())
+    mid = (cos.data_ptr(), sin.data_ptr(), kv_weight.data_ptr(), float(eps), seqlens_k.data_ptr(), B, H, n_new)
+    tail = (rank, rope, n_positions, flag, *nope_strides, *pe_strides, *kv_strides, _stream_ptr(stream))
+    if block_table is None:
+        check(lib.fa2_mla_kv_append(*head, *mid, capacity, *tail), "fa2_mla_kv_append")
+    else:
+        check(lib.fa2_mla_kv_append_paged(*head, block_table.data_ptr(), *mid, cache.shape[0], cache.shape[1], block_table.shape[1], *tail),
+              "fa2_mla_kv_append_paged")
+    return Q_out
+
+
+def mla_kv_cache_append(q_nope, q_pe, kv_new, ckv_cache, cos, sin, kv_weight, eps, seqlens_k, *, interleaved=False, Q_out=None,
+                        stream=None):
+    """The producer of the latent cache and of the Q that flash_attention_2_mla_decode takes (fa2_mla_kv_append,
+    include/fa2_mla_append_mi355x.h): ONE launch writes the n_new newest tokens' cache rows, row[:512] = RMSNorm(c_kv; kv_weight,
+    eps) (the models' kv_a_layernorm, over the 512 latent columns only) and row[512:] = rotate(k_pe, pos), and returns Q_out
+    bf16 [B, H, n_new, 576] contiguous: Q_out[..., :512] the bytes of q_nope, Q_out[..., 512:] = rotate(q_pe, pos).  A step is
+    seqlens_k += n_new (in place), mla_kv_cache_append, flash_attention_2_mla_decode(Q_out, ...); one captured graph serves every
+    step.
+    kv_new: bf16 [B, n_new, 576] VIEW (c_kv then k_pe: the slice of the fused kv_a_proj_with_mqa output, as it is); q_nope: bf16
+    [B, H, n_new, 512] view (the absorbed q_nope W_UK, e.g. the bmm output [H, B n_new, 512] viewed); q_pe: bf16 [B, H, n_new, 64]
+    view with strides of its own (the slice at column 128 of [..., H, 192]).  Last dimension contiguous, strides multiples of 8, no
+    .contiguous() copy.  q_nope = q_pe = None is the cache-only call (filling the cache after a prefill; returns None).
+    ckv_cache: bf16 [B, N_cap, 576] contiguous.  cos, sin: fp32 [n_positions, 32] device tensors, n_positions >= N_cap;
+    interleaved as rope_kv_cache_append.  kv_weight: fp32 [512] (convert a checkpoint's bf16 weight once); eps finite and > 0.
+    POSITION and the write-or-drop rule are rope_kv_cache_append's: pos = seqlens_k[b] - n_new + t (seqlens_k required, the
+    lengths AFTER the append), a row is written iff 0 <= pos < N_cap, EVERY Q_out row is written (+0.0 in all 576 columns for a
+    dropped position).  ARITHMETIC: norm_rope_kv_cache_append_ragged's norm at d = 512 (the butterfly runs over 64 lanes) and
+    rope_kv_cache_append's rotation, every product and sum one fp32 rounding, one rounding to bf16.  Q_out is allocated when not
+    given -- the ONLY allocation; pass one for graph capture.  Q_out overlapping an input is undefined."""
+    return _mla_append_call(q_nope, q_pe, kv_new, ckv_cache, None, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream)
+
+
+def mla_kv_cache_append_paged(q_nope, q_pe, kv_new, ckv_pages, block_table, cos, sin, kv_weight, eps, seqlens_k, *, interleaved=False,
+                              Q_out=None, stream=None):
+    """mla_kv_cache_append into a pool of pages (fa2_mla_kv_append_paged), the pool flash_attention_2_mla_decode_paged reads:
+    ckv_pages bf16 [n_pages, page_size, 576], page_size a multiple of 32, block_table int32 [B, max_pages] on the device, the
+    capacity max_pages * page_size (the tables need that many rows).  A token whose table entry lies outside [0, n_pages) has its
+    cache row DROPPED; its Q_out rows are still written: Q depends on the position alone.  PAGES WRITTEN BY ONE CALL MUST BELONG
+    TO ONE SEQUENCE EACH.  Everything else is mla_kv_cache_append's."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
+    return _mla_append_call(q_nope, q_pe, kv_new, ckv_pages, block_table, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream)
 
 
 def kv_cache_append_ragged(K_new, V_new, K_cache, V_cache, cu_seqlens_q_or_plan, seqlens_k, k_descale=None, v_descale=None, stream=None):

@@ -34,7 +34,7 @@
  * FA2_ERR_UNSUPPORTED_HEAD_DIM; the grid B x ceil(M / 32) x n_splits above INT_MAX or a workspace size that overflows ->
  * FA2_ERR_INVALID_SHAPE; n_splits > 1 with a workspace that is NULL, too small or not 16-byte aligned -> FA2_ERR_WORKSPACE.
  *
- * NOT COVERED: e4m3 latent caches, sinks, sliding windows, ragged / token-major Q, an append kernel for the latent cache,
+ * NOT COVERED: e4m3 latent caches, sinks, sliding windows, ragged / token-major Q (the cache's append: fa2_mla_append_mi355x.h),
  * merging with fa2_merge_states (O is 512 wide), a backward, other latent widths.
  */
 #ifndef FA2_MLA_MI355X_H
