@@ -21,6 +21,7 @@ ROPE_RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_r
 ROPE_NORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rope_norm_mi355x.h")
 MLA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_mi355x.h")
 MLA_APPEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_append_mi355x.h")
+MLA_FP8_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_fp8_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -164,6 +165,16 @@ MLA_APPEND_SIGNATURES = {
     "fa2_mla_kv_append_paged": (_i, [_vp] * 9 + [_f, _vp] + [_i] * 10 + [_ll] * 8 + [_vp]),
 }
 
+# include/fa2_mla_fp8_mi355x.h, the same library: the MLA decode and append over a 640-byte row (512 e4m3 latent codes, then the
+# 64 rotary columns in bf16) with one fp32 latent_descale per cache, a device pointer.  The two tables above stay pinned to their
+# headers; fa2_mla_decode_num_splits and _workspace_bytes serve these calls unchanged.
+MLA_FP8_SIGNATURES = {
+    "fa2_forward_mla_decode_fp8kv": (_i, [_vp] * 6 + [_i] * 6 + [_f, _i, _i, _vp, _sz, _vp]),
+    "fa2_forward_mla_decode_paged_fp8kv": (_i, [_vp] * 7 + [_i] * 8 + [_f, _i, _i, _vp, _sz, _vp]),
+    "fa2_mla_kv_append_fp8kv": (_i, [_vp] * 8 + [_f, _vp, _vp] + [_i] * 8 + [_ll] * 8 + [_vp]),
+    "fa2_mla_kv_append_paged_fp8kv": (_i, [_vp] * 9 + [_f, _vp, _vp] + [_i] * 10 + [_ll] * 8 + [_vp]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -191,7 +202,8 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(KVCACHE_SIGNATURES.items()) + list(ROPE_SIGNATURES.items())
                                   + list(EXTEND_SIGNATURES.items()) + list(EXTEND_RAGGED_SIGNATURES.items())
                                   + list(ROPE_RAGGED_SIGNATURES.items()) + list(ROPE_NORM_SIGNATURES.items())
-                                  + list(MLA_SIGNATURES.items()) + list(MLA_APPEND_SIGNATURES.items())):
+                                  + list(MLA_SIGNATURES.items()) + list(MLA_APPEND_SIGNATURES.items())
+                                  + list(MLA_FP8_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

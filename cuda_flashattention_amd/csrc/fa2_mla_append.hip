@@ -26,10 +26,18 @@
 // capacity <= n_positions.  A Q_out row is a function of (b, head, t) alone.  No loop bound comes from device memory.
 // ARITHMETIC.  fa2_qk_norm.h (steps 1-5 of fa2_rope_norm_mi355x.h at d = 512) and fa2_rope_rotate.h, unchanged: every product
 // and sum one fp32 rounding, nothing contracted, one rounding to bf16.
+// E4M3 LATENT CACHES (fa2_mla_kv_append_fp8kv / _paged_fp8kv, include/fa2_mla_fp8_mi355x.h): the same kernel at EB = 1.  A row is
+// 640 bytes and fa2_kv_append_addr.h counts it in bytes (d = 640).  The cache unit rounds the norm to bf16 exactly as above and
+// THEN quantises those eight values with kv_quantise8 (fa2_kv_quantise.h: a correctly rounded division by the cache's one descale,
+// read on the device, the clamp to +-448, round to nearest even): 8 bytes a lane at byte 8 lane -- one coalesced 512-byte request --
+// and the eight rotary lanes' bf16 at byte 512 + 16 c.  So the latent bytes are the quantisation of the bf16 call's latent columns
+// and the rotary bytes are its rotary bytes.  The query units are the ones above.
 #include "fa2_common.h"
 #include "fa2_kv_append_addr.h"
+#include "fa2_kv_quantise.h"
 #include "fa2_launch.h"
 #include "fa2_mla_append_mi355x.h"
+#include "fa2_mla_fp8_mi355x.h"
 #include "fa2_qk_norm.h"
 #include "fa2_rope_rotate.h"
 
@@ -59,6 +67,7 @@ struct MlaAppendArgs {
     long long nb, nh, nt;                        // q_nope's element strides: batch, head, token
     long long pb, ph, pt;                        // q_pe's
     long long kb, kt;                            // kv_new's: batch, token
+    const float* descale;                        // e4m3 latent columns: the cache holds y / *descale (DEVICE; NULL: 1)
 };
 
 // the value of lane ^ 32 added to the lane's own: v_permlane32_swap exchanges the upper half of its first operand with the
@@ -118,9 +127,16 @@ __device__ __forceinline__ u32x4 mla_app_rot(const MlaAppRot& v, int c)
     }
 }
 
-template <bool PAGED, bool INTERLEAVED>
+// EB: bytes per latent element of the cache row, 2 (bf16, everything above) or 1 (fa2_mla_kv_append_fp8kv / _paged_fp8kv).
+template <bool PAGED, bool INTERLEAVED, int EB = 2>
 __global__ __launch_bounds__(256) void fa2_mla_append_kernel(const MlaAppendArgs a)
 {
+    static_assert(EB == 1 || EB == 2, "bf16 or e4m3 latent columns");
+    constexpr int ROWB = EB * kMlaAppLatent + 2 * kMlaAppRope;      // bytes of a cache row: 1152 or 640
+    // the cache's descale, once per wave: a scalar load on the device, so that a captured graph sees the value of its replay
+    float ds = 1.0f;
+    if constexpr (EB == 1)
+        if (a.descale) ds = __uint_as_float(__builtin_amdgcn_readfirstlane(*(const mla_app_const_int*)a.descale));
     const int lane = threadIdx.x & 63;
     const int c = lane & 7, hh = lane >> 3;      // a rotary lane's chunk; a query unit's head of that lane
     // the lane's eight weights, once per wave
@@ -141,10 +157,10 @@ __global__ __launch_bounds__(256) void fa2_mla_append_kernel(const MlaAppendArgs
             if constexpr (PAGED) {
                 if (pos >= 0) {
                     const int entry = ((const mla_app_const_int*)a.block_table)[(long long)b * a.max_pages + kv_append_table_index(pos, a.page_size)];
-                    to = kv_append_offset_paged(pos, entry, a.n_pages, 0, 1, a.page_size, kMlaAppRow);
+                    to = kv_append_offset_paged(pos, entry, a.n_pages, 0, 1, a.page_size, EB == 2 ? kMlaAppRow : ROWB);
                 }
             } else {
-                to = kv_append_offset(pos, b, 0, 1, a.Ncap, kMlaAppRow);      // dropped for pos = -1
+                to = kv_append_offset(pos, b, 0, 1, a.Ncap, EB == 2 ? kMlaAppRow : ROWB);      // dropped for pos = -1; EB = 1: in bytes
             }
             if (to < 0) continue;      // wave-uniform: the whole wave leaves together
             const __bf16* src = (const __bf16*)a.kv + (long long)b * a.kb + (long long)t * a.kt;
@@ -152,9 +168,16 @@ __global__ __launch_bounds__(256) void fa2_mla_append_kernel(const MlaAppendArgs
             MlaAppRot rot;
             if (lane < 8) rot = mla_app_rot_load<INTERLEAVED>(src + kMlaAppLatent, c, pos, a.cos, a.sin);
             const float r = mla_app_rstd(qk_norm_sumsq8(x), a.eps);      // every lane
+            if constexpr (EB == 2) {
             __bf16* row = (__bf16*)a.C + to;
             *reinterpret_cast<u32x4*>(row + 8 * lane) = qk_norm_scale8(x, r, w0, w1);
             if (lane < 8) *reinterpret_cast<u32x4*>(row + kMlaAppLatent + 8 * c) = mla_app_rot<INTERLEAVED>(rot, c);
+            } else {
+                // the bf16 append's eight values, THEN their codes: 8 bytes a lane at byte 8 lane; the rotary bf16 behind byte 512
+                char* row = (char*)a.C + to;
+                *reinterpret_cast<u32x2*>(row + 8 * lane) = kv_quantise8(qk_norm_scale8(x, r, w0, w1), ds);
+                if (lane < 8) *reinterpret_cast<u32x4*>(row + kMlaAppLatent + 16 * c) = mla_app_rot<INTERLEAVED>(rot, c);
+            }
         } else {
             // ---- a query unit: heads h0 .. h0 + n - 1 of token (b, t)
             const int h0 = (k - 1) * kMlaAppHeads;
@@ -190,14 +213,14 @@ __global__ __launch_bounds__(256) void fa2_mla_append_kernel(const MlaAppendArgs
     }
 }
 
-template <bool PAGED, bool INTERLEAVED>
+template <bool PAGED, bool INTERLEAVED, int EB>
 hipError_t mla_append_launch(MlaAppendArgs a, hipStream_t stream)
 {
     a.upt = 1u + (unsigned)((a.H + kMlaAppHeads - 1) / kMlaAppHeads);
     const long long units = (long long)a.B * a.n_new * a.upt;      // <= B x (H + 1) x n_new
     a.units = (unsigned)units;
     const unsigned grid = (unsigned)std::min<long long>((units + 3) / 4, kMlaAppMaxBlocks);
-    hipLaunchKernelGGL((fa2_mla_append_kernel<PAGED, INTERLEAVED>), dim3(grid), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((fa2_mla_append_kernel<PAGED, INTERLEAVED, EB>), dim3(grid), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -216,7 +239,7 @@ inline bool mla_append_null(const void* q_nope, const void* q_pe, const void* Q_
 
 // Everything both entry points check after their NULL pointers and their own capacity rules, in the header's order, then the
 // launch; capacity is kv_capacity or max_pages_per_seq x page_size.
-template <bool PAGED>
+template <bool PAGED, int EB = 2>
 int mla_append_run(const MlaAppendArgs& a, int kv_lora_rank, int rope_dim, int n_positions, int interleaved, hipStream_t stream)
 {
     if ((long long)a.B * ((long long)a.H + 1) > 0x7fffffffLL || (long long)a.B * ((long long)a.H + 1) * a.n_new > 0x7fffffffLL)
@@ -231,8 +254,58 @@ int mla_append_run(const MlaAppendArgs& a, int kv_lora_rank, int rope_dim, int n
         mla_append_misaligned(a.C) || mla_append_misaligned(a.cos) || mla_append_misaligned(a.sin) || mla_append_misaligned(a.w))
         return FA2_ERR_INVALID_SHAPE;
     if (kv_lora_rank != kMlaAppLatent || rope_dim != kMlaAppRope) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
-    const hipError_t e = interleaved ? mla_append_launch<PAGED, true>(a, stream) : mla_append_launch<PAGED, false>(a, stream);
+    const hipError_t e = interleaved ? mla_append_launch<PAGED, true, EB>(a, stream) : mla_append_launch<PAGED, false, EB>(a, stream);
     return e == hipSuccess ? FA2_OK : FA2_ERR_HIP_BASE - (int)e;
+}
+
+}  // namespace
+
+}  // namespace fa2
+
+namespace fa2 {
+
+namespace {
+
+struct MlaAppendStrides { long long nb, nh, nt, pb, ph, pt, kb, kt; };
+
+// fa2_mla_kv_append and its e4m3 form: the checks of the contiguous call, then mla_append_run
+template <int EB>
+int mla_append_contiguous(const void* q_nope, const void* q_pe, void* Q_out, const void* kv_new, void* ckv_cache, const float* cos_table,
+                          const float* sin_table, const float* kv_weight, float eps, const float* descale, const int* seqlens_k, int B,
+                          int H, int n_new, int kv_capacity, int kv_lora_rank, int rope_dim, int n_positions, int interleaved,
+                          const MlaAppendStrides& s, void* stream)
+{
+    if (mla_append_null(q_nope, q_pe, Q_out, H, kv_new, ckv_cache, cos_table, sin_table, kv_weight, seqlens_k)) return FA2_ERR_NULL_POINTER;
+    if (B <= 0 || n_new <= 0 || kv_capacity <= 0 || H < 0) return FA2_ERR_INVALID_SHAPE;
+    // the MLA decode's limit: one sequence, one buffer resource of 1152-byte (e4m3: 640-byte) rows
+    if ((long long)kv_capacity * (EB * kMlaAppLatent + 2 * kMlaAppRope) > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;
+    MlaAppendArgs a{};
+    a.q_nope = q_nope; a.q_pe = q_pe; a.Qout = Q_out; a.kv = kv_new; a.C = ckv_cache; a.cos = cos_table; a.sin = sin_table;
+    a.w = kv_weight; a.eps = eps; a.seqlens = seqlens_k; a.descale = descale;
+    a.B = B; a.H = Q_out ? H : 0; a.n_new = n_new; a.Ncap = kv_capacity;
+    a.nb = s.nb; a.nh = s.nh; a.nt = s.nt; a.pb = s.pb; a.ph = s.ph; a.pt = s.pt; a.kb = s.kb; a.kt = s.kt;
+    return mla_append_run<false, EB>(a, kv_lora_rank, rope_dim, n_positions, interleaved, (hipStream_t)stream);
+}
+
+template <int EB>
+int mla_append_paged(const void* q_nope, const void* q_pe, void* Q_out, const void* kv_new, void* ckv_pages, const int* block_table,
+                     const float* cos_table, const float* sin_table, const float* kv_weight, float eps, const float* descale,
+                     const int* seqlens_k, int B, int H, int n_new, int n_pages, int page_size, int max_pages_per_seq, int kv_lora_rank,
+                     int rope_dim, int n_positions, int interleaved, const MlaAppendStrides& s, void* stream)
+{
+    if (mla_append_null(q_nope, q_pe, Q_out, H, kv_new, ckv_pages, cos_table, sin_table, kv_weight, seqlens_k) || !block_table)
+        return FA2_ERR_NULL_POINTER;
+    if (B <= 0 || n_new <= 0 || n_pages <= 0 || page_size <= 0 || max_pages_per_seq <= 0 || H < 0) return FA2_ERR_INVALID_SHAPE;
+    if (page_size % kDecodeTile) return FA2_ERR_INVALID_SHAPE;
+    // the paged MLA decode's capacity limit: what this call writes, that call must be able to read
+    if ((long long)max_pages_per_seq * page_size > 0x7fffffffLL - (kDecodeMaxSplits + 2) * kDecodeKB) return FA2_ERR_INVALID_SHAPE;
+    MlaAppendArgs a{};
+    a.q_nope = q_nope; a.q_pe = q_pe; a.Qout = Q_out; a.kv = kv_new; a.C = ckv_pages; a.cos = cos_table; a.sin = sin_table;
+    a.w = kv_weight; a.eps = eps; a.seqlens = seqlens_k; a.block_table = block_table; a.descale = descale;
+    a.B = B; a.H = Q_out ? H : 0; a.n_new = n_new; a.Ncap = max_pages_per_seq * page_size;
+    a.n_pages = n_pages; a.page_size = page_size; a.max_pages = max_pages_per_seq;
+    a.nb = s.nb; a.nh = s.nh; a.nt = s.nt; a.pb = s.pb; a.ph = s.ph; a.pt = s.pt; a.kb = s.kb; a.kt = s.kt;
+    return mla_append_run<true, EB>(a, kv_lora_rank, rope_dim, n_positions, interleaved, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -250,18 +323,10 @@ int fa2_mla_kv_append(const void* q_nope, const void* q_pe, void* Q_out, const v
                       long long q_pe_stride_b, long long q_pe_stride_h, long long q_pe_stride_t,
                       long long kv_stride_b, long long kv_stride_t, void* stream)
 {
-    if (fa2::mla_append_null(q_nope, q_pe, Q_out, H, kv_new, ckv_cache, cos_table, sin_table, kv_weight, seqlens_k)) return FA2_ERR_NULL_POINTER;
-    if (B <= 0 || n_new <= 0 || kv_capacity <= 0 || H < 0) return FA2_ERR_INVALID_SHAPE;
-    // the MLA decode's limit: one sequence, one buffer resource of 1152-byte rows
-    if ((long long)kv_capacity * fa2::kMlaAppRow * 2 > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;
-    fa2::MlaAppendArgs a{};
-    a.q_nope = q_nope; a.q_pe = q_pe; a.Qout = Q_out; a.kv = kv_new; a.C = ckv_cache; a.cos = cos_table; a.sin = sin_table;
-    a.w = kv_weight; a.eps = eps; a.seqlens = seqlens_k;
-    a.B = B; a.H = Q_out ? H : 0; a.n_new = n_new; a.Ncap = kv_capacity;
-    a.nb = q_nope_stride_b; a.nh = q_nope_stride_h; a.nt = q_nope_stride_t;
-    a.pb = q_pe_stride_b; a.ph = q_pe_stride_h; a.pt = q_pe_stride_t;
-    a.kb = kv_stride_b; a.kt = kv_stride_t;
-    return fa2::mla_append_run<false>(a, kv_lora_rank, rope_dim, n_positions, interleaved, (hipStream_t)stream);
+    return fa2::mla_append_contiguous<2>(q_nope, q_pe, Q_out, kv_new, ckv_cache, cos_table, sin_table, kv_weight, eps, nullptr, seqlens_k, B, H,
+                                         n_new, kv_capacity, kv_lora_rank, rope_dim, n_positions, interleaved,
+                                         {q_nope_stride_b, q_nope_stride_h, q_nope_stride_t, q_pe_stride_b, q_pe_stride_h, q_pe_stride_t,
+                                          kv_stride_b, kv_stride_t}, stream);
 }
 
 int fa2_mla_kv_append_paged(const void* q_nope, const void* q_pe, void* Q_out, const void* kv_new, void* ckv_pages,
@@ -275,21 +340,44 @@ int fa2_mla_kv_append_paged(const void* q_nope, const void* q_pe, void* Q_out, c
                             long long q_pe_stride_b, long long q_pe_stride_h, long long q_pe_stride_t,
                             long long kv_stride_b, long long kv_stride_t, void* stream)
 {
-    if (fa2::mla_append_null(q_nope, q_pe, Q_out, H, kv_new, ckv_pages, cos_table, sin_table, kv_weight, seqlens_k) || !block_table)
-        return FA2_ERR_NULL_POINTER;
-    if (B <= 0 || n_new <= 0 || n_pages <= 0 || page_size <= 0 || max_pages_per_seq <= 0 || H < 0) return FA2_ERR_INVALID_SHAPE;
-    if (page_size % fa2::kDecodeTile) return FA2_ERR_INVALID_SHAPE;
-    // the paged MLA decode's capacity limit: what this call writes, that call must be able to read
-    if ((long long)max_pages_per_seq * page_size > 0x7fffffffLL - (fa2::kDecodeMaxSplits + 2) * fa2::kDecodeKB) return FA2_ERR_INVALID_SHAPE;
-    fa2::MlaAppendArgs a{};
-    a.q_nope = q_nope; a.q_pe = q_pe; a.Qout = Q_out; a.kv = kv_new; a.C = ckv_pages; a.cos = cos_table; a.sin = sin_table;
-    a.w = kv_weight; a.eps = eps; a.seqlens = seqlens_k; a.block_table = block_table;
-    a.B = B; a.H = Q_out ? H : 0; a.n_new = n_new; a.Ncap = max_pages_per_seq * page_size;
-    a.n_pages = n_pages; a.page_size = page_size; a.max_pages = max_pages_per_seq;
-    a.nb = q_nope_stride_b; a.nh = q_nope_stride_h; a.nt = q_nope_stride_t;
-    a.pb = q_pe_stride_b; a.ph = q_pe_stride_h; a.pt = q_pe_stride_t;
-    a.kb = kv_stride_b; a.kt = kv_stride_t;
-    return fa2::mla_append_run<true>(a, kv_lora_rank, rope_dim, n_positions, interleaved, (hipStream_t)stream);
+    return fa2::mla_append_paged<2>(q_nope, q_pe, Q_out, kv_new, ckv_pages, block_table, cos_table, sin_table, kv_weight, eps, nullptr,
+                                    seqlens_k, B, H, n_new, n_pages, page_size, max_pages_per_seq, kv_lora_rank, rope_dim, n_positions,
+                                    interleaved,
+                                    {q_nope_stride_b, q_nope_stride_h, q_nope_stride_t, q_pe_stride_b, q_pe_stride_h, q_pe_stride_t,
+                                     kv_stride_b, kv_stride_t}, stream);
+}
+
+int fa2_mla_kv_append_fp8kv(const void* q_nope, const void* q_pe, void* Q_out, const void* kv_new, void* ckv_cache,
+                            const float* cos_table, const float* sin_table, const float* kv_weight, float eps,
+                            const float* latent_descale, const int* seqlens_k,
+                            int B, int H, int n_new, int kv_capacity, int kv_lora_rank, int rope_dim,
+                            int n_positions, int interleaved,
+                            long long q_nope_stride_b, long long q_nope_stride_h, long long q_nope_stride_t,
+                            long long q_pe_stride_b, long long q_pe_stride_h, long long q_pe_stride_t,
+                            long long kv_stride_b, long long kv_stride_t, void* stream)
+{
+    return fa2::mla_append_contiguous<1>(q_nope, q_pe, Q_out, kv_new, ckv_cache, cos_table, sin_table, kv_weight, eps, latent_descale,
+                                         seqlens_k, B, H, n_new, kv_capacity, kv_lora_rank, rope_dim, n_positions, interleaved,
+                                         {q_nope_stride_b, q_nope_stride_h, q_nope_stride_t, q_pe_stride_b, q_pe_stride_h, q_pe_stride_t,
+                                          kv_stride_b, kv_stride_t}, stream);
+}
+
+int fa2_mla_kv_append_paged_fp8kv(const void* q_nope, const void* q_pe, void* Q_out, const void* kv_new, void* ckv_pages,
+                                  const int* block_table,
+                                  const float* cos_table, const float* sin_table, const float* kv_weight, float eps,
+                                  const float* latent_descale, const int* seqlens_k,
+                                  int B, int H, int n_new, int n_pages, int page_size, int max_pages_per_seq,
+                                  int kv_lora_rank, int rope_dim,
+                                  int n_positions, int interleaved,
+                                  long long q_nope_stride_b, long long q_nope_stride_h, long long q_nope_stride_t,
+                                  long long q_pe_stride_b, long long q_pe_stride_h, long long q_pe_stride_t,
+                                  long long kv_stride_b, long long kv_stride_t, void* stream)
+{
+    return fa2::mla_append_paged<1>(q_nope, q_pe, Q_out, kv_new, ckv_pages, block_table, cos_table, sin_table, kv_weight, eps,
+                                    latent_descale, seqlens_k, B, H, n_new, n_pages, page_size, max_pages_per_seq, kv_lora_rank, rope_dim,
+                                    n_positions, interleaved,
+                                    {q_nope_stride_b, q_nope_stride_h, q_nope_stride_t, q_pe_stride_b, q_pe_stride_h, q_pe_stride_t,
+                                     kv_stride_b, kv_stride_t}, stream);
 }
 
 }  // extern "C"

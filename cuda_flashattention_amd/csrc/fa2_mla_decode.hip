@@ -24,7 +24,24 @@
 // ascending s with ONE rounding to bf16 (fa2_decode_combine.inc's arithmetic at D = 512, without the sink).
 // PAGED: the same body with one resource per tile; the tile's table entry is a scalar load one tile ahead of the loads that need
 // it, clamped to [0, n_pages) before it becomes an address.
+//
+// E4M3 LATENT CACHES (fa2_forward_mla_decode_fp8kv / _paged_fp8kv, include/fa2_mla_fp8_mi355x.h): the same body at EB = 1.  A row
+// is 640 bytes, 512 e4m3 codes then the 64 rotary columns in bf16, with ONE fp32 descale per cache read on the device (NULL: 1).
+// Work split, table walk, exchange, softmax, emit and combine are the ones above; what changes is a wave's slice of a tile:
+//   loads        wave w owns latent bytes [128 w, +128) and rotary bytes [512 + 32 w, +32): lane (key r, half h) issues FOUR
+//                16-byte loads of codes (load j: bytes 128 w + 32 j + 16 h ..+16) and the rotary load: 5 loads, 20 VGPRs a tile.
+//                The prefetch slots keep the raw codes, so kMlaPF8 tiles are in flight where the bf16 body keeps two;
+//   widening     a 16-byte load holds the elements of TWO k-steps (low eight codes: k-step 2 j, high eight: 2 j + 1), widened
+//                to bf16 in VGPRs (exact).  Q^T's fragment of k-step 2 j + u is Q[rho][128 w + 32 j + 16 h + 8 u ..+8];
+//   score        two accumulators, latent (8 MFMAs) and rotary (1 MFMA); what enters the exchange is descale x s_latent +
+//                s_rotary in fp32.  Q is not rescaled: that would round it a second time;
+//   value        the widened chunk of (load j, half h, sub-step u) is chunk 4 j + 2 h + u of row r of the wave's V image.  Every
+//                ds_write_b128 still has 16 consecutive rows and ONE chunk per 16-lane group, as the bf16 body's chunk 2 t + h
+//                has: lds_off<128>'s XOR takes 16 different values on them, 16 different slots of the 256-byte bank row --
+//                conflict-free, which chunk it is does not enter.  The image and its transposed reads are the bf16 ones;
+//   epilogue     descale multiplies the fp32 row piece once, behind 1 / l, before anything is rounded.
 #include "fa2_mla_mi355x.h"
+#include "fa2_mla_fp8_mi355x.h"
 #include "fa2_common.h"
 #include "fa2_launch.h"
 
@@ -38,6 +55,8 @@ constexpr float kMlaLn2 = 0.6931471805599453f;
 constexpr int kMlaLatent = 512, kMlaRope = 64;      // the one accepted (kv_lora_rank, rope_dim)
 constexpr int kMlaRow = kMlaLatent + kMlaRope;      // elements of a cache row and of a Q row
 constexpr int kMlaRowB = 2 * kMlaRow;               // bytes of a cache row
+constexpr int kMlaRowB8 = kMlaLatent + 2 * kMlaRope;      // ... of one with e4m3 latent columns: 640
+constexpr int kMlaPF8 = 4;                          // tiles in flight over such a cache (20 VGPRs each): from the register report, not tuned
 constexpr int kMlaTile = kDecodeTile;               // keys of a tile, rows of a block, and what a split's first key is a multiple of
 constexpr int kMlaWaves = 4;
 constexpr int kMlaKS = kMlaRow / 16 / kMlaWaves;    // 9 k-steps of a wave: 8 latent, 1 rotary
@@ -56,6 +75,7 @@ struct MlaArgs {
     float scale;
     int causal;
     int n_pages, page_size, max_pages;               // paged: C is [n_pages][page_size][576], Ncap = max_pages page_size
+    const float* descale;                            // e4m3 latent columns: the cache holds x / *descale (DEVICE; NULL: 1)
 };
 
 // (a copy of fa2_decode.hip's: that file's helpers sit in its anonymous namespace and its device code is left alone)
@@ -67,11 +87,23 @@ __device__ __forceinline__ bf16x4 mla_bf16x4(const f32x4& v)
     return r;
 }
 
-// PF: tiles in flight ahead of the arithmetic (36 VGPRs each).
-template <bool PAGED, int PF>
+// (fa2_decode.hip's, copied for the same reason) eight OCP e4m3 codes, two words of ascending bytes, as their bf16 values
+__device__ __forceinline__ bf16x8 mla_e4m3x8_to_bf16(uint32_t w0, uint32_t w1)
+{
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+    const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true);
+    const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true);
+    return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// PF: tiles in flight ahead of the arithmetic (36 VGPRs each; 20 at EB = 1).  EB: bytes per latent element, 2 (bf16) or 1 (e4m3).
+template <bool PAGED, int PF, int EB = 2>
 __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
 {
-    static_assert(PF == 1 || PF == 2, "one or two slots");
+    static_assert(EB == 1 || EB == 2, "bf16 or e4m3 latent columns");
+    static_assert(EB == 1 || PF == 1 || PF == 2, "one or two slots");
+    constexpr int ROWB = EB == 2 ? kMlaRowB : kMlaRowB8;      // bytes of a cache row
+    constexpr int NL = EB == 2 ? kMlaKS : 5;                  // 16-byte loads of a lane per tile, the last one the rotary columns
     extern __shared__ __attribute__((aligned(16))) char smem[];      // kMlaWaves V images | two exchange buffers
 
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -111,13 +143,15 @@ __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
     }
 
     // Q^T fragments of the wave's columns: lane (row r, half h) holds Q[rho][col_t + 8 h ..+8], col_t = 128 w + 16 t, 512 + 16 w
+    // (EB = 1: the latent k-step t = 2 j + u takes the columns its half of load j holds, 128 w + 32 j + 16 h + 8 u ..+8)
     const int rho = rb0 + r;
     bf16x8 q[kMlaKS];
     {
         const __bf16* Qg = (const __bf16*)a.Q + (row0 + (rho < M ? rho : 0)) * kMlaRow + 8 * h;
 #pragma unroll
         for (int t = 0; t < kMlaKS; ++t) {
-            q[t] = *reinterpret_cast<const bf16x8*>(Qg + (t < 8 ? 128 * wave + 16 * t : kMlaLatent + 16 * wave));
+            if constexpr (EB == 2) q[t] = *reinterpret_cast<const bf16x8*>(Qg + (t < 8 ? 128 * wave + 16 * t : kMlaLatent + 16 * wave));
+            else q[t] = *reinterpret_cast<const bf16x8*>(Qg + (t < 8 ? 128 * wave + 32 * (t / 2) + 8 * h + 8 * (t % 2) : kMlaLatent + 16 * wave));
             if (rho >= M) q[t] = bf16x8{};
         }
     }
@@ -126,11 +160,11 @@ __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
     if (a.causal) kmax = min(end, rho % a.Nq + len - a.Nq + 1);
     if (rho >= M) kmax = 0;
 
-    const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.C + (PAGED ? 0 : (size_t)b * a.Ncap * kMlaRow)), 0,
-                                                          PAGED ? 0 : end * kMlaRowB, 0x00020000);
-    // the lane's 16 bytes of k-step t: + 32 t below the rotary step
-    const uint32_t koff = (uint32_t)r * kMlaRowB + 256 * wave + 16 * h, roff = (uint32_t)r * kMlaRowB + 2 * kMlaLatent + 32 * wave + 16 * h;
-    u32x4 kf[PF][kMlaKS];
+    const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.C + (PAGED ? 0 : (size_t)b * a.Ncap * ROWB)), 0,
+                                                          PAGED ? 0 : end * ROWB, 0x00020000);
+    // the lane's 16 bytes of latent load t (a k-step; two at EB = 1): + 32 t below the rotary load
+    const uint32_t koff = (uint32_t)r * ROWB + 128 * EB * wave + 16 * h, roff = (uint32_t)r * ROWB + EB * kMlaLatent + 32 * wave + 16 * h;
+    u32x4 kf[PF][NL];
     // PAGED: fa2_decode.hip's table walk with every wave on every tile.  (pg_i, pg_o): page index and row within the page of the
     // tile whose entry is fetched next; (ent, ent_o): the fetched entry and row of the tile that is LOADED next.  A tile with a
     // key indexes the table below max_pages (kb < len <= max_pages page_size); one without reads entry 0 of its sequence, which
@@ -147,15 +181,15 @@ __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
         if constexpr (PAGED) {
             const int page = base < end ? min(max(ent, 0), a.n_pages - 1) : 0;      // the clamp is the contract
             const int rows = __builtin_amdgcn_readfirstlane(max(min(kMlaTile, end - base), 0));
-            const size_t at = ((size_t)page * a.page_size + ent_o) * kMlaRow;      // 64-bit: a pool may exceed 4 GiB
-            const auto cp = __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)a.C + at), 0, rows * kMlaRowB, 0x00020000);
+            const size_t at = ((size_t)page * a.page_size + ent_o) * ROWB;      // 64-bit: a pool may exceed 4 GiB
+            const auto cp = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.C + at), 0, rows * ROWB, 0x00020000);
 #pragma unroll
-            for (int t = 0; t < kMlaKS; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(cp, t < 8 ? koff + 32 * t : roff, 0, 0);
+            for (int t = 0; t < NL; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(cp, t < NL - 1 ? koff + 32 * t : roff, 0, 0);
             return;
         }
-        const uint32_t b0 = (uint32_t)base * kMlaRowB;
+        const uint32_t b0 = (uint32_t)base * ROWB;
 #pragma unroll
-        for (int t = 0; t < kMlaKS; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(c_rsrc, b0 + (t < 8 ? koff + 32 * t : roff), 0, 0);
+        for (int t = 0; t < NL; ++t) kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(c_rsrc, b0 + (t < NL - 1 ? koff + 32 * t : roff), 0, 0);
     };
 
     char* const vimg = smem + wave * kMlaVimg;
@@ -170,6 +204,10 @@ __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
 #pragma unroll
         for (int e = 0; e < 16; ++e) o[c][e] = 0.0f;
     const float sc = a.scale * kLog2e;
+    // the cache's descale: a scalar load, here and not on the host, so that a captured graph sees the value of its replay
+    float ds = 1.0f;
+    if constexpr (EB == 1)
+        if (a.descale) ds = __uint_as_float(__builtin_amdgcn_readfirstlane(*(const mla_const_int*)a.descale));
 
     int kb = begin;
     if constexpr (PAGED) {      // the one division of a workgroup
@@ -179,6 +217,7 @@ __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
     }
     load_tile(kb, 0);
     if constexpr (PAGED) fetch_entry(kb + kMlaTile);
+    if constexpr (EB == 2) {
     if constexpr (PF == 2) {
         load_tile(kb + kMlaTile, 1);
         if constexpr (PAGED) fetch_entry(kb + 2 * kMlaTile);
@@ -198,6 +237,27 @@ __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
 #include "fa2_mla_decode_tile.inc"
         }
     }
+    } else {
+        // PF tiles in flight and a round of ROUND tiles, a multiple of PF and of the two exchange buffers, unrolled: slot i % PF
+        // and buffer i & 1 are constants of the text.  A tile past `end` loads nothing (its resource has no rows there).
+        constexpr int ROUND = PF % 2 ? 2 * PF : PF;
+#pragma unroll
+        for (int i = 1; i < PF; ++i) {
+            load_tile(kb + i * kMlaTile, i);
+            if constexpr (PAGED) fetch_entry(kb + (i + 1) * kMlaTile);
+        }
+        for (; kb < end; kb += ROUND * kMlaTile) {
+#pragma unroll
+            for (int i = 0; i < ROUND; ++i) {
+                if (kb + i * kMlaTile < end) {
+#define MLA_KB (kb + i * kMlaTile)
+#define MLA_SL (i % PF)
+#define MLA_XB (i & 1)
+#include "fa2_mla_decode_tile.inc"
+                }
+            }
+        }
+    }
 
     // every wave holds the same m and l: it normalises and emits its own 128 columns (registers 4 g4 ..+4 of tile c are columns
     // 32 c + 8 g4 + 4 h ..+4 of row rho)
@@ -212,7 +272,7 @@ __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
             for (int g4 = 0; g4 < 4; ++g4) {
                 f32x4 v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = has ? o[c][4 * g4 + e] * inv : 0.0f;
+                for (int e = 0; e < 4; ++e) v[e] = has ? (EB == 2 ? o[c][4 * g4 + e] * inv : o[c][4 * g4 + e] * inv * ds) : 0.0f;
                 emit(rho, 32 * wave + 8 * c + 2 * g4 + h, v, Lrow);
             }
     }
@@ -224,6 +284,12 @@ template <bool PAGED>
 __global__ void __launch_bounds__(256, 2) fa2_mla_decode_split_kernel(MlaArgs a)
 {
     mla_split_body<PAGED, 2>(a);
+}
+
+template <bool PAGED>
+__global__ void __launch_bounds__(256, 2) fa2_mla_decode_fp8_split_kernel(MlaArgs a)
+{
+    mla_split_body<PAGED, kMlaPF8, 1>(a);
 }
 
 // rows x 128 lanes, a lane owns four columns of one row: partials in, ascending s, fp32, one rounding.  fa2_decode_combine.inc's
@@ -292,9 +358,11 @@ struct MlaCall {
     float scale;
     int causal, n_splits;
     void* ws; size_t ws_bytes; void* stream;
+    const float* descale = nullptr;      // fp8 only; never read by the host
 };
 
-int mla_run(const MlaCall& c, bool paged)
+// fp8: the latent columns of the cache are e4m3 codes (a 640-byte row); every check and its order are shared
+int mla_run(const MlaCall& c, bool paged, bool fp8 = false)
 {
     if (!c.Q || !c.C || !c.O || !c.L || (paged && !c.block_table)) return FA2_ERR_NULL_POINTER;
     if (c.B <= 0 || c.H <= 0 || c.q_len <= 0 || !(c.scale > 0.0f)) return FA2_ERR_INVALID_SHAPE;
@@ -307,7 +375,7 @@ int mla_run(const MlaCall& c, bool paged)
     } else {
         if (kv_capacity <= 0) return FA2_ERR_INVALID_SHAPE;
         // one sequence, one buffer resource (a 576-wide row whatever the widths asked for: those are refused below)
-        if ((long long)kv_capacity * kMlaRowB > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;
+        if ((long long)kv_capacity * (fp8 ? kMlaRowB8 : kMlaRowB) > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;
     }
     if (c.n_splits < 0 || c.n_splits > kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
     if ((long long)c.B * c.H * c.q_len > 0x7fffffffLL - kMlaTile) return FA2_ERR_INVALID_SHAPE;      // the rows of O and L
@@ -323,11 +391,17 @@ int mla_run(const MlaCall& c, bool paged)
     a.wsL = n_splits > 1 ? (float*)c.ws + (size_t)n_splits * c.B * c.H * c.q_len * kMlaLatent : nullptr;
     a.B = c.B; a.H = c.H; a.Nq = c.q_len; a.Ncap = kv_capacity; a.n_splits = n_splits;
     a.scale = c.scale; a.causal = c.causal ? 1 : 0;
+    a.descale = fp8 ? c.descale : nullptr;
     if (paged) { a.block_table = c.block_table; a.n_pages = c.n_pages; a.page_size = c.page_size; a.max_pages = c.max_pages; }
     const hipStream_t stream = (hipStream_t)c.stream;
     const unsigned grid = (unsigned)(c.B * mla_row_blocks(c.H, c.q_len) * n_splits);
-    hipError_t e = paged ? launch_lds<fa2_mla_decode_split_kernel<true>>(dim3(grid), dim3(256), kMlaLds, stream, a)
-                         : launch_lds<fa2_mla_decode_split_kernel<false>>(dim3(grid), dim3(256), kMlaLds, stream, a);
+    hipError_t e;
+    if (fp8)
+        e = paged ? launch_lds<fa2_mla_decode_fp8_split_kernel<true>>(dim3(grid), dim3(256), kMlaLds, stream, a)
+                  : launch_lds<fa2_mla_decode_fp8_split_kernel<false>>(dim3(grid), dim3(256), kMlaLds, stream, a);
+    else
+        e = paged ? launch_lds<fa2_mla_decode_split_kernel<true>>(dim3(grid), dim3(256), kMlaLds, stream, a)
+                  : launch_lds<fa2_mla_decode_split_kernel<false>>(dim3(grid), dim3(256), kMlaLds, stream, a);
     if (e == hipSuccess && n_splits > 1) {
         const size_t threads = (size_t)c.B * c.H * c.q_len * kMlaC4;      // < 2^31 x 128: the grid fits
         hipLaunchKernelGGL(fa2_mla_combine_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
@@ -374,6 +448,24 @@ int fa2_forward_mla_decode_paged(const void* Q, const void* ckv_pages, const int
 {
     return fa2::mla_run({Q, ckv_pages, block_table, seqlens_k, O, L, B, H, q_len, 0, n_pages, page_size, max_pages_per_seq, kv_lora_rank,
                          rope_dim, softmax_scale, causal, n_splits, workspace, workspace_bytes, stream}, true);
+}
+
+int fa2_forward_mla_decode_fp8kv(const void* Q, const void* ckv_cache, const float* latent_descale, const int* seqlens_k, void* O,
+                                 float* L, int B, int H, int q_len, int kv_capacity, int kv_lora_rank, int rope_dim,
+                                 float softmax_scale, int causal, int n_splits, void* workspace, size_t workspace_bytes,
+                                 void* stream)
+{
+    return fa2::mla_run({Q, ckv_cache, nullptr, seqlens_k, O, L, B, H, q_len, kv_capacity, 0, 0, 0, kv_lora_rank, rope_dim, softmax_scale,
+                         causal, n_splits, workspace, workspace_bytes, stream, latent_descale}, false, true);
+}
+
+int fa2_forward_mla_decode_paged_fp8kv(const void* Q, const void* ckv_pages, const int* block_table, const float* latent_descale,
+                                       const int* seqlens_k, void* O, float* L, int B, int H, int q_len, int n_pages,
+                                       int page_size, int max_pages_per_seq, int kv_lora_rank, int rope_dim, float softmax_scale,
+                                       int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return fa2::mla_run({Q, ckv_pages, block_table, seqlens_k, O, L, B, H, q_len, 0, n_pages, page_size, max_pages_per_seq, kv_lora_rank,
+                         rope_dim, softmax_scale, causal, n_splits, workspace, workspace_bytes, stream, latent_descale}, true, true);
 }
 
 }  // extern "C"

@@ -1,15 +1,20 @@
 // fa2_mla_decode_tile.inc -- one 32-key tile of the workgroup in mla_split_body (fa2_mla_decode.hip), textually included where
 // the tile loop stands: the tile's first key is MLA_KB, the wave's column slice of its 32 rows waits in kf[MLA_SL], and the
 // partial scores go through exchange buffer MLA_XB.  Behind the first product the slot takes the loads of the tile PF ahead.
-// Included text and not a lambda, like fa2_decode_tile.inc.
-        // the latent part of the slice is this wave's 128 columns of V: lane (key r, half h) holds chunk 2 t + h of row r
-#pragma unroll
-        for (int t = 0; t < 8; ++t) *reinterpret_cast<u32x4*>(vimg + lds_off<128>(r, 2 * t + h)) = kf[MLA_SL][t];
+// Included text and not a lambda, like fa2_decode_tile.inc.  EB = 1 (e4m3 latent columns): the slot holds raw codes and the tile's
+// first product is fa2_mla_decode_fp8_tile.inc; from the exchange on the text is shared.
         f32x16 s;
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[e] = 0.0f;
+        if constexpr (EB == 2) {
+        // the latent part of the slice is this wave's 128 columns of V: lane (key r, half h) holds chunk 2 t + h of row r
+#pragma unroll
+        for (int t = 0; t < 8; ++t) *reinterpret_cast<u32x4*>(vimg + lds_off<128>(r, 2 * t + h)) = kf[MLA_SL][t];
 #pragma unroll
         for (int t = 0; t < kMlaKS; ++t) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[MLA_SL][t]), q[t], s, 0, 0, 0);
+        } else {
+#include "fa2_mla_decode_fp8_tile.inc"
+        }
         load_tile(MLA_KB + PF * kMlaTile, MLA_SL);
         if constexpr (PAGED) fetch_entry(MLA_KB + (PF + 1) * kMlaTile);      // the table entry of the tile after the loaded one
 

@@ -716,14 +716,41 @@ def mla_decode_workspace(B, H, q_len, kv_capacity, n_splits=0, device="cuda"):
     return torch.empty(need, dtype=torch.uint8, device=device)
 
 
-def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream):
+MLA_FP8_ROW_BYTES = MLA_KV_LORA_RANK + 2 * MLA_ROPE_DIM      # a cache row with e4m3 latent columns: 512 codes, then 64 bf16
+
+
+def _mla_cache_kind(cache, name, latent_descale, ref):
+    """Whether the MLA cache is the e4m3 one -- a torch.uint8 tensor whose last dimension is 640 bytes; the dtype alone routes the
+    call -- after the checks of latent_descale: one fp32 element on the device, read there when the kernel runs, and an error beside
+    a bf16 cache."""
+    fp8 = isinstance(cache, torch.Tensor) and cache.dtype == torch.uint8
+    row = MLA_FP8_ROW_BYTES if fp8 else MLA_KV_LORA_RANK + MLA_ROPE_DIM
+    if not isinstance(cache, torch.Tensor) or cache.dim() != 3 or cache.shape[-1] != row or cache.dtype not in (torch.bfloat16, torch.uint8):
+        raise ValueError(f"{name}: expected a bf16 3-d tensor whose last dimension is {MLA_KV_LORA_RANK + MLA_ROPE_DIM} ({MLA_KV_LORA_RANK} "
+                         f"latent columns followed by {MLA_ROPE_DIM} rotary ones), or a torch.uint8 one whose last dimension is "
+                         f"{MLA_FP8_ROW_BYTES} ({MLA_KV_LORA_RANK} e4m3 codes followed by {MLA_ROPE_DIM} bf16), got "
+                         f"{(tuple(cache.shape), cache.dtype) if isinstance(cache, torch.Tensor) else type(cache).__name__}")
+    if latent_descale is not None:
+        if not fp8:
+            raise ValueError(f"latent_descale: a descale belongs to a torch.uint8 cache of {MLA_FP8_ROW_BYTES}-byte rows; {name} is bf16 and "
+                             "holds its own values")
+        if not isinstance(latent_descale, torch.Tensor) or latent_descale.dtype != torch.float32 or latent_descale.numel() != 1:
+            raise ValueError("latent_descale: expected an fp32 tensor of one element on the cache's device (the kernels read it on the "
+                             "device when they run), got "
+                             f"{(tuple(latent_descale.shape), latent_descale.dtype) if isinstance(latent_descale, torch.Tensor) else type(latent_descale).__name__}")
+        if not latent_descale.is_cuda or latent_descale.device != ref.device:
+            raise ValueError(f"latent_descale is on {latent_descale.device}, expected {ref.device}")
+    return fp8
+
+
+def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream, latent_descale=None):
     """flash_attention_2_mla_decode (block_table None) and _paged: one set of checks for both."""
     row, name = MLA_KV_LORA_RANK + MLA_ROPE_DIM, "ckv_cache" if block_table is None else "ckv_pages"
-    for n, t, dims in (("Q", Q, 4), (name, cache, 3)):
-        if not isinstance(t, torch.Tensor) or t.dim() != dims or t.shape[-1] != row or t.dtype != torch.bfloat16:
-            raise ValueError(f"{n}: expected a bf16 {dims}-d tensor whose last dimension is {row} ({MLA_KV_LORA_RANK} latent columns "
-                             f"followed by {MLA_ROPE_DIM} rotary ones), got "
-                             f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if not isinstance(Q, torch.Tensor) or Q.dim() != 4 or Q.shape[-1] != row or Q.dtype != torch.bfloat16:
+        raise ValueError(f"Q: expected a bf16 4-d tensor whose last dimension is {row} ({MLA_KV_LORA_RANK} latent columns "
+                         f"followed by {MLA_ROPE_DIM} rotary ones), got "
+                         f"{(tuple(Q.shape), Q.dtype) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
+    fp8 = _mla_cache_kind(cache, name, latent_descale, Q)
     B, H, Nq, _ = Q.shape
     if min(B, H, Nq) < 1 or cache.shape[0] < 1 or cache.shape[1] < 1:
         raise ValueError(f"Q {tuple(Q.shape)}, {name} {tuple(cache.shape)}: every dimension must be at least 1")
@@ -731,7 +758,7 @@ def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits,
         raise ValueError(f"n_splits: {n_splits!r}, expected an int in 1..{DECODE_MAX_SPLITS}, or 0 for the default")
     if block_table is None:
         if cache.shape[0] != B:
-            raise ValueError(f"{name}: shape {tuple(cache.shape)}, expected ({B}, N_cap, {row}): one slab per sequence of Q")
+            raise ValueError(f"{name}: shape {tuple(cache.shape)}, expected ({B}, N_cap, {cache.shape[-1]}): one slab per sequence of Q")
         kv_capacity = cache.shape[1]
     else:
         if cache.shape[1] % DECODE_PAGE_GRAIN:
@@ -757,7 +784,16 @@ def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits,
         raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (mla_decode_workspace)")
     tail = (MLA_KV_LORA_RANK, MLA_ROPE_DIM, float(softmax_scale), 1 if causal else 0, n_splits, _ptr(workspace),
             0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
-    if block_table is None:
+    if fp8 and block_table is None:
+        st = lib.fa2_forward_mla_decode_fp8kv(Q.data_ptr(), cache.data_ptr(), _ptr(latent_descale), _ptr(seqlens_k), O.data_ptr(),
+                                              L.data_ptr(), B, H, Nq, kv_capacity, *tail)
+        check(st, "fa2_forward_mla_decode_fp8kv")
+    elif fp8:
+        st = lib.fa2_forward_mla_decode_paged_fp8kv(Q.data_ptr(), cache.data_ptr(), block_table.data_ptr(), _ptr(latent_descale),
+                                                    _ptr(seqlens_k), O.data_ptr(), L.data_ptr(), B, H, Nq, cache.shape[0], cache.shape[1],
+                                                    block_table.shape[1], *tail)
+        check(st, "fa2_forward_mla_decode_paged_fp8kv")
+    elif block_table is None:
         st = lib.fa2_forward_mla_decode(Q.data_ptr(), cache.data_ptr(), _ptr(seqlens_k), O.data_ptr(), L.data_ptr(), B, H, Nq, kv_capacity, *tail)
         check(st, "fa2_forward_mla_decode")
     else:
@@ -768,7 +804,7 @@ def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits,
 
 
 def flash_attention_2_mla_decode(Q, ckv_cache, seqlens_k=None, *, softmax_scale, causal=True, n_splits=0, O=None, L=None,
-                                 workspace=None, stream=None):
+                                 workspace=None, stream=None, latent_descale=None):
     """O, L = a decode step of multi-head latent attention in absorbed form (fa2_forward_mla_decode, include/fa2_mla_mi355x.h):
     multi-query attention over ONE latent cache row per token.  Q [B, H, N_q, 576] bf16 (per head q_nope W_UK, 512 columns, then
     q_rope, 64 columns), ckv_cache [B, N_cap, 576] bf16 (the 512-wide compressed KV followed by the 64-wide rotary key).  The score
@@ -778,19 +814,27 @@ def flash_attention_2_mla_decode(Q, ckv_cache, seqlens_k=None, *, softmax_scale,
     seqlens_k, causal (bottom-right), rows without a key (O = 0, L = -inf), rows past a length (anything, NaN included), n_splits,
     workspace and graph capture are flash_attention_2_decode's: n_splits=0 is mla_decode_num_splits(B, H, N_q, N_cap), the workspace
     mla_decode_workspace(B, H, N_q, N_cap, n_splits).  The cache and Q are produced by mla_kv_cache_append.
-    Not covered: e4m3 caches, sinks, windows, ragged Q, merge_states_forward on the 512-wide O, a backward, other latent widths."""
-    return _mla_call(Q, ckv_cache, None, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream)
+    E4M3 LATENT CACHE (fa2_forward_mla_decode_fp8kv, include/fa2_mla_fp8_mi355x.h): ckv_cache torch.uint8 [B, N_cap, 640] -- the dtype
+    alone routes the call.  cache[..., :512].view(torch.float8_e4m3fn) are the latent columns' codes, cache[..., 512:].view(
+    torch.bfloat16) the 64 rotary columns as they are in the bf16 row.  latent_descale: fp32 device tensor of ONE element (None:
+    1.0), read on the device when the kernel runs; the cache holds x / latent_descale, and everything above holds on the dequantised
+    row.  Q, O, L, n_splits and the workspace are unchanged.  latent_descale beside a bf16 cache is a ValueError.
+    Not covered: per-token or per-block scales, fp8 Q, sinks, windows, ragged Q, merge_states_forward on the 512-wide O, a backward,
+    other latent widths."""
+    return _mla_call(Q, ckv_cache, None, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream, latent_descale)
 
 
 def flash_attention_2_mla_decode_paged(Q, ckv_pages, block_table, seqlens_k=None, *, softmax_scale, causal=True, n_splits=0, O=None,
-                                       L=None, workspace=None, stream=None):
+                                       L=None, workspace=None, stream=None, latent_descale=None):
     """flash_attention_2_mla_decode over a pool of pages (fa2_forward_mla_decode_paged): ckv_pages [n_pages, page_size, 576] bf16,
     page_size a multiple of 32, block_table int32 [B, max_pages] on the device as flash_attention_2_decode_paged describes it
     (shared pages, entries past a length never read, an entry in use clamped to [0, n_pages)).  The capacity is max_pages x
-    page_size; with the same n_splits the result is bit for bit flash_attention_2_mla_decode's on the gathered cache."""
+    page_size; with the same n_splits the result is bit for bit flash_attention_2_mla_decode's on the gathered cache.
+    ckv_pages torch.uint8 [n_pages, page_size, 640] with latent_descale is the e4m3 pool (fa2_forward_mla_decode_paged_fp8kv), as
+    flash_attention_2_mla_decode describes the row."""
     if block_table is None:
         raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
-    return _mla_call(Q, ckv_pages, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream)
+    return _mla_call(Q, ckv_pages, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream, latent_descale)
 
 
 class ExtendRaggedPlan:
@@ -1581,7 +1625,8 @@ def _mla_source_arg(x, name, shape, how):
     return strides
 
 
-def _mla_append_call(q_nope, q_pe, kv_new, cache, block_table, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream):
+def _mla_append_call(q_nope, q_pe, kv_new, cache, block_table, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream,
+                     latent_descale=None):
     """mla_kv_cache_append (block_table None) and _paged: one set of checks for both."""
     rank, rope, row = MLA_KV_LORA_RANK, MLA_ROPE_DIM, MLA_KV_LORA_RANK + MLA_ROPE_DIM
     name = "ckv_cache" if block_table is None else "ckv_pages"
@@ -1594,14 +1639,12 @@ def _mla_append_call(q_nope, q_pe, kv_new, cache, block_table, cos, sin, kv_weig
         nope_strides = _mla_source_arg(q_nope, "q_nope", (B, None, n_new, rank), f"[{B}, H, {n_new}, {rank}] (the absorbed q_nope W_UK; a view)")
         H = q_nope.shape[1]
         pe_strides = _mla_source_arg(q_pe, "q_pe", (B, H, n_new, rope), f"[{B}, {H}, {n_new}, {rope}] (a view, e.g. x[..., 128:].permute(0, 2, 1, 3))")
-    if not isinstance(cache, torch.Tensor) or cache.dim() != 3 or cache.shape[-1] != row or cache.dtype != torch.bfloat16:
-        raise ValueError(f"{name}: expected a bf16 3-d tensor whose last dimension is {row}, got "
-                         f"{(tuple(cache.shape), cache.dtype) if isinstance(cache, torch.Tensor) else type(cache).__name__}")
+    fp8 = _mla_cache_kind(cache, name, latent_descale, kv_new)
     if cache.shape[0] < 1 or cache.shape[1] < 1:
         raise ValueError(f"{name}: shape {tuple(cache.shape)}, every dimension must be at least 1")
     if block_table is None:
         if cache.shape[0] != B:
-            raise ValueError(f"{name}: shape {tuple(cache.shape)}, expected ({B}, N_cap, {row}): one slab per sequence of kv_new")
+            raise ValueError(f"{name}: shape {tuple(cache.shape)}, expected ({B}, N_cap, {cache.shape[-1]}): one slab per sequence of kv_new")
         capacity = cache.shape[1]
     else:
         if cache.shape[1] % DECODE_PAGE_GRAIN:
@@ -1632,7 +1675,14 @@ def _mla_append_call(q_nope, q_pe, kv_new, cache, block_table, cos, sin, kv_weig
     head = (_ptr(q_nope), _ptr(q_pe), _ptr(Q_out), kv_new.data_ptr(), cache.data_ptr())
     mid = (cos.data_ptr(), sin.data_ptr(), kv_weight.data_ptr(), float(eps), seqlens_k.data_ptr(), B, H, n_new)
     tail = (rank, rope, n_positions, flag, *nope_strides, *pe_strides, *kv_strides, _stream_ptr(stream))
-    if block_table is None:
+    if fp8:
+        mid = mid[:4] + (_ptr(latent_descale),) + mid[4:]
+    if fp8 and block_table is None:
+        check(lib.fa2_mla_kv_append_fp8kv(*head, *mid, capacity, *tail), "fa2_mla_kv_append_fp8kv")
+    elif fp8:
+        check(lib.fa2_mla_kv_append_paged_fp8kv(*head, block_table.data_ptr(), *mid, cache.shape[0], cache.shape[1], block_table.shape[1], *tail),
+              "fa2_mla_kv_append_paged_fp8kv")
+    elif block_table is None:
         check(lib.fa2_mla_kv_append(*head, *mid, capacity, *tail), "fa2_mla_kv_append")
     else:
         check(lib.fa2_mla_kv_append_paged(*head, block_table.data_ptr(), *mid, cache.shape[0], cache.shape[1], block_table.shape[1], *tail),
@@ -1641,7 +1691,7 @@ def _mla_append_call(q_nope, q_pe, kv_new, cache, block_table, cos, sin, kv_weig
 
 
 def mla_kv_cache_append(q_nope, q_pe, kv_new, ckv_cache, cos, sin, kv_weight, eps, seqlens_k, *, interleaved=False, Q_out=None,
-                        stream=None):
+                        stream=None, latent_descale=None):
     """The producer of the latent cache and of the Q that flash_attention_2_mla_decode takes (fa2_mla_kv_append,
     include/fa2_mla_append_mi355x.h): ONE launch writes the n_new newest tokens' cache rows, row[:512] = RMSNorm(c_kv; kv_weight,
     eps) (the models' kv_a_layernorm, over the 512 latent columns only) and row[512:] = rotate(k_pe, pos), and returns Q_out
@@ -1658,20 +1708,28 @@ def mla_kv_cache_append(q_nope, q_pe, kv_new, ckv_cache, cos, sin, kv_weight, ep
     lengths AFTER the append), a row is written iff 0 <= pos < N_cap, EVERY Q_out row is written (+0.0 in all 576 columns for a
     dropped position).  ARITHMETIC: norm_rope_kv_cache_append_ragged's norm at d = 512 (the butterfly runs over 64 lanes) and
     rope_kv_cache_append's rotation, every product and sum one fp32 rounding, one rounding to bf16.  Q_out is allocated when not
-    given -- the ONLY allocation; pass one for graph capture.  Q_out overlapping an input is undefined."""
-    return _mla_append_call(q_nope, q_pe, kv_new, ckv_cache, None, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream)
+    given -- the ONLY allocation; pass one for graph capture.  Q_out overlapping an input is undefined.
+    E4M3 LATENT CACHE (fa2_mla_kv_append_fp8kv, include/fa2_mla_fp8_mi355x.h): ckv_cache torch.uint8 [B, N_cap, 640], the row
+    flash_attention_2_mla_decode describes; the dtype alone routes the call.  The norm is rounded to bf16 as above and THEN stored
+    as e4m3(clamp(y / latent_descale, +-448)), round to nearest even: the latent bytes are the quantisation of what the bf16 call
+    writes, the rotary bytes and Q_out are its bits.  latent_descale: fp32 device tensor of one element (None: 1.0), read on the
+    device; beside a bf16 cache it is a ValueError."""
+    return _mla_append_call(q_nope, q_pe, kv_new, ckv_cache, None, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream,
+                            latent_descale)
 
 
 def mla_kv_cache_append_paged(q_nope, q_pe, kv_new, ckv_pages, block_table, cos, sin, kv_weight, eps, seqlens_k, *, interleaved=False,
-                              Q_out=None, stream=None):
+                              Q_out=None, stream=None, latent_descale=None):
     """mla_kv_cache_append into a pool of pages (fa2_mla_kv_append_paged), the pool flash_attention_2_mla_decode_paged reads:
     ckv_pages bf16 [n_pages, page_size, 576], page_size a multiple of 32, block_table int32 [B, max_pages] on the device, the
     capacity max_pages * page_size (the tables need that many rows).  A token whose table entry lies outside [0, n_pages) has its
     cache row DROPPED; its Q_out rows are still written: Q depends on the position alone.  PAGES WRITTEN BY ONE CALL MUST BELONG
-    TO ONE SEQUENCE EACH.  Everything else is mla_kv_cache_append's."""
+    TO ONE SEQUENCE EACH.  Everything else is mla_kv_cache_append's, the torch.uint8 pool [n_pages, page_size, 640] with
+    latent_descale included (fa2_mla_kv_append_paged_fp8kv)."""
     if block_table is None:
         raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
-    return _mla_append_call(q_nope, q_pe, kv_new, ckv_pages, block_table, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream)
+    return _mla_append_call(q_nope, q_pe, kv_new, ckv_pages, block_table, cos, sin, kv_weight, eps, seqlens_k, interleaved, Q_out, stream,
+                            latent_descale)
 
 
 def kv_cache_append_ragged(K_new, V_new, K_cache, V_cache, cu_seqlens_q_or_plan, seqlens_k, k_descale=None, v_descale=None, stream=None):
