@@ -11,6 +11,8 @@ from .ops import flash_attention_2_extend, flash_attention_2_extend_paged, exten
 from .ops import flash_attention_2_extend_ragged, flash_attention_2_extend_ragged_paged  # noqa: F401
 from .ops import ExtendRaggedPlan, extend_ragged_plan, extend_ragged_num_splits, extend_ragged_workspace  # noqa: F401
 from .ops import flash_attention_2_mla_decode, flash_attention_2_mla_decode_paged, mla_decode_num_splits, mla_decode_workspace  # noqa: F401
+from .ops import flash_attention_2_mla_decode_sparse, flash_attention_2_mla_decode_sparse_paged  # noqa: F401
+from .ops import mla_sparse_num_splits, mla_sparse_workspace  # noqa: F401
 from .ops import kv_cache_append, kv_cache_append_paged  # noqa: F401
 from .ops import rope_kv_cache_append, rope_kv_cache_append_paged  # noqa: F401
 from .ops import rope_kv_cache_append_ragged, rope_kv_cache_append_ragged_paged  # noqa: F401

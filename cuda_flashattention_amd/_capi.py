@@ -22,6 +22,7 @@ ROPE_NORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_rop
 MLA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_mi355x.h")
 MLA_APPEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_append_mi355x.h")
 MLA_FP8_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_fp8_mi355x.h")
+MLA_SPARSE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fa2_mla_sparse_mi355x.h")
 
 FA2_OK = 0
 FA2_DTYPE_BF16 = 0
@@ -175,6 +176,15 @@ MLA_FP8_SIGNATURES = {
     "fa2_mla_kv_append_paged_fp8kv": (_i, [_vp] * 9 + [_f, _vp, _vp] + [_i] * 10 + [_ll] * 8 + [_vp]),
 }
 
+# include/fa2_mla_sparse_mi355x.h, the same library: the MLA decode over the cache rows an int32 index tensor [B][q_len][topk]
+# names (logical key positions, one row of indices for all heads of a token).  The tables above stay pinned to their headers.
+MLA_SPARSE_SIGNATURES = {
+    "fa2_mla_sparse_num_splits": (_i, [_i] * 6),
+    "fa2_mla_sparse_workspace_bytes": (_sz, [_i] * 7),
+    "fa2_forward_mla_decode_sparse": (_i, [_vp] * 6 + [_i] * 7 + [_f, _i, _i, _vp, _sz, _vp]),
+    "fa2_forward_mla_decode_sparse_paged": (_i, [_vp] * 7 + [_i] * 9 + [_f, _i, _i, _vp, _sz, _vp]),
+}
+
 
 class FA2Error(RuntimeError):
     def __init__(self, status, where):
@@ -203,7 +213,7 @@ def lib():
                                   + list(EXTEND_SIGNATURES.items()) + list(EXTEND_RAGGED_SIGNATURES.items())
                                   + list(ROPE_RAGGED_SIGNATURES.items()) + list(ROPE_NORM_SIGNATURES.items())
                                   + list(MLA_SIGNATURES.items()) + list(MLA_APPEND_SIGNATURES.items())
-                                  + list(MLA_FP8_SIGNATURES.items())):
+                                  + list(MLA_FP8_SIGNATURES.items()) + list(MLA_SPARSE_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -42,6 +42,7 @@
 //   epilogue     descale multiplies the fp32 row piece once, behind 1 / l, before anything is rounded.
 #include "fa2_mla_mi355x.h"
 #include "fa2_mla_fp8_mi355x.h"
+#include "fa2_mla_sparse_mi355x.h"
 #include "fa2_common.h"
 #include "fa2_launch.h"
 
@@ -76,6 +77,7 @@ struct MlaArgs {
     int causal;
     int n_pages, page_size, max_pages;               // paged: C is [n_pages][page_size][576], Ncap = max_pages page_size
     const float* descale;                            // e4m3 latent columns: the cache holds x / *descale (DEVICE; NULL: 1)
+    const int* indices; int topk;                    // sparse: [B][Nq][topk] logical key positions, one row for all heads of a token
 };
 
 // (a copy of fa2_decode.hip's: that file's helpers sit in its anonymous namespace and its device code is left alone)
@@ -95,6 +97,9 @@ __device__ __forceinline__ bf16x8 mla_e4m3x8_to_bf16(uint32_t w0, uint32_t w1)
     const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true);
     return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
+
+// the tile's visibility predicate over consecutive keys: positions [0, kmax) of the lane's row
+#define MLA_VISIBLE(e) (MLA_KB + acc_row(e, h) < kmax)
 
 // PF: tiles in flight ahead of the arithmetic (36 VGPRs each; 20 at EB = 1).  EB: bytes per latent element, 2 (bf16) or 1 (e4m3).
 template <bool PAGED, int PF, int EB = 2>
@@ -277,6 +282,182 @@ __device__ __forceinline__ void mla_split_body(const MlaArgs& a)
             }
     }
 }
+#undef MLA_VISIBLE
+
+// SPARSE (fa2_forward_mla_decode_sparse / _paged): the rows of a tile are the cache rows that 32 consecutive SLOTS of the token's
+// index row name.  Loads and the index pipeline are this body's; from the first product on a tile is fa2_mla_decode_tile.inc.
+// One workgroup = (sequence b, query token i, block of 32 heads, split of the slot list): the index row belongs to the token, so
+// a row block never mixes tokens.  bit r of a tile's live mask: slot t0 + r names a live key (workgroup-uniform: every wave
+// ballots the same 32 indices).
+#define MLA_VISIBLE(e) ((vis >> acc_row(e, 0)) & 1u)
+
+template <bool PAGED, int EB = 2>      // EB: the tile text's; bf16 rows only here
+__device__ __forceinline__ void mla_sparse_body(const MlaArgs& a)
+{
+    static_assert(EB == 2, "bf16 latent columns");
+    // tiles of ROWS in flight ahead of the arithmetic, 36 VGPRs each as in mla_split_body<., 2>: what the register report leaves
+    // at two workgroups per CU.  The depth, and the distances of the index and table fetches below, are UNTUNED: nothing of this
+    // pipeline has been measured against another depth.
+    constexpr int PF = 2;
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // kMlaWaves V images | two exchange buffers
+
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int HB = (a.H + kMlaTile - 1) / kMlaTile;    // head blocks of a token
+    const int bid = blockIdx.x;
+    const int split = bid % a.n_splits, hb0 = bid / a.n_splits % HB * kMlaTile, tok = bid / (a.n_splits * HB);
+    const int b = tok / a.Nq, i = tok - b * a.Nq;
+    const int Hb = min(a.H - hb0, kMlaTile);           // the block's live heads
+
+    int len = a.Ncap;                                  // the clamp is the contract
+    if (a.seqlens) len = min(max(__builtin_amdgcn_readfirstlane(a.seqlens[b]), 0), a.Ncap);
+    // index j is live iff 0 <= j < jmax (bottom-right causal: j <= i + len - N_q)
+    const int jmax = a.causal ? min(len, i + len - a.Nq + 1) : len;
+    // the split's slots: host values only
+    const int per = (a.topk + a.n_splits - 1) / a.n_splits;
+    const int chunk = (per + kMlaTile - 1) / kMlaTile * kMlaTile;
+    const int begin = split * chunk;                   // <= topk + n_splits kMlaTile: no overflow
+    const int end = min(begin + chunk, a.topk);
+
+    const size_t R = (size_t)a.B * a.H * a.Nq;         // rows of O, L and of one split's partials
+    // (mla_split_body's emit at this body's rows: a shared function moved the dense kernels' registers)
+    const auto emit = [&](int head, int c4, f32x4 o, float Lrow) {
+        const size_t gr = ((size_t)b * a.H + head) * a.Nq + i;
+        if (a.n_splits > 1) {
+            *reinterpret_cast<f32x4*>(a.wsO + ((size_t)split * R + gr) * kMlaLatent + 4 * c4) = o;
+            if (c4 == 0) a.wsL[(size_t)split * R + gr] = Lrow;
+        } else {
+            *reinterpret_cast<bf16x4*>((__bf16*)a.O + gr * kMlaLatent + 4 * c4) = mla_bf16x4(o);
+            if (c4 == 0) a.L[gr] = Lrow;
+        }
+    };
+
+    if (begin >= end || jmax <= 0) {      // no slot, or no index can be live: workgroup-uniform, and no barrier met
+        for (int idx = tid; idx < Hb * kMlaC4; idx += 256) emit(hb0 + idx / kMlaC4, idx % kMlaC4, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, -INFINITY);
+        return;
+    }
+
+    // Q^T fragments as in mla_split_body: lane (row r, half h) holds Q[b][head][i][col_t + 8 h ..+8]; heads >= H are zero
+    const int head = hb0 + r;
+    bf16x8 q[kMlaKS];
+    {
+        const __bf16* Qg = (const __bf16*)a.Q + (((size_t)b * a.H + (head < a.H ? head : 0)) * a.Nq + i) * kMlaRow + 8 * h;
+#pragma unroll
+        for (int t = 0; t < kMlaKS; ++t) {
+            q[t] = *reinterpret_cast<const bf16x8*>(Qg + (t < 8 ? 128 * wave + 16 * t : kMlaLatent + 16 * wave));
+            if (head >= a.H) q[t] = bf16x8{};
+        }
+    }
+
+    // contiguous: one resource per sequence, ending at len rows; a dead slot's offset lies past every resource (zeros, no traffic)
+    const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.C + (PAGED ? 0 : (size_t)b * a.Ncap * kMlaRowB)), 0,
+                                                          PAGED ? 0 : len * kMlaRowB, 0x00020000);
+    const uint32_t kcol = 256 * wave + 16 * h, rcol = 2 * kMlaLatent + 32 * wave + 16 * h;      // the lane's bytes within a row
+    u32x4 kf[PF][kMlaKS];
+    uint32_t msk[PF];      // the live masks of the tiles in the slots
+
+    // INDEX PIPELINE.  Lane r (of both halves, of every wave) owns slot t0 + r of a tile.  With tile k in the first product:
+    //   j_a = index of tile k + 2 (its rows are loaded now), j_b = index of tile k + 3, and the index of tile k + 4 is fetched;
+    //   paged: (ent, rem) = table entry and row within the page of tile k + 2, fetched one tile ago; fetch_entry then fetches
+    //   those of tile k + 3 from j_b.
+    // So an index is two tiles old when a table entry or a row address is made of it and a table entry one tile old: no tile
+    // waits on an index or table load it issued itself.  The index fetch stands ahead of the row loads so that waiting for it
+    // (vmcnt counts in order) does not wait for them.
+    const int* const idx = a.indices + ((size_t)b * a.Nq + i) * a.topk;
+    // a slot past the split's last is dead; its lane re-reads the last slot (an unconditional load: a load that a branch may
+    // skip makes every later wait count a guess, and the compiler then waits for everything)
+    const auto fetch_index = [&](int t0) {
+        const int t = t0 + r, v = idx[min(t, end - 1)];
+        return t < end ? v : -1;
+    };
+    const auto is_live = [&](int j) { return (uint32_t)j < (uint32_t)jmax; };      // jmax > 0 here
+    int j_a = fetch_index(begin), j_b = fetch_index(begin + kMlaTile);
+    int ent = 0, rem = 0;
+    const int* const table = a.block_table + (size_t)b * a.max_pages;
+    const auto fetch_entry = [&](int) {                // PAGED only: of the tile j_a names, for live lanes only
+        const uint32_t pg = (uint32_t)j_a / (uint32_t)a.page_size;      // < max_pages for a live j
+        rem = j_a - (int)pg * a.page_size;
+        ent = is_live(j_a) ? table[pg] : 0;
+    };
+    const auto load_tile = [&](int base, int sl) {
+        const int j_n = fetch_index(base + 2 * kMlaTile);
+        const bool live = is_live(j_a);
+        msk[sl] = (uint32_t)__builtin_amdgcn_ballot_w64(live);      // both halves hold the same 32 bits
+        if constexpr (PAGED) {
+            // up to 32 pages a tile: a 64-bit address per lane (a pool may exceed 4 GiB), the loads under the live predicate
+            const int page = min(max(ent, 0), a.n_pages - 1);       // the clamp is the contract
+            const char* const row = (const char*)a.C + ((size_t)page * a.page_size + rem) * kMlaRowB;
+#pragma unroll
+            for (int t = 0; t < kMlaKS; ++t) kf[sl][t] = u32x4{0, 0, 0, 0};
+            if (live) {
+#pragma unroll
+                for (int t = 0; t < kMlaKS; ++t)
+                    kf[sl][t] = *reinterpret_cast<const u32x4*>(row + (t < kMlaKS - 1 ? kcol + 32 * t : rcol));
+            }
+        } else {
+            const uint32_t at = live ? (uint32_t)j_a * kMlaRowB : 0x80000000u;      // a resource has at most INT_MAX bytes
+#pragma unroll
+            for (int t = 0; t < kMlaKS; ++t)
+                kf[sl][t] = __builtin_amdgcn_raw_buffer_load_b128(c_rsrc, at + (t < kMlaKS - 1 ? kcol + 32 * t : rcol), 0, 0);
+        }
+        j_a = j_b;
+        j_b = j_n;
+    };
+
+    char* const vimg = smem + wave * kMlaVimg;
+    const int gi = lane & 15, qq = gi >> 2, pp = gi & 3, c0 = 16 * ((lane >> 4) & 1);      // mla_split_body's transposed reads
+
+    float m = -INFINITY, l = 0.0f;
+    f32x16 o[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[c][e] = 0.0f;
+    const float sc = a.scale * kLog2e;
+    constexpr float ds = 1.0f;      // (the tile text's e4m3 branch names it; EB = 2 discards that branch)
+
+    int kb = begin;                                    // a SLOT from here on
+    if constexpr (PAGED) fetch_entry(kb);
+    load_tile(kb, 0);
+    if constexpr (PAGED) fetch_entry(kb + kMlaTile);
+    load_tile(kb + kMlaTile, 1);
+    if constexpr (PAGED) fetch_entry(kb + 2 * kMlaTile);
+    // two tiles per round as in mla_split_body.  begin and end are host values: every wave meets every barrier
+    for (; kb < end; kb += 2 * kMlaTile) {
+        {
+            const uint32_t vis = msk[0] >> (4 * h);
+#define MLA_KB kb
+#define MLA_SL 0
+#define MLA_XB 0
+#include "fa2_mla_decode_tile.inc"
+        }
+        if (kb + kMlaTile < end) {
+            const uint32_t vis = msk[1] >> (4 * h);
+#define MLA_KB (kb + kMlaTile)
+#define MLA_SL 1
+#define MLA_XB 1
+#include "fa2_mla_decode_tile.inc"
+        }
+    }
+
+    // mla_split_body's epilogue at this body's rows
+    l = half_sum(l);
+    const bool has = l > 0.0f;                  // a select: a row without a live slot in this split
+    const float inv = 1.0f / l;
+    const float Lrow = has ? (m + __builtin_amdgcn_logf(l)) * kMlaLn2 : -INFINITY;
+    if (head < a.H) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = has ? o[c][4 * g4 + e] * inv : 0.0f;
+                emit(head, 32 * wave + 8 * c + 2 * g4 + h, v, Lrow);
+            }
+    }
+}
+#undef MLA_VISIBLE
 
 }  // namespace
 
@@ -290,6 +471,12 @@ template <bool PAGED>
 __global__ void __launch_bounds__(256, 2) fa2_mla_decode_fp8_split_kernel(MlaArgs a)
 {
     mla_split_body<PAGED, kMlaPF8, 1>(a);
+}
+
+template <bool PAGED>
+__global__ void __launch_bounds__(256, 2) fa2_mla_decode_sparse_kernel(MlaArgs a)
+{
+    mla_sparse_body<PAGED>(a);
 }
 
 // rows x 128 lanes, a lane owns four columns of one row: partials in, ascending s, fp32, one rounding.  fa2_decode_combine.inc's
@@ -359,6 +546,7 @@ struct MlaCall {
     int causal, n_splits;
     void* ws; size_t ws_bytes; void* stream;
     const float* descale = nullptr;      // fp8 only; never read by the host
+    const int* indices = nullptr; int topk = 0;      // sparse only; never read by the host
 };
 
 // fp8: the latent columns of the cache are e4m3 codes (a 640-byte row); every check and its order are shared
@@ -404,6 +592,53 @@ int mla_run(const MlaCall& c, bool paged, bool fp8 = false)
                   : launch_lds<fa2_mla_decode_split_kernel<false>>(dim3(grid), dim3(256), kMlaLds, stream, a);
     if (e == hipSuccess && n_splits > 1) {
         const size_t threads = (size_t)c.B * c.H * c.q_len * kMlaC4;      // < 2^31 x 128: the grid fits
+        hipLaunchKernelGGL(fa2_mla_combine_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
+        e = hipGetLastError();
+    }
+    return e == hipSuccess ? FA2_OK : FA2_ERR_HIP_BASE - (int)e;
+}
+
+inline long long mla_sparse_groups(int B, int H, int q_len) { return (long long)B * q_len * ((H + kMlaTile - 1) / kMlaTile); }
+
+// the sparse calls: mla_run's checks in mla_run's order, with indices among the pointers and topk among the shapes
+int mla_sparse_run(const MlaCall& c, bool paged)
+{
+    if (!c.Q || !c.C || !c.indices || !c.O || !c.L || (paged && !c.block_table)) return FA2_ERR_NULL_POINTER;
+    if (c.B <= 0 || c.H <= 0 || c.q_len <= 0 || c.topk <= 0 || !(c.scale > 0.0f)) return FA2_ERR_INVALID_SHAPE;
+    int kv_capacity = c.kv_capacity;
+    if (paged) {
+        if (c.n_pages <= 0 || c.page_size <= 0 || c.max_pages <= 0 || c.page_size % kMlaTile) return FA2_ERR_INVALID_SHAPE;
+        if ((long long)c.max_pages * c.page_size > 0x7fffffffLL - (kDecodeMaxSplits + 2) * kDecodeKB) return FA2_ERR_INVALID_SHAPE;
+        kv_capacity = c.max_pages * c.page_size;
+    } else {
+        if (kv_capacity <= 0) return FA2_ERR_INVALID_SHAPE;
+        if ((long long)kv_capacity * kMlaRowB > 0x7fffffffLL) return FA2_ERR_INVALID_SHAPE;      // one sequence, one buffer resource
+    }
+    // slots are ints, and the kernel forms begin = split chunk <= topk + n_splits kMlaTile and kb + 4 kMlaTile
+    if (c.topk > 0x7fffffff - (kDecodeMaxSplits + 2) * kDecodeKB) return FA2_ERR_INVALID_SHAPE;
+    if (c.n_splits < 0 || c.n_splits > kDecodeMaxSplits) return FA2_ERR_INVALID_SHAPE;
+    if ((long long)c.B * c.H * c.q_len > 0x7fffffffLL - kMlaTile) return FA2_ERR_INVALID_SHAPE;      // the rows of O and L
+    if (c.kv_lora_rank != kMlaLatent || c.rope_dim != kMlaRope) return FA2_ERR_UNSUPPORTED_HEAD_DIM;
+    const int n_splits = c.n_splits ? c.n_splits : fa2_mla_sparse_num_splits(c.B, c.H, c.q_len, c.topk, c.kv_lora_rank, c.rope_dim);
+    const long long groups = mla_sparse_groups(c.B, c.H, c.q_len);
+    if (groups > 0x7fffffffLL / n_splits) return FA2_ERR_INVALID_SHAPE;
+    const size_t need = n_splits > 1 ? mla_partials_bytes(c.B, c.H, c.q_len, n_splits) : 0;
+    if (n_splits > 1 && !need) return FA2_ERR_INVALID_SHAPE;
+    if (n_splits > 1 && (!c.ws || c.ws_bytes < need || ((uintptr_t)c.ws & 15))) return FA2_ERR_WORKSPACE;
+    MlaArgs a{};
+    a.Q = c.Q; a.C = c.C; a.seqlens = c.seqlens_k; a.O = c.O; a.L = c.L;
+    a.indices = c.indices; a.topk = c.topk;
+    a.wsO = (float*)c.ws;
+    a.wsL = n_splits > 1 ? (float*)c.ws + (size_t)n_splits * c.B * c.H * c.q_len * kMlaLatent : nullptr;
+    a.B = c.B; a.H = c.H; a.Nq = c.q_len; a.Ncap = kv_capacity; a.n_splits = n_splits;
+    a.scale = c.scale; a.causal = c.causal ? 1 : 0;
+    if (paged) { a.block_table = c.block_table; a.n_pages = c.n_pages; a.page_size = c.page_size; a.max_pages = c.max_pages; }
+    const hipStream_t stream = (hipStream_t)c.stream;
+    const unsigned grid = (unsigned)(groups * n_splits);
+    hipError_t e = paged ? launch_lds<fa2_mla_decode_sparse_kernel<true>>(dim3(grid), dim3(256), kMlaLds, stream, a)
+                         : launch_lds<fa2_mla_decode_sparse_kernel<false>>(dim3(grid), dim3(256), kMlaLds, stream, a);
+    if (e == hipSuccess && n_splits > 1) {      // the dense decode's combine: the partials have its layout
+        const size_t threads = (size_t)c.B * c.H * c.q_len * kMlaC4;
         hipLaunchKernelGGL(fa2_mla_combine_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
         e = hipGetLastError();
     }
@@ -466,6 +701,43 @@ int fa2_forward_mla_decode_paged_fp8kv(const void* Q, const void* ckv_pages, con
 {
     return fa2::mla_run({Q, ckv_pages, block_table, seqlens_k, O, L, B, H, q_len, 0, n_pages, page_size, max_pages_per_seq, kv_lora_rank,
                          rope_dim, softmax_scale, causal, n_splits, workspace, workspace_bytes, stream, latent_descale}, true, true);
+}
+
+int fa2_mla_sparse_num_splits(int B, int H, int q_len, int topk, int kv_lora_rank, int rope_dim)
+{
+    if (B <= 0 || H <= 0 || q_len <= 0 || topk <= 0 || kv_lora_rank != fa2::kMlaLatent || rope_dim != fa2::kMlaRope) return 1;
+    const long long groups = fa2::mla_sparse_groups(B, H, q_len);
+    const long long fill = (fa2::kDecodeCUs + groups - 1) / groups;      // smallest s with groups x s >= the CU count
+    const long long room = std::max(1, topk / fa2::kDecodeMinSplitKeys);  // the family's floor, unmeasured for a gather
+    return (int)std::min<long long>(std::min(fill, room), fa2::kDecodeMaxSplits);
+}
+
+size_t fa2_mla_sparse_workspace_bytes(int B, int H, int q_len, int topk, int kv_lora_rank, int rope_dim, int n_splits)
+{
+    if (B <= 0 || H <= 0 || q_len <= 0 || topk <= 0 || kv_lora_rank != fa2::kMlaLatent || rope_dim != fa2::kMlaRope) return 0;
+    if (n_splits < 0 || n_splits > fa2::kDecodeMaxSplits) return 0;
+    if (n_splits == 0) n_splits = fa2_mla_sparse_num_splits(B, H, q_len, topk, kv_lora_rank, rope_dim);
+    if (n_splits == 1) return 0;
+    return fa2::mla_partials_bytes(B, H, q_len, n_splits);
+}
+
+int fa2_forward_mla_decode_sparse(const void* Q, const void* ckv_cache, const int* indices, const int* seqlens_k, void* O, float* L,
+                                  int B, int H, int q_len, int topk, int kv_capacity, int kv_lora_rank, int rope_dim,
+                                  float softmax_scale, int causal, int n_splits, void* workspace, size_t workspace_bytes,
+                                  void* stream)
+{
+    return fa2::mla_sparse_run({Q, ckv_cache, nullptr, seqlens_k, O, L, B, H, q_len, kv_capacity, 0, 0, 0, kv_lora_rank, rope_dim,
+                                softmax_scale, causal, n_splits, workspace, workspace_bytes, stream, nullptr, indices, topk}, false);
+}
+
+int fa2_forward_mla_decode_sparse_paged(const void* Q, const void* ckv_pages, const int* block_table, const int* indices,
+                                        const int* seqlens_k, void* O, float* L, int B, int H, int q_len, int topk, int n_pages,
+                                        int page_size, int max_pages_per_seq, int kv_lora_rank, int rope_dim, float softmax_scale,
+                                        int causal, int n_splits, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return fa2::mla_sparse_run({Q, ckv_pages, block_table, seqlens_k, O, L, B, H, q_len, 0, n_pages, page_size, max_pages_per_seq,
+                                kv_lora_rank, rope_dim, softmax_scale, causal, n_splits, workspace, workspace_bytes, stream, nullptr,
+                                indices, topk}, true);
 }
 
 }  // extern "C"

@@ -3,6 +3,8 @@
 // partial scores go through exchange buffer MLA_XB.  Behind the first product the slot takes the loads of the tile PF ahead.
 // Included text and not a lambda, like fa2_decode_tile.inc.  EB = 1 (e4m3 latent columns): the slot holds raw codes and the tile's
 // first product is fa2_mla_decode_fp8_tile.inc; from the exchange on the text is shared.
+// MLA_VISIBLE(e): whether key acc_row(e, h) of the tile is visible to the lane's row.  The including body defines it: a key
+// position below kmax (mla_split_body), a bit of the tile's live mask (mla_sparse_body, whose load_tile gathers the rows).
         f32x16 s;
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[e] = 0.0f;
@@ -42,7 +44,7 @@
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             s[e] *= sc;
-            mx = MLA_KB + acc_row(e, h) < kmax ? fmaxf(mx, s[e]) : mx;
+            mx = MLA_VISIBLE(e) ? fmaxf(mx, s[e]) : mx;
         }
         mx = half_max(mx);
         const float m_new = fmaxf(m, mx);
@@ -53,7 +55,7 @@
         bf16x8 p[2];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const float pe = MLA_KB + acc_row(e, h) < kmax ? __builtin_amdgcn_exp2f(s[e] - m0) : 0.0f;
+            const float pe = MLA_VISIBLE(e) ? __builtin_amdgcn_exp2f(s[e] - m0) : 0.0f;
             ps += pe;
             p[e >> 3][e & 7] = (__bf16)pe;
         }

@@ -743,8 +743,9 @@ def _mla_cache_kind(cache, name, latent_descale, ref):
     return fp8
 
 
-def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream, latent_descale=None):
-    """flash_attention_2_mla_decode (block_table None) and _paged: one set of checks for both."""
+def _mla_args(Q, cache, block_table, seqlens_k, softmax_scale, n_splits, latent_descale=None):
+    """The checks every MLA decode call makes of Q, the cache, the table, the lengths, the scale and n_splits ->
+    (fp8, kv_capacity, name of the cache argument)."""
     row, name = MLA_KV_LORA_RANK + MLA_ROPE_DIM, "ckv_cache" if block_table is None else "ckv_pages"
     if not isinstance(Q, torch.Tensor) or Q.dim() != 4 or Q.shape[-1] != row or Q.dtype != torch.bfloat16:
         raise ValueError(f"Q: expected a bf16 4-d tensor whose last dimension is {row} ({MLA_KV_LORA_RANK} latent columns "
@@ -773,15 +774,29 @@ def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits,
         raise ValueError(f"{name} must be a contiguous device tensor on Q's device (got {cache.device}, strides {tuple(cache.stride())})")
     if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)) or not softmax_scale > 0.0:
         raise ValueError(f"softmax_scale: {softmax_scale!r}, expected a positive number (the model's scale: 576 does not tell it)")
+    return fp8, kv_capacity, name
+
+
+def _mla_outputs(Q, O, L, workspace, need, maker):
+    """O [B, H, N_q, 512], L [B, H, N_q] and the workspace of `need` bytes of an MLA decode call: made, or the caller's checked."""
+    B, H, Nq, _ = Q.shape
     O = torch.empty(B, H, Nq, MLA_KV_LORA_RANK, dtype=Q.dtype, device=Q.device) if O is None else \
         _like(O, "O", Q, (B, H, Nq, MLA_KV_LORA_RANK), Q.dtype)
     L = torch.empty(B, H, Nq, dtype=torch.float32, device=Q.device) if L is None else _rows(L, "L", Q, B, H, Nq)
-    lib = _capi.lib()
-    need = lib.fa2_mla_decode_workspace_bytes(B, H, Nq, kv_capacity, MLA_KV_LORA_RANK, MLA_ROPE_DIM, n_splits)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
     if workspace is not None and _nbytes(_workspace_arg(workspace, Q)) < need:
-        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed (mla_decode_workspace)")
+        raise ValueError(f"workspace: {_nbytes(workspace)} bytes, {need} needed ({maker})")
+    return O, L, workspace
+
+
+def _mla_call(Q, cache, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream, latent_descale=None):
+    """flash_attention_2_mla_decode (block_table None) and _paged: one set of checks for both."""
+    fp8, kv_capacity, _ = _mla_args(Q, cache, block_table, seqlens_k, softmax_scale, n_splits, latent_descale)
+    B, H, Nq, _ = Q.shape
+    lib = _capi.lib()
+    need = lib.fa2_mla_decode_workspace_bytes(B, H, Nq, kv_capacity, MLA_KV_LORA_RANK, MLA_ROPE_DIM, n_splits)
+    O, L, workspace = _mla_outputs(Q, O, L, workspace, need, "mla_decode_workspace")
     tail = (MLA_KV_LORA_RANK, MLA_ROPE_DIM, float(softmax_scale), 1 if causal else 0, n_splits, _ptr(workspace),
             0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
     if fp8 and block_table is None:
@@ -835,6 +850,76 @@ def flash_attention_2_mla_decode_paged(Q, ckv_pages, block_table, seqlens_k=None
     if block_table is None:
         raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
     return _mla_call(Q, ckv_pages, block_table, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream, latent_descale)
+
+
+def mla_sparse_num_splits(B, H, q_len, topk):
+    """The split count n_splits=0 stands for in the sparse MLA decode calls (fa2_mla_sparse_num_splits): mla_decode_num_splits'
+    rule on B q_len ceil(H / 32) workgroups, with the slot count topk in place of the capacity."""
+    return _capi.lib().fa2_mla_sparse_num_splits(B, H, q_len, topk, MLA_KV_LORA_RANK, MLA_ROPE_DIM)
+
+
+def mla_sparse_workspace(B, H, q_len, topk, n_splits=0, device="cuda"):
+    """Scratch for flash_attention_2_mla_decode_sparse / _paged (the splits' fp32 partials; empty for one split): allocate once,
+    pass as workspace= (graph capture).  n_splits=0 is mla_sparse_num_splits(B, H, q_len, topk)."""
+    need = _capi.lib().fa2_mla_sparse_workspace_bytes(B, H, q_len, topk, MLA_KV_LORA_RANK, MLA_ROPE_DIM, n_splits)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _mla_sparse_call(Q, cache, block_table, indices, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream):
+    """flash_attention_2_mla_decode_sparse (block_table None) and _paged: _mla_call's checks, and the one of indices."""
+    if isinstance(cache, torch.Tensor) and cache.dtype == torch.uint8:
+        raise ValueError("an e4m3 (torch.uint8) latent cache is not covered by the sparse MLA decode: bf16 caches only")
+    _, kv_capacity, _ = _mla_args(Q, cache, block_table, seqlens_k, softmax_scale, n_splits)
+    B, H, Nq, _ = Q.shape
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32 or indices.dim() != 3 or indices.shape[:2] != (B, Nq) \
+            or indices.shape[2] < 1:
+        raise ValueError(f"indices: expected an int32 tensor [{B}, {Nq}, topk] of logical key positions (one row for all heads of a "
+                         f"token, -1 for padding), got "
+                         f"{(tuple(indices.shape), indices.dtype) if isinstance(indices, torch.Tensor) else type(indices).__name__}")
+    if not indices.is_cuda or not indices.is_contiguous() or indices.device != Q.device:
+        raise ValueError(f"indices must be a contiguous device tensor on Q's device (got {indices.device}, strides {tuple(indices.stride())})")
+    topk = indices.shape[2]
+    lib = _capi.lib()
+    need = lib.fa2_mla_sparse_workspace_bytes(B, H, Nq, topk, MLA_KV_LORA_RANK, MLA_ROPE_DIM, n_splits)
+    O, L, workspace = _mla_outputs(Q, O, L, workspace, need, "mla_sparse_workspace")
+    tail = (MLA_KV_LORA_RANK, MLA_ROPE_DIM, float(softmax_scale), 1 if causal else 0, n_splits, _ptr(workspace),
+            0 if workspace is None else _nbytes(workspace), _stream_ptr(stream))
+    if block_table is None:
+        st = lib.fa2_forward_mla_decode_sparse(Q.data_ptr(), cache.data_ptr(), indices.data_ptr(), _ptr(seqlens_k), O.data_ptr(),
+                                               L.data_ptr(), B, H, Nq, topk, kv_capacity, *tail)
+        check(st, "fa2_forward_mla_decode_sparse")
+    else:
+        st = lib.fa2_forward_mla_decode_sparse_paged(Q.data_ptr(), cache.data_ptr(), block_table.data_ptr(), indices.data_ptr(),
+                                                     _ptr(seqlens_k), O.data_ptr(), L.data_ptr(), B, H, Nq, topk, cache.shape[0],
+                                                     cache.shape[1], block_table.shape[1], *tail)
+        check(st, "fa2_forward_mla_decode_sparse_paged")
+    return O, L
+
+
+def flash_attention_2_mla_decode_sparse(Q, ckv_cache, indices, seqlens_k=None, *, softmax_scale, causal=True, n_splits=0, O=None,
+                                        L=None, workspace=None, stream=None):
+    """flash_attention_2_mla_decode over the cache rows an index tensor names (fa2_forward_mla_decode_sparse,
+    include/fa2_mla_sparse_mi355x.h): indices int32 [B, N_q, topk] on the device, any topk >= 1; entry (b, i, t) is a LOGICAL key
+    position of sequence b, and one row serves all H heads of query token i (a lightning indexer's top-k).  An entry is live iff
+    0 <= j < len_b and, when causal, j <= i + len_b - N_q; anything else (-1 padding, stale or garbage values) contributes nothing
+    and neither its cache row nor its table entry is read.  A duplicate counts once per occurrence.  A row without a live entry
+    has O = 0, L = -inf.  Q, ckv_cache (bf16 only), seqlens_k, O, L, softmax_scale and graph capture are
+    flash_attention_2_mla_decode's; the splits run over the topk slots: n_splits=0 is mla_sparse_num_splits(B, H, N_q, topk), the
+    workspace mla_sparse_workspace(B, H, N_q, topk, n_splits).  With indices = arange and one split the result is
+    flash_attention_2_mla_decode's bit for bit.
+    Not covered: e4m3 caches, physical pool-slot indices, an index row per head, the indexer, sinks, windows, a backward."""
+    return _mla_sparse_call(Q, ckv_cache, None, indices, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream)
+
+
+def flash_attention_2_mla_decode_sparse_paged(Q, ckv_pages, block_table, indices, seqlens_k=None, *, softmax_scale, causal=True,
+                                              n_splits=0, O=None, L=None, workspace=None, stream=None):
+    """flash_attention_2_mla_decode_sparse over a pool of pages (fa2_forward_mla_decode_sparse_paged): ckv_pages and block_table
+    are flash_attention_2_mla_decode_paged's; indices stay LOGICAL positions, position j goes through block_table[b, j //
+    page_size], read for a live j only and clamped to [0, n_pages).  With the same n_splits the result is bit for bit
+    flash_attention_2_mla_decode_sparse's on the gathered cache."""
+    if block_table is None:
+        raise ValueError("block_table must be an int32 device tensor [B, max_pages]")
+    return _mla_sparse_call(Q, ckv_pages, block_table, indices, seqlens_k, softmax_scale, causal, n_splits, O, L, workspace, stream)
 
 
 class ExtendRaggedPlan:
